@@ -5,7 +5,7 @@ Metric (BASELINE.json): G1 scalar-muls/s per MI355X on a batch of 2^20 random (p
 configs[1] — bit-exact vs the CPU path.  A "step" is one pass of the hot path (c12381_g1_mul_batch_dev: scalar-mul
 kernel + inversion/encode kernel) over one batch whose inputs are already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started plainly with --gpus N > 1 (no WORLD_SIZE in the environment) the script becomes the launcher: before anything touches the
@@ -241,10 +241,15 @@ def main():
     ap.add_argument("--sampled-parity", action="store_true", help="compare 64 pairing lanes instead of the whole batch (quick A/B runs)")
     ap.add_argument("--no-clock-probe", action="store_true", help="skip the in-run clock probe (roofline.issue then has no clock)")
     ap.add_argument("--lib", default=None, help="another build of the same C ABI (A/B runs, tools/build_variant.sh); default: the product library")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what each timed leg's last step returned as DIR/<name>.npy (float32 byte values; "
+                         "large outputs as a fixed seeded sample of lanes, DIR/<name>_lanes.npy): rank 0, at most 64 MB in all")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             # nothing in this process has touched the GPU yet (importing torch does not): become the launcher of N fresh ranks
@@ -347,6 +352,22 @@ def main():
             if clocks[name] and probe.last_xcd:
                 xcd_clocks[name] = (probe.last_xcd[0], probe.last_xcd[-1], len(probe.last_xcd))
 
+    dumps = {}                                        # --dump-outputs: name -> array, written after the last timed leg
+
+    def keep(name, buf, width, units, k, seed):
+        """--dump-outputs: the `width`-byte rows of `buf` that the leg's last timed step left there — every row when there are at most k,
+        else lanes 0..7 (the edge inputs) and a sample fixed by `seed` — as float32 byte values (exact), the sampled lanes beside them"""
+        if args.dump_outputs is None or rank != 0:
+            return
+        lanes = np.arange(units)
+        if units > k:
+            pick = np.random.Generator(np.random.PCG64(seed)).choice(units - 8, k - 8, replace=False)
+            lanes = np.concatenate([lanes[:8], 8 + np.sort(pick)])
+            dumps[name + "_lanes"] = lanes.astype(np.float64)
+        torch.cuda.synchronize(dev)                   # the library's stream included
+        rows = buf[: units * width].view(units, width)[torch.from_numpy(lanes).to(dev)]
+        dumps[name] = rows.cpu().numpy().astype(np.float32)
+
     n = 1 << args.log2_batch
     # ---- synthetic inputs, resident in HBM before the timed region
     base_sc_h = make_scalars(1000 + rank, n)
@@ -379,6 +400,7 @@ def main():
     ctx.profile(False)
     if ctx.sync() != 0:
         raise SystemExit("bench: invalid input point reported by the kernels")
+    keep("g1_mul", out, 96, n, 1 << 15, 11)
     probe_clock("g1_mul_kernel", g1_step)
 
     # ================================================================== configs[2]: pairings
@@ -403,6 +425,7 @@ def main():
         ctx.profile(False)
         if ctx.sync() != 0:
             raise SystemExit("bench: invalid input reported by the pairing kernel")
+        keep("pairing", gt, 576, npair, 1 << 11, 12)
         probe_clock("pair", lambda: ctx.pair_dev(npair, p1.data_ptr(), q2.data_ptr(), gt.data_ptr()))
         pair = {"npair": npair, "steps": max(1, args.steps), "elapsed": pel, "kernel_ms": pk_ms, "launches": pk_launches,
                 "p1": p1, "q2": q2, "gt": gt}
@@ -441,6 +464,9 @@ def main():
         ctx.profile(False)
         if ctx.sync() != 0:
             raise SystemExit("bench: invalid input reported by the split kernels")
+        keep("g2_mul", g2_out, 192, ng2, 1 << 11, 13)
+        keep("miller", mil, 576, npair, 1 << 11, 14)
+        keep("fexp", fex, 576, npair, 1 << 11, 14)
         probe_clock("g2_mul2_kernel", lambda: ctx.g2_mul_dev(ng2, g2_in.data_ptr(), g2_sc.data_ptr(), g2_out.data_ptr(), 192))
         probe_clock("miller", lambda: ctx.miller_dev(npair, pair["p1"].data_ptr(), pair["q2"].data_ptr(), mil.data_ptr()))
         probe_clock("fexp", lambda: ctx.gt_op_dev("fexp", npair, mil.data_ptr(), None, fex.data_ptr()))
@@ -528,6 +554,7 @@ def main():
         mel = timed(lambda: ctx.g1_msm_dev(nm, mp_.data_ptr(), ms_.data_ptr(), mo_.data_ptr(), 96), msteps, 0)
         bk_ms, bk_launches = ctx.profile_read(5)
         ctx.profile(False)
+        keep("msm", mo_, 96, 1, 1, 0)
         probe_clock("msm_bucket_kernel", lambda: ctx.g1_msm_dev(nm, mp_.data_ptr(), ms_.data_ptr(), mo_.data_ptr(), 96))
         msm = {"n": nm, "steps": msteps, "elapsed": mel, "bucket_ms": bk_ms, "bucket_launches": bk_launches, "out": mo_.cpu().numpy().tobytes(),
                "reps": reps, "scalars": ms_h, "bases": msm_base_h}
@@ -629,6 +656,7 @@ def main():
         bpk_ms, bpk_launches = ctx.profile_read(4)
         ctx.profile(False)
         ctx.sync()
+        keep("bbs_plus", okb, 1, nb, nb, 0)
         ok_h = okb.cpu().numpy()
         exp_ok = np.ones(nb, dtype=np.uint8); exp_ok[bad_lanes] = 0
         if not (ok_h == exp_ok).all():
@@ -661,6 +689,7 @@ def main():
         torch.cuda.synchronize(dev)
         wel = timed(wire_step, bsteps, 0)
         ctx.sync()
+        keep("bbs_plus_wire", okw, 1, nb, nb, 0)
         okw_h = okw.cpu().numpy()
         if not (okw_h == exp_ok).all():
             raise SystemExit("bench: wire-format BBS+ verdicts differ from the construction (valid signatures / corrupted lanes) — number withheld")
@@ -719,6 +748,16 @@ def main():
             extras["bbs_plus_aggregate"] = {"metric": "BBS+ signatures/s covered by ONE aggregate verdict (optional mode, not in the reference)",
                                             "value": world * bbs["n"] * 2 / el, "unit": "signatures/s", "ms_per_batch": el / 2 * 1e3}
         ctx.sync()
+
+    if dumps:
+        total = sum(a.nbytes for a in dumps.values())
+        if total > 64_000_000:
+            raise SystemExit("bench: --dump-outputs would write %d bytes (limit 64 MB)" % total)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumps.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        print("bench.py: %d arrays, %d bytes -> %s" % (len(dumps), total, args.dump_outputs), file=sys.stderr, flush=True)
+        dumps.clear()
 
     # ================================================================== parity and CPU baselines (outside every timed region)
     # kind: the compiled reference (oracle/_ref) or the C port — said on every parity object, never silent
