@@ -6,7 +6,8 @@
 // Design for CDNA4: one (point, scalar) per lane, homogeneous projective coordinates with
 // the Renes–Costello–Batina COMPLETE formulas for a = 0 — no exceptional cases, hence no
 // data-dependent branch and no wavefront divergence (P+P, P+(-P), infinity operands and
-// zero digits all go through the same instruction stream).  GLV: k = k0 + k1*x^2 with
+// zero digits all go through the same instruction stream) — for the MSM, the additions and the fallback; the batched scalar
+// multiplication runs Jacobian formulas over a co-Z affine table (g1_scalar_mul).  GLV: k = k0 + k1*x^2 with
 // [x^2](x,y) = (beta*x, -y), so both 128-bit halves share ONE table of 8 multiples of P (signed
 // 4-bit windows) that lives in HBM as one contiguous 1408-byte record per lane.
 #pragma once
@@ -75,6 +76,93 @@ C12381_HD void g1_endo_x2(g1p& r, const g1p& p) {
     fp_mul(r.x, p.x, beta);
     fp_neg(r.y, p.y);
     r.z = p.z;
+}
+
+// ------------------------------------------------------------------ Jacobian a = 0 (incomplete: the scalar multiplication's fast path)
+// (X:Y:Z) stands for (X/Z^2, Y/Z^3).  None of these formulas reads the curve constant b, so they hold unchanged on every curve
+// y^2 = x^3 + b', in particular on the isomorphic curve of a co-Z table (g1_scalar_mul).  Z = 0 is the point at infinity, and it
+// is absorbing: a doubling gives Z3 = 2YZ, a mixed addition Z3 = Z1 H.
+struct g1j { fp x, y, z; };
+
+// P = 2P (dbl-2009-l): 2M + 5S, 7 reductions; the linear terms -A - C, -2D and -8C ride in the reductions (fp_*_inj), so every output
+// coordinate is normalised.  Operand limb bound: <= 2^28 + slack (reduction outputs).
+C12381_HD void g1j_dbl(g1j& p) {
+    fp a, b, c, d, e, xb, x3, y3, z3, y2;
+    const int32_t cm1 = fp_opaque_const(-1), cm4 = fp_opaque_const(-4), cm8 = fp_opaque_const(-8);
+    fp_raw_dbl(y2, p.y);
+    fp_mul(z3, y2, p.z);                                 // Z3 = 2YZ
+    fp_sqr(a, p.x);                                      // A = X^2
+    fp_sqr(b, p.y);                                      // B = Y^2
+    fp_sqr(c, b);                                        // C = B^2
+    fp_add(xb, p.x, b);
+    fp_sqr_inj(d, xb, [&](int i, int64_t& acc) { fp_inj(acc, a, i, cm1); fp_inj(acc, c, i, cm1); },
+               C12381_BV(a.vb + c.vb), C12381_BV(a.lb + c.lb));                       // D/2 = (X + B)^2 - A - C = 2XB
+    fp_mul_small(e, a, 3);                               // E = 3A
+    fp_sqr_inj(x3, e, [&](int i, int64_t& acc) { fp_inj(acc, d, i, cm4); }, C12381_BV(4 * d.vb), C12381_BV(4 * d.lb));   // X3 = E^2 - 2D
+    fp_raw_dbl(d, d);
+    fp_sub(d, d, x3);
+    fp_mul_inj(y3, e, d, [&](int i, int64_t& acc) { fp_inj(acc, c, i, cm8); }, C12381_BV(8 * c.vb), C12381_BV(8 * c.lb));  // Y3 = E (D - X3) - 8C
+    p.x = x3; p.y = y3; p.z = z3;
+}
+
+// r = p + (x2, y2) with (x2, y2) affine on the same curve (madd-2004-hmv): 6M + 3S and one lazily reduced pair, 10 reductions.
+// Exceptional (Z3 = 0) when p = +-(x2, y2) or p is infinity; the caller selects around d = 0 and an accumulator at infinity.
+C12381_HD void g1j_madd(g1j& r, const g1j& p, const fp& x2, const fp& y2) {
+    fp zz, zzz, u2, s2, h, s, hh, hhh, v, x3, y3, z3, vx;
+    const int32_t cm1 = fp_opaque_const(-1), cm2 = fp_opaque_const(-2);
+    fp_sqr(zz, p.z);
+    fp_mul(u2, x2, zz);                                  // U2 = x2 Z1^2
+    fp_mul(zzz, p.z, zz);
+    fp_mul(s2, y2, zzz);                                 // S2 = y2 Z1^3
+    fp_sub(h, u2, p.x);                                  // H = U2 - X1
+    fp_sub(s, s2, p.y);                                  // s = S2 - Y1
+    fp_mul(z3, p.z, h);                                  // Z3 = Z1 H
+    fp_sqr(hh, h);
+    fp_mul(hhh, h, hh);
+    fp_mul(v, p.x, hh);                                  // V = X1 H^2
+    fp_sqr_inj(x3, s, [&](int i, int64_t& acc) { fp_inj(acc, hhh, i, cm1); fp_inj(acc, v, i, cm2); },
+               C12381_BV(hhh.vb + 2 * v.vb), C12381_BV(hhh.lb + 2 * v.lb));         // X3 = s^2 - H^3 - 2V
+    fp_sub(vx, v, x3);
+    fp_mul2<true>(y3, s, vx, p.y, hhh);                  // Y3 = s (V - X3) - Y1 H^3
+    r.x = x3; r.y = y3; r.z = z3;
+}
+
+// Co-Z steps of the table (Meloni): points that share one Z are passed without it.
+// DBLU: (x, y) affine -> 2P = (x2, y2) and P = (x1, y1), both with Z = 2y.  1M + 5S.
+C12381_HD void g1j_dblu(fp& x2, fp& y2, fp& x1, fp& y1, const fp& x, const fp& y) {
+    fp a, b, c, d, e, xb, dd;
+    const int32_t cm1 = fp_opaque_const(-1), cm4 = fp_opaque_const(-4), cm8 = fp_opaque_const(-8);
+    fp_sqr(a, x);
+    fp_sqr(b, y);
+    fp_sqr(c, b);
+    fp_add(xb, x, b);
+    fp_sqr_inj(d, xb, [&](int i, int64_t& acc) { fp_inj(acc, a, i, cm1); fp_inj(acc, c, i, cm1); },
+               C12381_BV(a.vb + c.vb), C12381_BV(a.lb + c.lb));                       // D/2 = 2 x y^2
+    fp_mul_small(e, a, 3);
+    fp_sqr_inj(x2, e, [&](int i, int64_t& acc) { fp_inj(acc, d, i, cm4); }, C12381_BV(4 * d.vb), C12381_BV(4 * d.lb));
+    fp_raw_dbl(dd, d);
+    fp_sub(dd, dd, x2);
+    fp_mul_inj(y2, e, dd, [&](int i, int64_t& acc) { fp_inj(acc, c, i, cm8); }, C12381_BV(8 * c.vb), C12381_BV(8 * c.lb));
+    fp_mul_small(x1, d, 2);                              // x (2y)^2 = D
+    fp_mul_small(y1, c, 8);                              // y (2y)^3 = 8C
+}
+// ZADDU: P = (x1, y1), Q = (x2, y2) on one Z  ->  P + Q = (x3, y3) and P = (x1, y1) both on Z' = Z h, h = x1 - x2 returned
+// lazily.  4M + 2S (Z' itself is not formed).  h = 0 (Q = +-P) gives Z' = 0.
+C12381_HD void g1j_zaddu(fp& x3, fp& y3, fp& x1, fp& y1, fp& h, const fp& x2, const fp& y2) {
+    fp c, w1, w2, sd, dw, a1, wx;
+    const int32_t cm1 = fp_opaque_const(-1);
+    fp_sub(h, x1, x2);
+    fp_sqr(c, h);
+    fp_mul(w1, x1, c);                                   // W1 = x1 h^2
+    fp_mul(w2, x2, c);
+    fp_sub(sd, y1, y2);
+    fp_sub(dw, w1, w2);
+    fp_mul(a1, y1, dw);                                  // A1 = y1 h^3
+    fp_sqr_inj(x3, sd, [&](int i, int64_t& acc) { fp_inj(acc, w1, i, cm1); fp_inj(acc, w2, i, cm1); },
+               C12381_BV(w1.vb + w2.vb), C12381_BV(w1.lb + w2.lb));                 // X3 = (y1 - y2)^2 - W1 - W2
+    fp_sub(wx, w1, x3);
+    fp_mul_inj(y3, sd, wx, [&](int i, int64_t& acc) { fp_inj(acc, a1, i, cm1); }, C12381_BV(a1.vb), C12381_BV(a1.lb));  // Y3 = (y1 - y2)(W1 - X3) - A1
+    x1 = w1; y1 = a1;
 }
 
 // ------------------------------------------------------------------ scalars
@@ -329,8 +417,10 @@ C12381_HDN void g1_glv_small_scalar_term(g1p& acc, const g1p& base) {
     g1_add(acc, s2);
 }
 
-// [k]P for an AFFINE input point (x, y) or infinity.  `lane_tab` = this lane's table record (G1_TAB_DWORDS).
-C12381_HD void g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf, const uint32_t (&kin)[8], int32_t* lane_tab) {
+// [k]P for an AFFINE input point (x, y) or infinity with the complete formulas: no exceptional case.  `lane_tab` = this lane's table
+// record (G1_TAB_DWORDS).  Out of line: g1_scalar_mul falls back to it for the rare lanes its incomplete formulas cannot serve, and
+// the main loop's register allocation does not pay for the second copy.
+C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, bool p_is_inf, const uint32_t (&kin)[8], int32_t* lane_tab) {
     uint32_t k[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) k[i] = kin[i];
@@ -409,6 +499,188 @@ C12381_HD void g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf
         g1_add_digit(acc, lane_tab, glv_digit(kb1, w), true);
 #endif
     }
+}
+
+// ------------------------------------------------------------------ co-Z affine table (the fast path)
+// Record of entry j: x | y | beta x | 2 pad dwords (44 dwords, as the complete path's X | Y | Z).  The pads of entries 1..7 carry the
+// 14 limbs of Z_T, the shared Z of the table.  While the table is built, entry j holds (X_j, Y_j, h_j) instead: jP on its own Z and the
+// factor h_j that carries Z_j to Z_(j+1).
+constexpr double G1_REC_LB = 268435456.0 + 8.0;
+C12381_HD void tab_store_rec(int32_t* ent, const fp& a, const fp& b, const fp& c, double vb_cap) {
+    (void)vb_cap;
+    C12381_BOUNDS(for (const fp* e : {&a, &b, &c}) { if (e->vb > vb_cap) bounds_fail("tab_store_rec value bound", e->vb, vb_cap);
+                                                      if (e->lb > G1_REC_LB) bounds_fail("tab_store_rec limb bound", e->lb, G1_REC_LB); })
+    int32_t w[G1_ENT_DWORDS];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) { w[i] = a.l[i]; w[NL + i] = b.l[i]; w[2 * NL + i] = c.l[i]; }
+    w[42] = 0; w[43] = 0;
+    q4* dst = reinterpret_cast<q4*>(ent);
+#pragma unroll
+    for (int i = 0; i < G1_ENT_DWORDS / 4; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; dst[i] = t; }
+}
+// dwords [4 q0, 4 q0 + 4 nq) of a record into w
+template <int Q0, int NQ>
+C12381_HD void tab_load_q4(int32_t (&w)[G1_ENT_DWORDS], const int32_t* ent) {
+    const q4* src = reinterpret_cast<const q4*>(ent);
+#pragma unroll
+    for (int i = Q0; i < Q0 + NQ; ++i) { q4 t = src[i]; w[4 * i] = t.v[0]; w[4 * i + 1] = t.v[1]; w[4 * i + 2] = t.v[2]; w[4 * i + 3] = t.v[3]; }
+}
+C12381_HD void rec_field(fp& a, const int32_t (&w)[G1_ENT_DWORDS], int off, double vb_cap) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) a.l[i] = w[off + i];
+    (void)vb_cap;
+    C12381_BOUNDS(a.lb = G1_REC_LB; a.vb = vb_cap; check_actual(a, "rec_field");)
+}
+C12381_HD void tab_load_rec(fp& a, fp& b, fp& c, const int32_t* ent, double vb_cap) {
+    int32_t w[G1_ENT_DWORDS];
+    tab_load_q4<0, G1_ENT_DWORDS / 4>(w, ent);
+    rec_field(a, w, 0, vb_cap); rec_field(b, w, NL, vb_cap); rec_field(c, w, 2 * NL, vb_cap);
+}
+// what an addition reads: x and y (dwords 0..27), or y and beta x (dwords 12..43)
+C12381_HD void tab_load_xy(fp& x, fp& y, const int32_t* ent) {
+    int32_t w[G1_ENT_DWORDS];
+    tab_load_q4<0, 7>(w, ent);
+    rec_field(x, w, 0, 4.0); rec_field(y, w, NL, 4.0);
+}
+C12381_HD void tab_load_ybx(fp& y, fp& bx, const int32_t* ent) {
+    int32_t w[G1_ENT_DWORDS];
+    tab_load_q4<3, 8>(w, ent);
+    rec_field(y, w, NL, 4.0); rec_field(bx, w, 2 * NL, 4.0);
+}
+struct alignas(8) d2 { int32_t v[2]; };
+C12381_HD void tab_store_zt(int32_t* lane_tab, const fp& zt) {
+#pragma unroll
+    for (int j = 0; j < NL / 2; ++j) { d2 t; t.v[0] = zt.l[2 * j]; t.v[1] = zt.l[2 * j + 1]; *reinterpret_cast<d2*>(lane_tab + j * G1_ENT_DWORDS + 42) = t; }
+}
+C12381_HD void tab_load_zt(fp& zt, const int32_t* lane_tab) {
+#pragma unroll
+    for (int j = 0; j < NL / 2; ++j) { const d2 t = *reinterpret_cast<const d2*>(lane_tab + j * G1_ENT_DWORDS + 42); zt.l[2 * j] = t.v[0]; zt.l[2 * j + 1] = t.v[1]; }
+    C12381_BOUNDS(zt.lb = G1_REC_LB; zt.vb = 4.0; check_actual(zt, "tab_load_zt");)
+}
+
+// acc += sign(d) T[|d|], or its image (beta x, -y) under the endomorphism, given the entry's x (beta x) and y.  d = 0 keeps acc (the
+// addition with entry 1 is computed and dropped); an accumulator at infinity (acc_inf) takes the looked-up point with Z = 1.
+C12381_HD void g1j_add_digit(g1j& acc, bool& acc_inf, const fp& x, const fp& y, int d, bool endo) {
+    fp ny, ys, one;
+    fp_neg(ny, y);
+    fp_select(ys, (d < 0) != endo, ny, y);
+    g1j r;
+    g1j_madd(r, acc, x, ys);
+    fp_one(one);
+    fp_select(r.x, acc_inf, x, r.x); fp_select(r.y, acc_inf, ys, r.y); fp_select(r.z, acc_inf, one, r.z);
+    const bool keep = d == 0;
+    fp_select(acc.x, keep, acc.x, r.x); fp_select(acc.y, keep, acc.y, r.y); fp_select(acc.z, keep, acc.z, r.z);
+    acc_inf = acc_inf && keep;
+}
+
+// [k]P for an AFFINE input point (x, y) or infinity, result in homogeneous coordinates.  `lane_tab` = this lane's table record
+// (G1_TAB_DWORDS).  Returns true for a lane that took the complete path.
+// Jacobian doublings and mixed additions over an affine table: a table whose entries share one Jacobian Z = Z_T is affine on the
+// isomorphic curve E': y^2 = x^3 + 4 Z_T^6 ((x, y) -> (Z_T^2 x, Z_T^3 y)); the loop runs there (its formulas never read b), and
+// (X : Y : Z) on E' is (X : Y : Z Z_T) on E.  The endomorphism commutes with the map (beta Z^2 x = Z^2 beta x).  Co-Z additions
+// (Meloni) give the shared Z without an inversion: DBLU, fourteen ZADDUs, and one backward pass that carries entry j from Z_j to Z_T.
+// The formulas are incomplete: an addition with acc = +-T, or a ZADDU whose operands coincide (points of small order), gives Z = 0,
+// and Z = 0 survives every later step.  So one test at the end suffices: a lane whose final Z is 0 mod p while the accumulator is
+// not the point at infinity recomputes its product with g1_scalar_mul_complete.  No lane of a random subgroup batch does.
+C12381_HD bool g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf, const uint32_t (&kin)[8], int32_t* lane_tab) {
+    uint32_t k[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = kin[i];
+    scalar_mod_r(k);
+    uint32_t k0[4], k1[4], kb0[5], kb1[5];
+    scalar_glv_split(k0, k1, k);
+    glv_bias(kb0, k0);
+    glv_bias(kb1, k1);
+
+    fp beta;
+    fp_set_const(beta, FP_BETA_A);
+    {   // table T[j] = jP, j = 1..16: forward co-Z pass
+        fp x1, y1, xj, yj, xn, yn, h, hn, bx;
+        g1j_dblu(xj, yj, x1, y1, px, py);                       // 2P and P on Z_2 = 2y
+#pragma unroll 1
+        for (int j = 2; j < G1_TAB; ++j) {
+            g1j_zaddu(xn, yn, x1, y1, h, xj, yj);               // (j+1)P and P on Z_(j+1) = Z_j h_j
+            fp_norm1(hn, h);
+            tab_store_rec(lane_tab + (j - 1) * G1_ENT_DWORDS, xj, yj, hn, 32.0);
+            xj = xn; yj = yn;
+        }
+        fp_mul(bx, xj, beta);
+        tab_store_rec(lane_tab + (G1_TAB - 1) * G1_ENT_DWORDS, xj, yj, bx, 4.0);
+        fp_mul(bx, x1, beta);
+        tab_store_rec(lane_tab, x1, y1, bx, 4.0);
+    }
+    {   // backward pass: entry j times mu_j^2, mu_j^3 with mu_j = h_j h_(j+1) ... h_15 = Z_T / Z_j
+        fp mu, m2, m3, x, y, h, bx, zt, y2;
+#pragma unroll 1
+        for (int j = G1_TAB - 1; j >= 2; --j) {
+            int32_t* ent = lane_tab + (j - 1) * G1_ENT_DWORDS;
+            tab_load_rec(x, y, h, ent, 32.0);
+            if (j == G1_TAB - 1) mu = h; else fp_mul(mu, mu, h);   // wave-uniform
+            fp_sqr(m2, mu);
+            fp_mul(m3, m2, mu);
+            fp_mul(x, x, m2);
+            fp_mul(y, y, m3);
+            fp_mul(bx, x, beta);
+            tab_store_rec(ent, x, y, bx, 4.0);
+        }
+        fp_raw_dbl(y2, py);
+        fp_mul(zt, mu, y2);                                     // Z_T = Z_2 mu_2
+        tab_store_zt(lane_tab, zt);
+    }
+
+    // the top window starts the accumulator with its first digit's entry (Z = 1)
+    g1j a;
+    bool acc_inf;
+    {
+        const int d0 = glv_digit(kb0, G1_WINDOWS - 1);
+        fp x, y, ny;
+        tab_load_xy(x, y, g1_digit_entry(lane_tab, d0));
+        fp_neg(ny, y);
+        a.x = x;
+        fp_select(a.y, d0 < 0, ny, y);
+        fp_one(a.z);
+        acc_inf = d0 == 0;
+        const int d1 = glv_digit(kb1, G1_WINDOWS - 1);
+        tab_load_ybx(y, x, g1_digit_entry(lane_tab, d1));
+        g1j_add_digit(a, acc_inf, x, y, d1, true);
+    }
+    // the record of an addition is requested one operation ahead (round 4): the first digit's before the window's doublings, the second
+    // digit's before the first addition
+#pragma unroll 1
+    for (int w = G1_WINDOWS - 2; w >= 0; --w) {
+        const int d0 = glv_digit(kb0, w), d1 = glv_digit(kb1, w);
+        fp x0, y0, x1, y1;
+        tab_load_xy(x0, y0, g1_digit_entry(lane_tab, d0));
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);               // the loads stay in front of the doublings
+#endif
+        g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); g1j_dbl(a);
+        if (G1_WIN == 5) g1j_dbl(a);
+        tab_load_ybx(y1, x1, g1_digit_entry(lane_tab, d1));
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+        g1j_add_digit(a, acc_inf, x0, y0, d0, false);
+        g1j_add_digit(a, acc_inf, x1, y1, d1, true);
+    }
+
+    // back to E and to homogeneous coordinates: (X Z : Y : Z^3) with Z = Z_acc Z_T
+    fp zt, z, z2;
+    tab_load_zt(zt, lane_tab);
+    fp_mul(z, a.z, zt);
+    const bool inf = acc_inf || p_is_inf;
+    const bool exc = !inf && fp_is_zero(z);
+    fp_sqr(z2, z);
+    fp_mul(acc.x, a.x, z);
+    acc.y = a.y;
+    fp_mul(acc.z, z2, z);
+    {
+        g1p o;
+        g1_set_inf(o);
+        fp_select(acc.x, inf, o.x, acc.x); fp_select(acc.y, inf, o.y, acc.y); fp_select(acc.z, inf, o.z, acc.z);
+    }
+    if (exc) g1_scalar_mul_complete(acc, px, py, p_is_inf, kin, lane_tab);
+    return exc;
 }
 // k mod r < x^2, i.e. k div x^2 == 0: the lanes that owe g1_glv_small_scalar_term (evaluated by a separate, almost always
 // empty fix-up kernel so that the main loop's register allocation does not pay for the rare branch)
