@@ -484,8 +484,11 @@ C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, boo
         g1p q0, q1, e;
         tab_load_g1(q0, g1_digit_entry(lane_tab, d0));
         __builtin_amdgcn_sched_barrier(0);               // the loads stay in front of the doublings
-        g1_dbl(acc); g1_dbl(acc); g1_dbl(acc); g1_dbl(acc);
-        if (G1_WIN == 5) g1_dbl(acc);
+        // a loop, not G1_WIN copies: this function is called, and a loop body beyond the reach of s_cbranch (+-128 KiB) gets long
+        // branches whose expansion (ROCm 7.2 clang) takes s[30:31], the return address, so the call never came back and the lane
+        // ran wild (an illegal memory access on the first fallback lane)
+#pragma unroll 1
+        for (int j = 0; j < G1_WIN; ++j) g1_dbl(acc);
         tab_load_g1(q1, g1_digit_entry(lane_tab, d1));
         __builtin_amdgcn_sched_barrier(0);
         g1_digit_fix(e, q0, d0, false);

@@ -1,22 +1,25 @@
 """CPU tests of the G1 scalar multiplication's fast path (g1.hpp: co-Z affine table, Jacobian doublings and mixed additions) and of
 its complete fallback, under the bounds checker (tests/host_sim/g1_coz.cpp, C12381_CHECK_BOUNDS).  Results are compared with the
-oracle lane by lane, and the set of lanes that took the complete path is compared with the set the formulas predict: the lanes whose
-Jacobian Z becomes 0 (an addition acc = +-T, a table built on a point of order 3 or 11), and never a lane of a random subgroup batch."""
+oracle lane by lane, and the set of lanes that took the complete path is compared with the set the formulas predict (g1_torsion.py).
+Two causes give a lane Jacobian Z = 0, and the tests reach them with different points:
+- a table built on a point of order 3 or 11 (jP = -P for some j <= 16): every such lane with k != 0 mod r (the edge test);
+- an addition acc = +-T inside the loop: never for a point of G1 or of G1 + T3, whose multiples need s = +-t mod r, which the reduced
+  GLV halves exclude (the edge test's "sub" and "mixed3" kinds predict and see none); but for eigenpoints of E(x, y) = (beta x, -y) of
+  order 10177 and 859267, where s = +-t mod q happens in about 1 % of random lanes, both as a doubling (s = t) and through infinity
+  (s = -t) (the eigenpoint test)."""
 import ctypes
 import os
 import subprocess
 
 import pytest
 
+from g1_torsion import DBL, INF, X2, crt, ec_add, ec_mul, edge_scalars, eigenpoint, enc, exceptional, point_of_order
 from util import P, R, golden, prng, scalars
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SIM_DIR = os.path.join(HERE, "host_sim")
 CSRC = os.path.join(os.path.dirname(HERE), "crypto12381_amd", "csrc")
 sz = ctypes.c_size_t
-
-X2 = 0xd201000000010000 ** 2
-H1 = 0x396c8c005555e1568c00aaab0000aaab           # cofactor of G1: #E(Fp) = H1 * R
 
 
 @pytest.fixture(scope="module")
@@ -35,91 +38,6 @@ def run(coz, pts, sc):
     comp = ctypes.create_string_buffer(n)
     assert coz.sim_g1coz_mul_batch(sz(n), pts, sc, out, comp) == 0
     return out.raw, list(comp.raw)
-
-
-# ---------------------------------------------------------------- affine arithmetic on E: y^2 = x^3 + 4 (None = infinity)
-def ec_add(a, b):
-    if a is None:
-        return b
-    if b is None:
-        return a
-    if a[0] == b[0]:
-        if (a[1] + b[1]) % P == 0:
-            return None
-        lam = 3 * a[0] * a[0] * pow(2 * a[1], -1, P) % P
-    else:
-        lam = (b[1] - a[1]) * pow(b[0] - a[0], -1, P) % P
-    x = (lam * lam - a[0] - b[0]) % P
-    return x, (lam * (a[0] - x) - a[1]) % P
-
-
-def ec_mul(k, a):
-    r = None
-    while k:
-        if k & 1:
-            r = ec_add(r, a)
-        a = ec_add(a, a)
-        k >>= 1
-    return r
-
-
-def enc(a):
-    return bytes(96) if a is None else a[0].to_bytes(48, "big") + a[1].to_bytes(48, "big")
-
-
-def point_of_order(q):
-    """a point of prime order q | #E(Fp): the q-part of a curve point found by counting x upwards, multiplied down to order q"""
-    m = H1 * R
-    while m % q == 0:
-        m //= q
-    x = 1
-    while True:
-        x += 1
-        rhs = (x ** 3 + 4) % P
-        y = pow(rhs, (P + 1) // 4, P)
-        if y * y % P != rhs:
-            continue
-        t = ec_mul(m, (x, y))
-        if t is None:
-            continue
-        while ec_mul(q, t) is not None:
-            t = ec_mul(q, t)
-        return t
-
-
-# ---------------------------------------------------------------- which lanes the incomplete formulas cannot serve
-def digits(k):
-    kb = k + sum(16 << (5 * w) for w in range(26))
-    return [((kb >> (5 * w)) & 31) - 16 for w in range(26)]
-
-
-def exceptional(k, tor=1):
-    """the digit schedule of g1_scalar_mul on P = G' + T with G' of order R and T of order tor (1 or 3; the endomorphism acts as x^2 on
-    G' and, T being (0, +-2), as -1 on T), tracked as the accumulator's multiples (s mod R, s mod tor): an addition of a table point t
-    with the accumulator not at infinity is exceptional when s = +-t in both parts"""
-    k %= R
-    k1, k0 = divmod(k, X2)
-    d0, d1 = digits(k0), digits(k1)
-    s, inf, exc = (0, 0), True, False
-    for w in range(25, -1, -1):
-        s = (32 * s[0] % R, 32 * s[1] % tor)
-        for d, t in ((d0[w], (d0[w] % R, d0[w] % tor)), (d1[w], (d1[w] * X2 % R, -d1[w] % tor))):
-            if d == 0:
-                continue
-            if inf:
-                s, inf = t, False
-                continue
-            if all((a - b) % m == 0 for a, b, m in zip(s, t, (R, tor))) or all((a + b) % m == 0 for a, b, m in zip(s, t, (R, tor))):
-                exc = True
-            s = ((s[0] + t[0]) % R, (s[1] + t[1]) % tor)
-    return exc
-
-
-def edge_scalars():
-    ks = [0] + list(range(1, 41)) + [R - 1, R, R + 1, (1 << 256) - 1, X2 - 1, X2, X2 + 1, R - X2]
-    ks += [(1 << 124) + 3, (1 << 125) - 1, 5 * X2 + 7, ((1 << 100) + 1) * X2 + 2, 3 * X2 - 40]     # top windows zero in one or both halves
-    ks += [(R - j) % R for j in range(2, 8)] + [16, 32 * 16, 32 * 16 + 16]
-    return ks
 
 
 def test_coz_edge_points_and_scalars(coz, oracle_port):
@@ -151,7 +69,7 @@ def test_coz_edge_points_and_scalars(coz, oracle_port):
         if kind == "small":                       # the table's ZADDU chain meets jP = -P: Z_T = 0, every lane but k = 0 (mod R)
             return k % R != 0
         if kind in ("sub", "mixed3"):             # mixed3 = G + (0, 2), of order 3R: its table is regular
-            return exceptional(k, 3 if kind == "mixed3" else 1)
+            return exceptional(k, 3 * R, crt(X2, R, -1, 3)) is not None if kind == "mixed3" else exceptional(k, R, X2 % R) is not None
         return False                              # points of large order off the subgroup: none of these scalars meets an exception
 
     want = [1 if expected(kind, k) else 0 for kind, k in kinds]
@@ -170,3 +88,25 @@ def test_coz_random_subgroup_lanes_never_fall_back(coz, oracle_port):
     got, comp = run(coz, pts, sc)
     assert sum(comp) == 0
     assert got == oracle_port.g1_mul(pts, sc, 96, 8)
+
+
+def test_coz_eigenpoint_lanes_take_the_loop_exception(coz, oracle_port):
+    """Eigenpoints T_e of order q = 10177 and 859267 (E(T_e) = lambda T_e) with 4000 seeded random 256-bit scalars each plus the edge
+    scalars: results equal the oracle's lane by lane, and the lanes that take the complete path are exactly those whose digit schedule
+    meets s = +-t mod q, with both cases present"""
+    n = 4000
+    ks = edge_scalars() + [prng(9301, i) % (1 << 256) for i in range(n)]
+    P_, S_, want = b"", b"", []
+    for q in (10177, 859267):
+        te, lam = eigenpoint(q)
+        P_ += enc(te) * len(ks)
+        S_ += b"".join(k.to_bytes(32, "big") for k in ks)
+        want += [exceptional(k, q, lam) for k in ks]
+    got, comp = run(coz, P_, S_)
+    exp = oracle_port.g1_mul(P_, S_, 96, 8)
+    m = len(want)
+    bad = [i for i in range(m) if got[96 * i:96 * i + 96] != exp[96 * i:96 * i + 96]]
+    assert bad == [], bad[:8]
+    assert comp == [0 if w is None else 1 for w in want], [(i, comp[i], want[i]) for i in range(m) if comp[i] != (want[i] is not None)][:8]
+    print("eigenpoint lanes on the complete path: %d of %d (s=t: %d, s=-t: %d)" % (sum(comp), m, want.count(DBL), want.count(INF)))
+    assert sum(comp) >= 30 and want.count(DBL) > 0 and want.count(INF) > 0

@@ -4,7 +4,7 @@ import hashlib
 
 import pytest
 
-from util import P, R, cat, golden
+from util import P, R, cat, golden, prng, scalars
 
 
 @pytest.fixture(params=["port", "reference"])
@@ -244,3 +244,52 @@ def test_bbs_wire_restatement_matches_reference(oracle_ref, oracle_port):
     a = oracle_ref.bbs_plus_verify_wire(pp, h49, pk, sigs, msgs, msg_len, 4)
     b = oracle_port.bbs_plus_verify_wire(pp, h49, pk, sigs, msgs, msg_len, 4)
     assert a == b and list(a) == [1, 1, 0, 0xff, 0xff, 0, 1, 1]
+
+
+def test_port_matches_reference_on_torsion_points(oracle_port, oracle_ref):
+    """The C restatement against the compiled reference on points outside G1 that reach the fallback of the GPU's G1 scalar
+    multiplication (g1_torsion.py): infinity, (0, +-2) of order 3, a point of order 11, the order-10177 eigenpoint of the endomorphism,
+    G + (0, 2) and G + T_e — multiplication at 49 and 96 bytes with the edge scalars and random ones, the bucket product and
+    sum_of_products with these among subgroup terms, every pairwise addition (P + P and P + (-P) on the order-3 points among them, checked
+    against affine arithmetic as well) and compress / decompress round trips including the x = 0 encodings.  Inputs are computed here."""
+    from g1_torsion import X2, dec, ec_add, edge_scalars, eigenpoint, enc, generator, point_of_order
+    g = generator()
+    te, _ = eigenpoint(10177)
+    pts = [None, (0, 2), (0, P - 2), point_of_order(11), te, ec_add(g, (0, 2)), ec_add(g, te)]
+    ks = edge_scalars() + [prng(9401, i) % (1 << 256) for i in range(24)]
+    pb = b"".join(enc(p) * len(ks) for p in pts)
+    sb = b"".join(k.to_bytes(32, "big") for k in ks) * len(pts)
+    for fmt in (49, 96):
+        assert oracle_port.g1_mul(pb, sb, fmt, 4) == oracle_ref.g1_mul(pb, sb, fmt, 4), fmt
+    # products: the torsion points among random subgroup terms, with small, edge and random scalars
+    m = 40
+    sub = oracle_ref.g1_mul(enc(g) * m, scalars(9402, m), 96, 4)
+    terms = b"".join(enc(p) for p in pts) + sub
+    tsc = b"".join(k.to_bytes(32, "big") for k in (5, 22, R - 1, X2 + 1, (1 << 256) - 1, 7, 3 * X2 - 40)) + scalars(9403, m, 1 << 256)
+    for fmt in (49, 96):
+        assert oracle_port.g1_msm(terms, tsc, fmt, 2) == oracle_ref.g1_msm(terms, tsc, fmt, 2), fmt
+        assert oracle_port.g1_sum_of_products(terms, tsc, fmt) == oracle_ref.g1_sum_of_products(terms, tsc, fmt), fmt
+    for j in range(len(pts)):                                  # each torsion point alone with one subgroup term
+        one = enc(pts[j]) + sub[:96]
+        assert oracle_port.g1_msm(one, tsc[32 * j:32 * j + 32] + tsc[-32:], 96, 1) == oracle_ref.g1_msm(one, tsc[32 * j:32 * j + 32] + tsc[-32:], 96, 1), j
+    # additions: every ordered pair
+    a = b"".join(enc(p) for p in pts for _ in pts)
+    b = b"".join(enc(q) for _ in pts for q in pts)
+    for fmt in (49, 96):
+        assert oracle_port.g1_add(a, b, fmt) == oracle_ref.g1_add(a, b, fmt), fmt
+    assert oracle_ref.g1_add(a, b, 96) == b"".join(enc(ec_add(p, q)) for p in pts for q in pts)
+    assert oracle_ref.g1_add(enc((0, 2)), enc((0, 2)), 96) == enc((0, P - 2))          # [2](0, 2) = (0, -2)
+    assert oracle_ref.g1_add(enc((0, 2)), enc((0, P - 2)), 96) == bytes(96)
+    # compress / decompress: the points' own encodings, and x = 0 and x = p under both sign tags
+    allp = b"".join(enc(p) for p in pts)
+    c = oracle_ref.g1_compress(allp)
+    assert oracle_port.g1_compress(allp) == c
+    c += b"".join(bytes([tag]) + x.to_bytes(48, "big") for tag in (2, 3) for x in (0, P))
+    d = oracle_ref.g1_decompress(c)
+    assert oracle_port.g1_decompress(c) == d
+    out, st = d
+    assert list(st) == [1] * (len(c) // 49)
+    assert out[:96 * len(pts)] == allp
+    n0 = len(pts)
+    assert [dec(out[96 * i:96 * i + 96]) for i in range(n0, n0 + 4)] == [(0, 2), (0, 2), (0, P - 2), (0, P - 2)] or \
+        [dec(out[96 * i:96 * i + 96]) for i in range(n0, n0 + 4)] == [(0, P - 2), (0, P - 2), (0, 2), (0, 2)]   # x = p is x = 0; the tags differ
