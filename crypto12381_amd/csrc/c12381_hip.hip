@@ -9,6 +9,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
+#include <initializer_list>
 #include <new>
 #include <thread>
 #include <vector>
@@ -66,7 +67,9 @@ struct c12381_ctx {
     std::vector<hipStream_t> sort_streams; // further streams for the segment sorts of the bucket product (created on first use)
     std::vector<hipEvent_t> sort_events;
     char err[256] = {0};
-    enum { WS_TAB, WS_PROJ, WS_PREF, WS_IN0, WS_IN1, WS_OUT, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_IN, WS_BBS_WIRE, WS_BBS_WIRE_IN,
+    // WS_STAGE holds the caller's buffers of a host form (stage / unstage).  No _dev path uses it and no _dev path calls a host form
+    // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
+    enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
            WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_G, WS_FQ_GATE, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
@@ -180,24 +183,60 @@ int read_flag(c12381_ctx* c) {
     }
     return c->h_flag[0] ? C12381_E_POINT : 0;
 }
-// stage host buffers: copies up to three inputs in, runs body, copies output back
-struct staged {
-    uint8_t *in0 = nullptr, *in1 = nullptr, *out = nullptr;
+// Host forms: the caller's inputs and outputs, (host pointer, bytes) each, laid out in WS_STAGE at 256-byte-aligned offsets.  stage() copies
+// every non-empty input in and hands back the device pointers (a null host pointer stays null); unstage() copies the outputs back after
+// the _dev call and ends with read_flag.  Up to 12 inputs and 2 outputs.
+struct host_buf { const void* p; size_t bytes; };
+struct staging {
+    const uint8_t* in[12] = {};
+    uint8_t* out[2] = {};
+    host_buf host_out[2] = {};
+    size_t nout = 0;
 };
-int stage_in(c12381_ctx* c, staged& s, const void* h0, size_t b0, const void* h1, size_t b1, size_t bout) {
+int stage(c12381_ctx* c, staging& s, std::initializer_list<host_buf> ins, std::initializer_list<host_buf> outs) {
+    size_t bytes = 0;
+    for (const host_buf& b : ins) bytes += b.p ? round_up(b.bytes, 256) : 0;
+    for (const host_buf& b : outs) bytes += round_up(b.bytes, 256);
     int rc;
-    if ((rc = ensure(c, c12381_ctx::WS_IN0, round_up(b0 ? b0 : 16, 256)))) return rc;
-    if ((rc = ensure(c, c12381_ctx::WS_IN1, round_up(b1 ? b1 : 16, 256)))) return rc;
-    if ((rc = ensure(c, c12381_ctx::WS_OUT, round_up(bout ? bout : 16, 256)))) return rc;
-    s.in0 = (uint8_t*)c->ws[c12381_ctx::WS_IN0]; s.in1 = (uint8_t*)c->ws[c12381_ctx::WS_IN1]; s.out = (uint8_t*)c->ws[c12381_ctx::WS_OUT];
-    if (h0 && b0) HIPCK(c, hipMemcpyAsync(s.in0, h0, b0, hipMemcpyHostToDevice, c->stream));
-    if (h1 && b1) HIPCK(c, hipMemcpyAsync(s.in1, h1, b1, hipMemcpyHostToDevice, c->stream));
+    if ((rc = ensure(c, c12381_ctx::WS_STAGE, bytes))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_STAGE];
+    size_t i = 0;
+    for (const host_buf& b : ins) {
+        s.in[i++] = b.p ? d : nullptr;
+        if (!b.p) continue;
+        if (b.bytes) HIPCK(c, hipMemcpyAsync(d, b.p, b.bytes, hipMemcpyHostToDevice, c->stream));
+        d += round_up(b.bytes, 256);
+    }
+    for (const host_buf& b : outs) {
+        s.out[s.nout] = d; s.host_out[s.nout++] = b;
+        d += round_up(b.bytes, 256);
+    }
     return 0;
 }
-int stage_out(c12381_ctx* c, const staged& s, void* hout, size_t bout) {
-    HIPCK(c, hipMemcpyAsync(hout, s.out, bout, hipMemcpyDeviceToHost, c->stream));
+int unstage(c12381_ctx* c, const staging& s) {
+    for (size_t i = 0; i < s.nout; ++i)
+        HIPCK(c, hipMemcpyAsync(const_cast<void*>(s.host_out[i].p), s.out[i], s.host_out[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    return read_flag(c);
+}
+// Projective tree sum of the n elements at `cur` (SoA with stride `stride`, `words` dwords per element: 3 NL for G1, 6 NL for G2) by the
+// reduce kernel, ping-pong between WS_RED0 and WS_RED1: levels of round_up(n / 32, 64) elements above 4096, of 64 above 64, then 1.
+// cur / stride end at the single projective result.
+using reduce_fn = void (*)(size_t, const int32_t*, size_t, size_t, int32_t*, size_t);
+int tree_sum(c12381_ctx* c, reduce_fn reduce, size_t words, size_t n, const int32_t*& cur, size_t& stride) {
+    int slot = c12381_ctx::WS_RED0, rc;
+    for (size_t cur_n = n; cur_n > 1;) {
+        const size_t m = cur_n > 4096 ? round_up(cur_n / 32, 64) : (cur_n > 64 ? 64 : 1);
+        const size_t m_stride = round_up(m, 64);
+        if ((rc = ensure(c, slot, words * m_stride * 4))) return rc;
+        hipLaunchKernelGGL(reduce, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, cur_n, cur, stride, m, (int32_t*)c->ws[slot], m_stride);
+        HIPCK(c, hipGetLastError());
+        cur = (const int32_t*)c->ws[slot]; cur_n = m; stride = m_stride;
+        slot = slot == c12381_ctx::WS_RED0 ? c12381_ctx::WS_RED1 : c12381_ctx::WS_RED0;
+    }
     return 0;
 }
+inline bool g1_fmt(int fmt) { return fmt == 49 || fmt == 96; }
+inline bool g2_fmt(int fmt) { return fmt == 97 || fmt == 192; }
 
 // ev_chunk[0]: the event the bucket product forks its side-stream work from (the scalar-multiplication batches use the same vector per chunk)
 static int ensure_fork_event(c12381_ctx* c) {
@@ -434,7 +473,7 @@ void c12381_destroy(c12381_ctx* c) {
 const char* c12381_last_error(const c12381_ctx* c) { return c ? c->err : "null context"; }
 
 // Workspaces grow to the largest call a context has served and stay (a GT power of 2^16 elements leaves 1.4 GB of tables, 2^18 BBS+ verifications
-// a 172 MB state slab, a 2^20 scalar multiplication its 2.95 GB table slab): a long-lived context that has finished with the large batches hands
+// a 344 MB state slab, a 2^20 scalar multiplication its 2.95 GB table slab): a long-lived context that has finished with the large batches hands
 // them back here; the next call allocates what it needs again.
 int c12381_trim(c12381_ctx* c) {
     int rc = bind(c); if (rc) return rc;
@@ -519,23 +558,20 @@ int c12381_profile_read(c12381_ctx* c, int kind, double* total_ms, uint64_t* lau
 }
 
 // ---------------------------------------------------------------- Fp
+static int fp_op_args(int op, const void* a, const void* b, const void* out) { return (op < 0 || op > 5 || !a || !out || (op <= 2 && !b)) ? C12381_E_ARG : 0; }
 int c12381_fp_op_batch_dev(c12381_ctx* c, int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (op < 0 || op > 5 || !a || !out || (op <= 2 && !b)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = fp_op_args(op, a, b, out))) return rc;
     if (n == 0) return 0;
     hipLaunchKernelGGL(fp_op_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, op, n, a, op <= 2 ? b : nullptr, out);
     HIPCK(c, hipGetLastError());
     return 0;
 }
 int c12381_fp_op_batch(c12381_ctx* c, int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (op < 0 || op > 5 || !a || !out || (op <= 2 && !b)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = fp_op_args(op, a, b, out))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, a, 48 * n, op <= 2 ? b : nullptr, op <= 2 ? 48 * n : 0, 48 * n))) return rc;
-    if ((rc = c12381_fp_op_batch_dev(c, op, n, s.in0, s.in1, s.out))) return rc;
-    if ((rc = stage_out(c, s, out, 48 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{a, 48 * n}, {op <= 2 ? b : nullptr, 48 * n}}, {{out, 48 * n}})) || (rc = c12381_fp_op_batch_dev(c, op, n, s.in[0], s.in[1], s.out[0]))) return rc;
+    return unstage(c, s);
 }
 int c12381_fp_mulchain_dev(c12381_ctx* c, size_t n, int iters, const uint8_t* a, const uint8_t* b, uint8_t* out) {
     int rc = bind(c); if (rc) return rc;
@@ -549,9 +585,12 @@ int c12381_fp_mulchain_dev(c12381_ctx* c, size_t n, int iters, const uint8_t* a,
 // ---------------------------------------------------------------- G1
 // C12381_F_COMPRESSED_IN: pts are n x 49 bytes (the serialized form, g1_point.hpp:87-111 -> ECP_fromOctet): from_bytes -> multiply ->
 // to_bytes in ONE kernel — the square root runs in the kernel's prologue; a rejected encoding is a lane of 0xff + C12381_E_POINT
+// (also the check of the fixed-base forms, with flags 0)
+static int g1_mul_args(const void* pts, const void* sc, const void* out, int fmt, unsigned flags) {
+    return (!pts || !sc || !out || !g1_fmt(fmt) || (flags & ~(unsigned)(C12381_F_IN_SUBGROUP | C12381_F_COMPRESSED_IN))) ? C12381_E_ARG : 0;
+}
 int c12381_g1_mul_batch_flags_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!pts || !sc || !out || (fmt != 49 && fmt != 96) || (flags & ~(unsigned)(C12381_F_IN_SUBGROUP | C12381_F_COMPRESSED_IN))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_mul_args(pts, sc, out, fmt, flags))) return rc;
     if (n == 0) return 0;
     const size_t stride = round_up(n, 64);
     if ((rc = g1_mul_to_proj(c, n, pts, sc, stride, (flags & C12381_F_COMPRESSED_IN) ? 49 : 96, 0, nullptr, (flags & C12381_F_IN_SUBGROUP) != 0))) return rc;
@@ -561,32 +600,31 @@ int c12381_g1_mul_batch_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const u
     return c12381_g1_mul_batch_flags_dev(c, n, pts, sc, out, fmt, 0u);
 }
 int c12381_g1_mul_batch_flags(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!pts || !sc || !out || (fmt != 49 && fmt != 96) || (flags & ~(unsigned)(C12381_F_IN_SUBGROUP | C12381_F_COMPRESSED_IN))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_mul_args(pts, sc, out, fmt, flags))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, pts, ((flags & C12381_F_COMPRESSED_IN) ? 49 : 96) * n, sc, 32 * n, (size_t)fmt * n))) return rc;
-    if ((rc = c12381_g1_mul_batch_flags_dev(c, n, s.in0, s.in1, s.out, fmt, flags))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{pts, ((flags & C12381_F_COMPRESSED_IN) ? 49 : 96) * n}, {sc, 32 * n}}, {{out, (size_t)fmt * n}}))) return rc;
+    if ((rc = c12381_g1_mul_batch_flags_dev(c, n, s.in[0], s.in[1], s.out[0], fmt, flags))) return rc;
+    return unstage(c, s);
 }
 int c12381_g1_mul_batch(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
     return c12381_g1_mul_batch_flags(c, n, pts, sc, out, fmt, 0u);
 }
+static int g1_add_dev(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, int fmt) {
+    const size_t stride = round_up(n, 64);
+    int rc;
+    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+    hipLaunchKernelGGL(g1_add_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, a, b, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, c->d_flag);
+    HIPCK(c, hipGetLastError());
+    return g1_finish(c, n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, out, fmt);
+}
 int c12381_g1_add_batch(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, int fmt) {
     int rc = bind(c); if (rc) return rc;
-    if (!a || !b || !out || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    if (!a || !b || !out || !g1_fmt(fmt)) return C12381_E_ARG;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, a, 96 * n, b, 96 * n, (size_t)fmt * n))) return rc;
-    const size_t stride = round_up(n, 64);
-    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
-    hipLaunchKernelGGL(g1_add_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, s.in0, s.in1, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride,
-                       c->d_flag);
-    HIPCK(c, hipGetLastError());
-    if ((rc = g1_finish(c, n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, s.out, fmt))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{a, 96 * n}, {b, 96 * n}}, {{out, (size_t)fmt * n}})) || (rc = g1_add_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
 }
 
 // MSM: the bucket method (g1_msm_pippenger); a single term (or C12381_MSM=naive) takes n independent GLV scalar
@@ -596,40 +634,30 @@ int c12381_g1_add_batch(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t
 // src/miracl_core_interface.cpp:129-132 -> ECP_add) and the combine step of a product that was sharded over GPUs:
 // lift + tree sum + one affine conversion — tens of microseconds for the 8 partial points of a node, where the bucket method's
 // fixed stages cost 2.3 ms.
+static int g1_sum_args(size_t n, const void* pts, const void* out, int fmt) { return (!out || (n && !pts) || !g1_fmt(fmt)) ? C12381_E_ARG : 0; }
 int c12381_g1_sum_dev(c12381_ctx* c, size_t n, const uint8_t* pts, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && !pts) || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_sum_args(n, pts, out, fmt))) return rc;
     if (n == 0) { HIPCK(c, hipMemsetAsync(out, 0, fmt, c->stream)); return 0; }
-    const size_t stride = round_up(n, 64);
+    size_t stride = round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
     hipLaunchKernelGGL(g1_lift_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, pts, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, c->d_flag);
     HIPCK(c, hipGetLastError());
     const int32_t* cur = (const int32_t*)c->ws[c12381_ctx::WS_PROJ];
-    size_t cur_n = n, cur_stride = stride;
-    int slot = c12381_ctx::WS_RED0;
-    while (cur_n > 1) {
-        const size_t m = cur_n > 4096 ? round_up(cur_n / 32, 64) : (cur_n > 64 ? 64 : 1);
-        const size_t m_stride = round_up(m, 64);
-        if ((rc = ensure(c, slot, (size_t)3 * NL * m_stride * 4))) return rc;
-        hipLaunchKernelGGL(g1_reduce_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, cur_n, cur, cur_stride, m, (int32_t*)c->ws[slot], m_stride);
-        HIPCK(c, hipGetLastError());
-        cur = (const int32_t*)c->ws[slot]; cur_n = m; cur_stride = m_stride;
-        slot = slot == c12381_ctx::WS_RED0 ? c12381_ctx::WS_RED1 : c12381_ctx::WS_RED0;
-    }
-    return g1_finish(c, 1, cur, cur_stride, out, fmt);
+    if ((rc = tree_sum(c, g1_reduce_kernel, 3 * NL, n, cur, stride))) return rc;
+    return g1_finish(c, 1, cur, stride, out, fmt);
 }
 int c12381_g1_sum(c12381_ctx* c, size_t n, const uint8_t* pts, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && !pts) || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
-    staged s;
-    if ((rc = stage_in(c, s, pts, 96 * n, nullptr, 0, (size_t)fmt))) return rc;
-    if ((rc = c12381_g1_sum_dev(c, n, s.in0, s.out, fmt))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt))) return rc;
-    return read_flag(c);
+    int rc = bind(c); if (rc || (rc = g1_sum_args(n, pts, out, fmt))) return rc;
+    staging s;                                                  // n == 0: the identity, through the _dev form
+    if ((rc = stage(c, s, {{pts, 96 * n}}, {{out, (size_t)fmt}})) || (rc = c12381_g1_sum_dev(c, n, s.in[0], s.out[0], fmt))) return rc;
+    return unstage(c, s);
+}
+// (also the check of c12381_g1_sum_of_products, with flags 0)
+static int g1_msm_args(size_t n, const void* pts, const void* sc, const void* out, int fmt, unsigned flags) {
+    return (!out || (n && (!pts || !sc)) || !g1_fmt(fmt) || (flags & ~(unsigned)C12381_F_COMPRESSED_IN)) ? C12381_E_ARG : 0;
 }
 int c12381_g1_msm_flags_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && (!pts || !sc)) || (fmt != 49 && fmt != 96) || (flags & ~(unsigned)C12381_F_COMPRESSED_IN)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_msm_args(n, pts, sc, out, fmt, flags))) return rc;
     const int in_fmt = (flags & C12381_F_COMPRESSED_IN) ? 49 : 96;        // compressed terms are decoded by the preparation kernel
     if (n == 0) { HIPCK(c, hipMemsetAsync(out, 0, fmt, c->stream)); return 0; }
     if (n > MSM_MAX_TERMS) {
@@ -645,33 +673,21 @@ int c12381_g1_msm_flags_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const u
         return c12381_g1_sum_dev(c, parts, pp, out, fmt);
     }
     if (msm_use_buckets(n)) return g1_msm_pippenger(c, n, pts, sc, out, fmt, in_fmt);
-    const size_t stride = round_up(n, 64);
+    size_t stride = round_up(n, 64);
     if ((rc = g1_mul_to_proj(c, n, pts, sc, stride, (size_t)in_fmt))) return rc;
     const int32_t* cur = (const int32_t*)c->ws[c12381_ctx::WS_PROJ];
-    size_t cur_n = n, cur_stride = stride;
-    int slot = c12381_ctx::WS_RED0;
-    while (cur_n > 1) {
-        size_t m = cur_n > 4096 ? round_up(cur_n / 32, 64) : (cur_n > 64 ? 64 : 1);
-        const size_t m_stride = round_up(m, 64);
-        if ((rc = ensure(c, slot, (size_t)3 * NL * m_stride * 4))) return rc;
-        hipLaunchKernelGGL(g1_reduce_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, cur_n, cur, cur_stride, m, (int32_t*)c->ws[slot], m_stride);
-        HIPCK(c, hipGetLastError());
-        cur = (const int32_t*)c->ws[slot]; cur_n = m; cur_stride = m_stride;
-        slot = slot == c12381_ctx::WS_RED0 ? c12381_ctx::WS_RED1 : c12381_ctx::WS_RED0;
-    }
-    return g1_finish(c, 1, cur, cur_stride, out, fmt);
+    if ((rc = tree_sum(c, g1_reduce_kernel, 3 * NL, n, cur, stride))) return rc;
+    return g1_finish(c, 1, cur, stride, out, fmt);
 }
 int c12381_g1_msm_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
     return c12381_g1_msm_flags_dev(c, n, pts, sc, out, fmt, 0u);
 }
 int c12381_g1_msm_flags(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && (!pts || !sc)) || (fmt != 49 && fmt != 96) || (flags & ~(unsigned)C12381_F_COMPRESSED_IN)) return C12381_E_ARG;
-    staged s;
-    if ((rc = stage_in(c, s, pts, ((flags & C12381_F_COMPRESSED_IN) ? 49 : 96) * n, sc, 32 * n, (size_t)fmt))) return rc;
-    if ((rc = c12381_g1_msm_flags_dev(c, n, s.in0, s.in1, s.out, fmt, flags))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt))) return rc;
-    return read_flag(c);
+    int rc = bind(c); if (rc || (rc = g1_msm_args(n, pts, sc, out, fmt, flags))) return rc;
+    staging s;                                                  // n == 0: the identity, through the _dev form
+    if ((rc = stage(c, s, {{pts, ((flags & C12381_F_COMPRESSED_IN) ? 49 : 96) * n}, {sc, 32 * n}}, {{out, (size_t)fmt}}))) return rc;
+    if ((rc = c12381_g1_msm_flags_dev(c, n, s.in[0], s.in[1], s.out[0], fmt, flags))) return rc;
+    return unstage(c, s);
 }
 int c12381_g1_msm(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
     return c12381_g1_msm_flags(c, n, pts, sc, out, fmt, 0u);
@@ -680,42 +696,28 @@ int c12381_g1_msm(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc
 // of the TRUE multiples [k_i mod r]P_i for any curve points.  On G1 it equals c12381_g1_msm — use that for throughput; this entry
 // exists so that the seam function has the reference's value for every input (n plain ladders + tree sum; the seam is scalar).
 int c12381_g1_sum_of_products_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && (!pts || !sc)) || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_msm_args(n, pts, sc, out, fmt, 0u))) return rc;
     if (n == 0) { HIPCK(c, hipMemsetAsync(out, 0, fmt, c->stream)); return 0; }
-    const size_t stride = round_up(n, 64);
+    size_t stride = round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
     hipLaunchKernelGGL(g1_mul_plain_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, pts, sc, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, c->d_flag);
     HIPCK(c, hipGetLastError());
     const int32_t* cur = (const int32_t*)c->ws[c12381_ctx::WS_PROJ];
-    size_t cur_n = n, cur_stride = stride;
-    int slot = c12381_ctx::WS_RED0;
-    while (cur_n > 1) {
-        const size_t m = cur_n > 4096 ? round_up(cur_n / 32, 64) : (cur_n > 64 ? 64 : 1);
-        const size_t m_stride = round_up(m, 64);
-        if ((rc = ensure(c, slot, (size_t)3 * NL * m_stride * 4))) return rc;
-        hipLaunchKernelGGL(g1_reduce_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, cur_n, cur, cur_stride, m, (int32_t*)c->ws[slot], m_stride);
-        HIPCK(c, hipGetLastError());
-        cur = (const int32_t*)c->ws[slot]; cur_n = m; cur_stride = m_stride;
-        slot = slot == c12381_ctx::WS_RED0 ? c12381_ctx::WS_RED1 : c12381_ctx::WS_RED0;
-    }
-    return g1_finish(c, 1, cur, cur_stride, out, fmt);
+    if ((rc = tree_sum(c, g1_reduce_kernel, 3 * NL, n, cur, stride))) return rc;
+    return g1_finish(c, 1, cur, stride, out, fmt);
 }
 int c12381_g1_sum_of_products(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && (!pts || !sc)) || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
-    staged s;
-    if ((rc = stage_in(c, s, pts, 96 * n, sc, 32 * n, (size_t)fmt))) return rc;
-    if ((rc = c12381_g1_sum_of_products_dev(c, n, s.in0, s.in1, s.out, fmt))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt))) return rc;
-    return read_flag(c);
+    int rc = bind(c); if (rc || (rc = g1_msm_args(n, pts, sc, out, fmt, 0u))) return rc;
+    staging s;                                                  // n == 0: the identity, through the _dev form
+    if ((rc = stage(c, s, {{pts, 96 * n}, {sc, 32 * n}}, {{out, (size_t)fmt}})) || (rc = c12381_g1_sum_of_products_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
 }
 // One host process driving several GPUs: terms are split contiguously over the contexts, every
 // context runs its local MSM on its own device from its own host thread, and the partial points (96 B each) are
 // summed on the first context — the elliptic-curve "all-reduce" has no RCCL reduction op, the payload is ngpu x 96 B.
 // (One process per GPU with torch.distributed does the same through an all-gather: crypto12381_amd/distributed.py.)
 int c12381_g1_msm_multi(c12381_ctx** ctxs, int ngpu, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
-    if (!ctxs || ngpu <= 0 || !out || (n && (!pts || !sc)) || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    if (!ctxs || ngpu <= 0 || g1_msm_args(n, pts, sc, out, fmt, 0u)) return C12381_E_ARG;
     for (int g = 0; g < ngpu; ++g) if (!ctxs[g]) return C12381_E_ARG;
     if (ngpu == 1) return c12381_g1_msm(ctxs[0], n, pts, sc, out, fmt);
     std::vector<uint8_t> partial((size_t)96 * ngpu, 0);
@@ -746,9 +748,12 @@ static int g2_finish(c12381_ctx* c, size_t n, uint8_t* d_out, int fmt) {
     return 0;
 }
 // C12381_F_COMPRESSED_IN: pts are n x 97 bytes (g2_point.hpp:73-77 -> ECP2_fromOctet), decoded in the kernel's prologue
+// (also the check of the fixed-base form, with flags 0)
+static int g2_mul_args(const void* pts, const void* sc, const void* out, int fmt, unsigned flags) {
+    return (!pts || !sc || !out || !g2_fmt(fmt) || (flags & ~(unsigned)(C12381_F_IN_SUBGROUP | C12381_F_COMPRESSED_IN))) ? C12381_E_ARG : 0;
+}
 int c12381_g2_mul_batch_flags_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!pts || !sc || !out || (fmt != 97 && fmt != 192) || (flags & ~(unsigned)(C12381_F_IN_SUBGROUP | C12381_F_COMPRESSED_IN))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g2_mul_args(pts, sc, out, fmt, flags))) return rc;
     if (n == 0) return 0;
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)6 * NL * round_up(n, 64) * 4))) return rc;
     if ((rc = g2_mul_dev_strided(c, n, pts, (flags & C12381_F_COMPRESSED_IN) ? 97 : 192, sc, out, fmt, nullptr, true, (flags & C12381_F_IN_SUBGROUP) != 0))) return rc;
@@ -759,9 +764,7 @@ int c12381_g2_mul_batch_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const u
 }
 static int g2_mul_dev_strided(c12381_ctx* c, size_t n, const uint8_t* pts, size_t pt_stride, const uint8_t* sc, uint8_t* out, int fmt,
                               const int32_t* skip_if, bool finish, bool in_g2) {
-    int rc = bind(c); if (rc) return rc;
-    if (!pts || !sc || !out || (fmt != 97 && fmt != 192)) return C12381_E_ARG;
-    if (n == 0) return 0;
+    int rc;
     const size_t chunk = n < G2_CHUNK ? round_up(n, 64) : G2_CHUNK;
     // C12381_G2_LANES=1 keeps the one-lane-per-point kernel for the batch entry points (A/B measurements); default:
     // two lanes per point (k_g2h.hip), whose per-lane table records are those of G1 (2 x 1408 B per point)
@@ -785,14 +788,12 @@ static int g2_mul_dev_strided(c12381_ctx* c, size_t n, const uint8_t* pts, size_
     return 0;
 }
 int c12381_g2_mul_batch_flags(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!pts || !sc || !out || (fmt != 97 && fmt != 192) || (flags & ~(unsigned)(C12381_F_IN_SUBGROUP | C12381_F_COMPRESSED_IN))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g2_mul_args(pts, sc, out, fmt, flags))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, pts, ((flags & C12381_F_COMPRESSED_IN) ? 97 : 192) * n, sc, 32 * n, (size_t)fmt * n))) return rc;
-    if ((rc = c12381_g2_mul_batch_flags_dev(c, n, s.in0, s.in1, s.out, fmt, flags))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{pts, ((flags & C12381_F_COMPRESSED_IN) ? 97 : 192) * n}, {sc, 32 * n}}, {{out, (size_t)fmt * n}}))) return rc;
+    if ((rc = c12381_g2_mul_batch_flags_dev(c, n, s.in[0], s.in[1], s.out[0], fmt, flags))) return rc;
+    return unstage(c, s);
 }
 int c12381_g2_mul_batch(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
     return c12381_g2_mul_batch_flags(c, n, pts, sc, out, fmt, 0u);
@@ -800,11 +801,11 @@ int c12381_g2_mul_batch(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8
 // Π q_i^{x_i} in G2 (scalars == NULL: the plain product of the points, g2_point.hpp:225-236).  The reference evaluates it as n
 // multiply(point2&, big) calls and a chain of add(point2&, point2&); here: the batched scalar multiplication into the
 // projective workspace, then a tree sum (two levels), one affine conversion.  Only the final point is canonical.
+static int g2_msm_args(size_t n, const void* pts, const void* out, int fmt) { return (!out || (n && !pts) || !g2_fmt(fmt)) ? C12381_E_ARG : 0; }
 int c12381_g2_msm_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && !pts) || (fmt != 97 && fmt != 192)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g2_msm_args(n, pts, out, fmt))) return rc;
     if (n == 0) { HIPCK(c, hipMemsetAsync(out, 0, fmt, c->stream)); return 0; }
-    const size_t stride = round_up(n, 64);
+    size_t stride = round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)6 * NL * stride * 4))) return rc;
     if (sc) {
         if ((rc = g2_mul_dev_strided(c, n, pts, 192, sc, out, fmt, nullptr, true))) return rc;
@@ -813,41 +814,30 @@ int c12381_g2_msm_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t
         HIPCK(c, hipGetLastError());
     }
     const int32_t* cur = (const int32_t*)c->ws[c12381_ctx::WS_PROJ];
-    size_t cur_n = n, cur_stride = stride;
-    int slot = c12381_ctx::WS_RED0;
-    while (cur_n > 1) {
-        const size_t m = cur_n > 4096 ? round_up(cur_n / 32, 64) : (cur_n > 64 ? 64 : 1);
-        const size_t m_stride = round_up(m, 64);
-        if ((rc = ensure(c, slot, (size_t)6 * NL * m_stride * 4))) return rc;
-        hipLaunchKernelGGL(g2_reduce_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, cur_n, cur, cur_stride, m, (int32_t*)c->ws[slot], m_stride);
-        HIPCK(c, hipGetLastError());
-        cur = (const int32_t*)c->ws[slot]; cur_n = m; cur_stride = m_stride;
-        slot = slot == c12381_ctx::WS_RED0 ? c12381_ctx::WS_RED1 : c12381_ctx::WS_RED0;
-    }
+    if ((rc = tree_sum(c, g2_reduce_kernel, 6 * NL, n, cur, stride))) return rc;
     if ((rc = ensure(c, c12381_ctx::WS_PREF, (size_t)2 * NL * 64 * 4))) return rc;
-    hipLaunchKernelGGL(g2_finish_kernel, dim3(1), dim3(BLOCK), 0, c->stream, (size_t)1, cur, cur_stride, (int32_t*)c->ws[c12381_ctx::WS_PREF], out, fmt, (size_t)1);
+    hipLaunchKernelGGL(g2_finish_kernel, dim3(1), dim3(BLOCK), 0, c->stream, (size_t)1, cur, stride, (int32_t*)c->ws[c12381_ctx::WS_PREF], out, fmt, (size_t)1);
     HIPCK(c, hipGetLastError());
     return 0;
 }
 int c12381_g2_msm(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && !pts) || (fmt != 97 && fmt != 192)) return C12381_E_ARG;
-    staged s;
-    if ((rc = stage_in(c, s, pts, 192 * n, sc, sc ? 32 * n : 0, (size_t)fmt))) return rc;
-    if ((rc = c12381_g2_msm_dev(c, n, s.in0, sc ? s.in1 : nullptr, s.out, fmt))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt))) return rc;
-    return read_flag(c);
+    int rc = bind(c); if (rc || (rc = g2_msm_args(n, pts, out, fmt))) return rc;
+    staging s;                                                  // n == 0: the identity, through the _dev form
+    if ((rc = stage(c, s, {{pts, 192 * n}, {sc, 32 * n}}, {{out, (size_t)fmt}})) || (rc = c12381_g2_msm_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
+}
+static int g2_add_dev(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, int fmt) {
+    hipLaunchKernelGGL(g2_add_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, a, (size_t)192, b, out, fmt, c->d_flag, (const int32_t*)nullptr);
+    HIPCK(c, hipGetLastError());
+    return 0;
 }
 int c12381_g2_add_batch(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, int fmt) {
     int rc = bind(c); if (rc) return rc;
-    if (!a || !b || !out || (fmt != 97 && fmt != 192)) return C12381_E_ARG;
+    if (!a || !b || !out || !g2_fmt(fmt)) return C12381_E_ARG;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, a, 192 * n, b, 192 * n, (size_t)fmt * n))) return rc;
-    hipLaunchKernelGGL(g2_add_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, s.in0, (size_t)192, s.in1, s.out, fmt, c->d_flag, (const int32_t*)nullptr);
-    HIPCK(c, hipGetLastError());
-    if ((rc = stage_out(c, s, out, (size_t)fmt * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{a, 192 * n}, {b, 192 * n}}, {{out, (size_t)fmt * n}})) || (rc = g2_add_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
 }
 
 // ---------------------------------------------------------------- pairing
@@ -979,9 +969,12 @@ static int launch_pair_eq(c12381_ctx* c, size_t n, const uint8_t* a1, const uint
     HIPCK(c, hipGetLastError());
     return 0;
 }
+// (also the check of c12381_pair_fixed_g2_batch and c12381_miller_batch, with flags 0)
+static int pair_args(const void* g1, const void* g2, const void* gt, unsigned flags) {
+    return (!g1 || !g2 || !gt || (flags & ~(unsigned)C12381_F_COMPRESSED_IN)) ? C12381_E_ARG : 0;
+}
 int c12381_pair_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1 || !g2 || !gt) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_args(g1, g2, gt, 0u))) return rc;
     if (n == 0) return 0;
     if (pair_lanes() != 1 && pair_use_queue(n)) {            // workspace and its reset stay outside the timed bracket
         uint4* st; unsigned int *fl, *ct, ep; unsigned blocks;
@@ -999,8 +992,7 @@ int c12381_pair_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, const uint
 // so the decoding runs as its own two kernels into a workspace (288 B per pairing, against ~280 ns of arithmetic); a rejected
 // encoding becomes an off-curve record there and surfaces exactly like an invalid 96 / 192-byte input: 0xff lane, C12381_E_POINT.
 int c12381_pair_batch_flags_dev(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1 || !g2 || !gt || (flags & ~(unsigned)C12381_F_COMPRESSED_IN)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_args(g1, g2, gt, flags))) return rc;
     if (n == 0) return 0;
     if (!(flags & C12381_F_COMPRESSED_IN)) return c12381_pair_batch_dev(c, n, g1, g2, gt);
     if ((rc = ensure(c, c12381_ctx::WS_DEC1, 96 * n))) return rc;
@@ -1012,21 +1004,21 @@ int c12381_pair_batch_flags_dev(c12381_ctx* c, size_t n, const uint8_t* g1, cons
     return c12381_pair_batch_dev(c, n, d1, d2, gt);
 }
 int c12381_pair_batch_flags(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1 || !g2 || !gt || (flags & ~(unsigned)C12381_F_COMPRESSED_IN)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_args(g1, g2, gt, flags))) return rc;
     if (n == 0) return 0;
     const bool comp = (flags & C12381_F_COMPRESSED_IN) != 0;
-    staged s;
-    if ((rc = stage_in(c, s, g1, (comp ? 49 : 96) * n, g2, (comp ? 97 : 192) * n, 576 * n))) return rc;
-    if ((rc = c12381_pair_batch_flags_dev(c, n, s.in0, s.in1, s.out, flags))) return rc;
-    if ((rc = stage_out(c, s, gt, 576 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{g1, (comp ? 49 : 96) * n}, {g2, (comp ? 97 : 192) * n}}, {{gt, 576 * n}}))) return rc;
+    if ((rc = c12381_pair_batch_flags_dev(c, n, s.in[0], s.in[1], s.out[0], flags))) return rc;
+    return unstage(c, s);
 }
 int c12381_pair_batch(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt) { return c12381_pair_batch_flags(c, n, g1, g2, gt, 0u); }
 // Product of k pairings per element with shared squarings (pair3_prod_kernel)
+static int pair_product_args(int k, const void* g1s, const void* g2s, const void* gt, unsigned flags) {
+    return (!g1s || !g2s || !gt || k < 1 || k > MAX_PROD || (flags & ~(unsigned)C12381_F_MILLER_ONLY)) ? C12381_E_ARG : 0;
+}
 int c12381_pair_product_batch_dev(c12381_ctx* c, size_t n, int k, const uint8_t* g1s, const uint8_t* g2s, uint8_t* gt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1s || !g2s || !gt || k < 1 || k > MAX_PROD || (flags & ~(unsigned)C12381_F_MILLER_ONLY)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_product_args(k, g1s, g2s, gt, flags))) return rc;
     if (n == 0) return 0;
     timed tm(c, 3);
     hipLaunchKernelGGL(pair3_prod_kernel, dim3(grid_tri(n)), dim3(BLOCK), 0, c->stream, n, k, g1s, g2s, gt, c->d_flag, (flags & C12381_F_MILLER_ONLY) ? 1 : 0);
@@ -1034,22 +1026,19 @@ int c12381_pair_product_batch_dev(c12381_ctx* c, size_t n, int k, const uint8_t*
     return 0;
 }
 int c12381_pair_product_batch(c12381_ctx* c, size_t n, int k, const uint8_t* g1s, const uint8_t* g2s, uint8_t* gt, unsigned flags) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1s || !g2s || !gt || k < 1 || k > MAX_PROD || (flags & ~(unsigned)C12381_F_MILLER_ONLY)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_product_args(k, g1s, g2s, gt, flags))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, g1s, 96 * n * (size_t)k, g2s, 192 * n * (size_t)k, 576 * n))) return rc;
-    if ((rc = c12381_pair_product_batch_dev(c, n, k, s.in0, s.in1, s.out, flags))) return rc;
-    if ((rc = stage_out(c, s, gt, 576 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{g1s, 96 * n * (size_t)k}, {g2s, 192 * n * (size_t)k}}, {{gt, 576 * n}}))) return rc;
+    if ((rc = c12381_pair_product_batch_dev(c, n, k, s.in[0], s.in[1], s.out[0], flags))) return rc;
+    return unstage(c, s);
 }
 static int lines_table(c12381_ctx* c, int slot, const uint8_t* d_q192, int need_g2);
 // gt[i] = e(P_i, Q) with ONE G2 argument for the batch: the 69 line-coefficient triples of Q are computed once (and kept
 // until Q changes), every element then runs the table-driven Miller loop.  Same field elements as the running-point loop,
 // so the GT bytes equal c12381_pair_batch on n copies of Q for every Q, infinity included.
 int c12381_pair_fixed_g2_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2_192, uint8_t* gt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1 || !g2_192 || !gt) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_args(g1, g2_192, gt, 0u))) return rc;
     if (n == 0) return 0;
     if ((rc = lines_table(c, c12381_ctx::WS_FQ_P, g2_192, 0))) return rc;
     uint4* st; unsigned int *fl, *ct; unsigned blocks;
@@ -1062,75 +1051,61 @@ int c12381_pair_fixed_g2_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, c
     return 0;
 }
 int c12381_pair_fixed_g2_batch(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2_192, uint8_t* gt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1 || !g2_192 || !gt) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_args(g1, g2_192, gt, 0u))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, g1, 96 * n, g2_192, 192, 576 * n))) return rc;
-    if ((rc = c12381_pair_fixed_g2_batch_dev(c, n, s.in0, s.in1, s.out))) return rc;
-    if ((rc = stage_out(c, s, gt, 576 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{g1, 96 * n}, {g2_192, 192}}, {{gt, 576 * n}})) || (rc = c12381_pair_fixed_g2_batch_dev(c, n, s.in[0], s.in[1], s.out[0]))) return rc;
+    return unstage(c, s);
 }
+static int pair_eq_args(const void* a1, const void* a2, const void* b1, const void* b2, const void* ok) { return (!a1 || !a2 || !b1 || !b2 || !ok) ? C12381_E_ARG : 0; }
 int c12381_pair_eq_batch_dev(c12381_ctx* c, size_t n, const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, uint8_t* ok) {
-    int rc = bind(c); if (rc) return rc;
-    if (!a1 || !a2 || !b1 || !b2 || !ok) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_eq_args(a1, a2, b1, b2, ok))) return rc;
     if (n == 0) return 0;
     timed tm(c, 4);
     return launch_pair_eq(c, n, a1, a2, b1, b2, (size_t)192, ok);
 }
 int c12381_pair_eq_batch(c12381_ctx* c, size_t n, const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, uint8_t* ok) {
-    int rc = bind(c); if (rc) return rc;
-    if (!a1 || !a2 || !b1 || !b2 || !ok) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_eq_args(a1, a2, b1, b2, ok))) return rc;
     if (n == 0) return 0;
-    int r2;
-    if ((r2 = ensure(c, c12381_ctx::WS_IN0, round_up(96 * n, 256)))) return r2;
-    if ((r2 = ensure(c, c12381_ctx::WS_IN1, round_up(192 * n, 256)))) return r2;
-    if ((r2 = ensure(c, c12381_ctx::WS_RED0, round_up(96 * n, 256)))) return r2;
-    if ((r2 = ensure(c, c12381_ctx::WS_RED1, round_up(192 * n, 256)))) return r2;
-    if ((r2 = ensure(c, c12381_ctx::WS_OUT, round_up(n, 256)))) return r2;
-    uint8_t* d_a1 = (uint8_t*)c->ws[c12381_ctx::WS_IN0]; uint8_t* d_a2 = (uint8_t*)c->ws[c12381_ctx::WS_IN1];
-    uint8_t* d_b1 = (uint8_t*)c->ws[c12381_ctx::WS_RED0]; uint8_t* d_b2 = (uint8_t*)c->ws[c12381_ctx::WS_RED1];
-    uint8_t* d_ok = (uint8_t*)c->ws[c12381_ctx::WS_OUT];
-    HIPCK(c, hipMemcpyAsync(d_a1, a1, 96 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d_a2, a2, 192 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d_b1, b1, 96 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d_b2, b2, 192 * n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = c12381_pair_eq_batch_dev(c, n, d_a1, d_a2, d_b1, d_b2, d_ok))) return rc;
-    HIPCK(c, hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c->stream));
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{a1, 96 * n}, {a2, 192 * n}, {b1, 96 * n}, {b2, 192 * n}}, {{ok, n}}))) return rc;
+    if ((rc = c12381_pair_eq_batch_dev(c, n, s.in[0], s.in[1], s.in[2], s.in[3], s.out[0]))) return rc;
+    return unstage(c, s);
 }
 
 // ---------------------------------------------------------------- decode / split pairing / GT
+static int decompress_args(const void* in, const void* out, const void* status) { return (!in || !out || !status) ? C12381_E_ARG : 0; }
 int c12381_g1_decompress_batch_dev(c12381_ctx* c, size_t n, const uint8_t* in49, uint8_t* out96, uint8_t* status) {
-    int rc = bind(c); if (rc) return rc;
-    if (!in49 || !out96 || !status) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = decompress_args(in49, out96, status))) return rc;
     if (n == 0) return 0;
     hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, in49, out96, status, 0);
     HIPCK(c, hipGetLastError());
     return 0;
 }
 int c12381_g2_decompress_batch_dev(c12381_ctx* c, size_t n, const uint8_t* in97, uint8_t* out192, uint8_t* status) {
-    int rc = bind(c); if (rc) return rc;
-    if (!in97 || !out192 || !status) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = decompress_args(in97, out192, status))) return rc;
     if (n == 0) return 0;
     hipLaunchKernelGGL(g2_decompress_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, in97, out192, status, 0);
     HIPCK(c, hipGetLastError());
     return 0;
 }
 int c12381_g1_decompress_batch(c12381_ctx* c, size_t n, const uint8_t* in49, uint8_t* out96, uint8_t* status) {
-    int rc = bind(c); if (rc) return rc;
-    if (!in49 || !out96 || !status) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = decompress_args(in49, out96, status))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, in49, 49 * n, nullptr, n, 96 * n))) return rc;
-    hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, s.in0, s.out, s.in1, 0);
-    HIPCK(c, hipGetLastError());
-    if ((rc = stage_out(c, s, out96, 96 * n))) return rc;
-    HIPCK(c, hipMemcpyAsync(status, s.in1, n, hipMemcpyDeviceToHost, c->stream));
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{in49, 49 * n}}, {{out96, 96 * n}, {status, n}})) || (rc = c12381_g1_decompress_batch_dev(c, n, s.in[0], s.out[0], s.out[1]))) return rc;
+    return unstage(c, s);
+}
+int c12381_g2_decompress_batch(c12381_ctx* c, size_t n, const uint8_t* in97, uint8_t* out192, uint8_t* status) {
+    int rc = bind(c); if (rc || (rc = decompress_args(in97, out192, status))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{in97, 97 * n}}, {{out192, 192 * n}, {status, n}})) || (rc = c12381_g2_decompress_batch_dev(c, n, s.in[0], s.out[0], s.out[1]))) return rc;
+    return unstage(c, s);
 }
 // ---------------------------------------------------------------- hash-to-G1, Zp helpers
-static int g1_map_common(c12381_ctx* c, size_t n, const uint8_t* d_in, int mode, uint8_t* d_out, int fmt) {
+// mode 0: 64-byte digests (hash to G1), 1: field elements (map to the curve), 2: points (cofactor clearing)
+static int g1_map_dev(c12381_ctx* c, size_t n, const uint8_t* d_in, int mode, uint8_t* d_out, int fmt) {
     const size_t stride = round_up(n, 64);
     int rc;
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
@@ -1139,41 +1114,34 @@ static int g1_map_common(c12381_ctx* c, size_t n, const uint8_t* d_in, int mode,
     HIPCK(c, hipGetLastError());
     return g1_finish(c, n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, d_out, fmt);
 }
+static int g1_from_hash_args(const void* digests, const void* out, int fmt) { return (!digests || !out || !g1_fmt(fmt)) ? C12381_E_ARG : 0; }
 int c12381_g1_from_hash_batch_dev(c12381_ctx* c, size_t n, const uint8_t* digests, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!digests || !out || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_from_hash_args(digests, out, fmt))) return rc;
     if (n == 0) return 0;
-    return g1_map_common(c, n, digests, 0, out, fmt);
+    return g1_map_dev(c, n, digests, 0, out, fmt);
 }
 int c12381_g1_from_hash_batch(c12381_ctx* c, size_t n, const uint8_t* digests, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!digests || !out || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_from_hash_args(digests, out, fmt))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, digests, 64 * n, nullptr, 0, (size_t)fmt * n))) return rc;
-    if ((rc = g1_map_common(c, n, s.in0, 0, s.out, fmt))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{digests, 64 * n}}, {{out, (size_t)fmt * n}})) || (rc = c12381_g1_from_hash_batch_dev(c, n, s.in[0], s.out[0], fmt))) return rc;
+    return unstage(c, s);
 }
 int c12381_g1_map_to_point_batch(c12381_ctx* c, size_t n, const uint8_t* u48, uint8_t* out96) {
     int rc = bind(c); if (rc) return rc;
     if (!u48 || !out96) return C12381_E_ARG;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, u48, 48 * n, nullptr, 0, 96 * n))) return rc;
-    if ((rc = g1_map_common(c, n, s.in0, 1, s.out, 96))) return rc;
-    if ((rc = stage_out(c, s, out96, 96 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{u48, 48 * n}}, {{out96, 96 * n}})) || (rc = g1_map_dev(c, n, s.in[0], 1, s.out[0], 96))) return rc;
+    return unstage(c, s);
 }
 int c12381_g1_clear_cofactor_batch(c12381_ctx* c, size_t n, const uint8_t* in96, uint8_t* out96) {
     int rc = bind(c); if (rc) return rc;
     if (!in96 || !out96) return C12381_E_ARG;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, in96, 96 * n, nullptr, 0, 96 * n))) return rc;
-    if ((rc = g1_map_common(c, n, s.in0, 2, s.out, 96))) return rc;
-    if ((rc = stage_out(c, s, out96, 96 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{in96, 96 * n}}, {{out96, 96 * n}})) || (rc = g1_map_dev(c, n, s.in[0], 2, s.out[0], 96))) return rc;
+    return unstage(c, s);
 }
 // out[i] = 1 / (x[i] + gamma) (gamma may be null), simultaneous inversion in runs of ZP_INV_RUN (k_hash_zp.hip)
 static int zp_batch_inverse(c12381_ctx* c, size_t n, const uint8_t* x, const uint8_t* gamma, uint8_t* out) {
@@ -1184,9 +1152,9 @@ static int zp_batch_inverse(c12381_ctx* c, size_t n, const uint8_t* x, const uin
     HIPCK(c, hipGetLastError());
     return 0;
 }
+static int zp_op_args(int op, const void* a, const void* b, const void* out) { return (op < 0 || op > 4 || !a || !out || (op <= 2 && !b)) ? C12381_E_ARG : 0; }
 int c12381_zp_op_batch_dev(c12381_ctx* c, int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (op < 0 || op > 4 || !a || !out || (op <= 2 && !b)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = zp_op_args(op, a, b, out))) return rc;
     if (n == 0) return 0;
     if (op == 4) return zp_batch_inverse(c, n, a, nullptr, out);
     hipLaunchKernelGGL(zp_op_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, op, n, a, op <= 2 ? b : nullptr, out);
@@ -1194,30 +1162,29 @@ int c12381_zp_op_batch_dev(c12381_ctx* c, int op, size_t n, const uint8_t* a, co
     return 0;
 }
 int c12381_zp_op_batch(c12381_ctx* c, int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (op < 0 || op > 4 || !a || !out || (op <= 2 && !b)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = zp_op_args(op, a, b, out))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, a, 32 * n, op <= 2 ? b : nullptr, op <= 2 ? 32 * n : 0, 32 * n))) return rc;
-    if ((rc = c12381_zp_op_batch_dev(c, op, n, s.in0, s.in1, s.out))) return rc;
-    if ((rc = stage_out(c, s, out, 32 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{a, 32 * n}, {op <= 2 ? b : nullptr, 32 * n}}, {{out, 32 * n}})) || (rc = c12381_zp_op_batch_dev(c, op, n, s.in[0], s.in[1], s.out[0]))) return rc;
+    return unstage(c, s);
+}
+static int zp_from_hash_dev(c12381_ctx* c, size_t n, const uint8_t* digests, uint8_t* out) {
+    hipLaunchKernelGGL(zp_from_hash_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, digests, out);
+    HIPCK(c, hipGetLastError());
+    return 0;
 }
 int c12381_zp_from_hash_batch(c12381_ctx* c, size_t n, const uint8_t* digests, uint8_t* out) {
     int rc = bind(c); if (rc) return rc;
     if (!digests || !out) return C12381_E_ARG;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, digests, 64 * n, nullptr, 0, 32 * n))) return rc;
-    hipLaunchKernelGGL(zp_from_hash_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, s.in0, s.out);
-    HIPCK(c, hipGetLastError());
-    if ((rc = stage_out(c, s, out, 32 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{digests, 64 * n}}, {{out, 32 * n}})) || (rc = zp_from_hash_dev(c, n, s.in[0], s.out[0]))) return rc;
+    return unstage(c, s);
 }
+static int zp_inner_product_args(size_t n, const void* a, const void* out) { return (!out || (n && !a)) ? C12381_E_ARG : 0; }
 // strided partial sums, 64 terms per lane and stage, ping-pong between two reduction slots
 int c12381_zp_inner_product_dev(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && !a)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = zp_inner_product_args(n, a, out))) return rc;
     if (n == 0) { HIPCK(c, hipMemsetAsync(out, 0, 32, c->stream)); return 0; }
     const uint8_t *cur_a = a, *cur_b = b;
     size_t cur_n = n;
@@ -1237,28 +1204,13 @@ int c12381_zp_inner_product_dev(c12381_ctx* c, size_t n, const uint8_t* a, const
     }
 }
 int c12381_zp_inner_product(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (!out || (n && !a)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = zp_inner_product_args(n, a, out))) return rc;
     if (n == 0) { std::memset(out, 0, 32); return 0; }
-    staged s;
-    if ((rc = stage_in(c, s, a, 32 * n, b, b ? 32 * n : 0, 32))) return rc;
-    if ((rc = c12381_zp_inner_product_dev(c, n, s.in0, b ? s.in1 : nullptr, s.out))) return rc;
-    if ((rc = stage_out(c, s, out, 32))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{a, 32 * n}, {b, 32 * n}}, {{out, 32}})) || (rc = c12381_zp_inner_product_dev(c, n, s.in[0], s.in[1], s.out[0]))) return rc;
+    return unstage(c, s);
 }
 
-int c12381_g2_decompress_batch(c12381_ctx* c, size_t n, const uint8_t* in97, uint8_t* out192, uint8_t* status) {
-    int rc = bind(c); if (rc) return rc;
-    if (!in97 || !out192 || !status) return C12381_E_ARG;
-    if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, in97, 97 * n, nullptr, n, 192 * n))) return rc;
-    hipLaunchKernelGGL(g2_decompress_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, s.in0, s.out, s.in1, 0);
-    HIPCK(c, hipGetLastError());
-    if ((rc = stage_out(c, s, out192, 192 * n))) return rc;
-    HIPCK(c, hipMemcpyAsync(status, s.in1, n, hipMemcpyDeviceToHost, c->stream));
-    return read_flag(c);
-}
 static int launch_miller(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out) {
 #ifdef C12381_EXPERIMENTS
     if (pair_lanes() == 1) { hipLaunchKernelGGL(miller_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, g1, g2, out, c->d_flag); HIPCK(c, hipGetLastError()); return 0; }
@@ -1315,58 +1267,50 @@ static int launch_gt_is_unity(c12381_ctx* c, size_t n, const uint8_t* a, uint8_t
     HIPCK(c, hipGetLastError());
     return 0;
 }
-int c12381_miller_batch(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out576) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1 || !g2 || !out576) return C12381_E_ARG;
-    if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, g1, 96 * n, g2, 192 * n, 576 * n))) return rc;
-    if ((rc = launch_miller(c, n, s.in0, s.in1, s.out))) return rc;
-    if ((rc = stage_out(c, s, out576, 576 * n))) return rc;
-    return read_flag(c);
-}
 int c12381_miller_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out576) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1 || !g2 || !out576) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = pair_args(g1, g2, out576, 0u))) return rc;
     if (n == 0) return 0;
     timed tm(c, 6);
     return launch_miller(c, n, g1, g2, out576);
 }
-int c12381_gt_op_batch(c12381_ctx* c, int op, size_t n, const uint8_t* a576, const uint8_t* b, uint8_t* out576) {
-    int rc = bind(c); if (rc) return rc;
-    if (op < 0 || op > 3 || !a576 || !out576 || ((op == 0 || op == 2) && !b)) return C12381_E_ARG;
+int c12381_miller_batch(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out576) {
+    int rc = bind(c); if (rc || (rc = pair_args(g1, g2, out576, 0u))) return rc;
     if (n == 0) return 0;
-    staged s;
-    const size_t bb = op == 0 ? 576 * n : (op == 2 ? 32 * n : 0);
-    if ((rc = stage_in(c, s, a576, 576 * n, bb ? b : nullptr, bb, 576 * n))) return rc;
-    if ((rc = launch_gt_op(c, op, n, s.in0, s.in1, s.out))) return rc;
-    if ((rc = stage_out(c, s, out576, 576 * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{g1, 96 * n}, {g2, 192 * n}}, {{out576, 576 * n}})) || (rc = c12381_miller_batch_dev(c, n, s.in[0], s.in[1], s.out[0]))) return rc;
+    return unstage(c, s);
+}
+static int gt_op_args(int op, const void* a, const void* b, const void* out) {
+    return (op < 0 || op > 3 || !a || !out || ((op == 0 || op == 2) && !b)) ? C12381_E_ARG : 0;
 }
 int c12381_gt_op_batch_dev(c12381_ctx* c, int op, size_t n, const uint8_t* a576, const uint8_t* b, uint8_t* out576) {
-    int rc = bind(c); if (rc) return rc;
-    if (op < 0 || op > 3 || !a576 || !out576 || ((op == 0 || op == 2) && !b)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = gt_op_args(op, a576, b, out576))) return rc;
     if (n == 0) return 0;
     timed tm(c, 7);
     return launch_gt_op(c, op, n, a576, b, out576);
 }
+int c12381_gt_op_batch(c12381_ctx* c, int op, size_t n, const uint8_t* a576, const uint8_t* b, uint8_t* out576) {
+    int rc = bind(c); if (rc || (rc = gt_op_args(op, a576, b, out576))) return rc;
+    if (n == 0) return 0;
+    const size_t bb = op == 0 ? 576 * n : (op == 2 ? 32 * n : 0);
+    staging s;
+    if ((rc = stage(c, s, {{a576, 576 * n}, {bb ? b : nullptr, bb}}, {{out576, 576 * n}})) || (rc = c12381_gt_op_batch_dev(c, op, n, s.in[0], s.in[1], s.out[0]))) return rc;
+    return unstage(c, s);
+}
 int c12381_fexp_batch(c12381_ctx* c, size_t n, const uint8_t* in576, uint8_t* out576) { return c12381_gt_op_batch(c, 3, n, in576, nullptr, out576); }
 int c12381_fexp_batch_dev(c12381_ctx* c, size_t n, const uint8_t* in576, uint8_t* out576) { return c12381_gt_op_batch_dev(c, 3, n, in576, nullptr, out576); }
-int c12381_gt_is_unity_batch(c12381_ctx* c, size_t n, const uint8_t* a576, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (!a576 || !out) return C12381_E_ARG;
-    if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, a576, 576 * n, nullptr, 0, n))) return rc;
-    if ((rc = launch_gt_is_unity(c, n, s.in0, s.out))) return rc;
-    if ((rc = stage_out(c, s, out, n))) return rc;
-    return read_flag(c);
-}
+static int gt_is_unity_args(const void* a, const void* out) { return (!a || !out) ? C12381_E_ARG : 0; }
 int c12381_gt_is_unity_batch_dev(c12381_ctx* c, size_t n, const uint8_t* a576, uint8_t* out) {
-    int rc = bind(c); if (rc) return rc;
-    if (!a576 || !out) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = gt_is_unity_args(a576, out))) return rc;
     if (n == 0) return 0;
     return launch_gt_is_unity(c, n, a576, out);
+}
+int c12381_gt_is_unity_batch(c12381_ctx* c, size_t n, const uint8_t* a576, uint8_t* out) {
+    int rc = bind(c); if (rc || (rc = gt_is_unity_args(a576, out))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{a576, 576 * n}}, {{out, n}})) || (rc = c12381_gt_is_unity_batch_dev(c, n, s.in[0], s.out[0]))) return rc;
+    return unstage(c, s);
 }
 
 // Fixed-base tables (fixed_base.hpp): make sure slot `slot` holds the table of the point at `d_base`; everything is
@@ -1410,8 +1354,7 @@ static bool fixed_base_enabled() {
 
 // ---------------------------------------------------------------- one base for the whole batch (g^x_i)
 int c12381_g1_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base96, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!base96 || !sc || !out || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_mul_args(base96, sc, out, fmt, 0u))) return rc;
     if (n == 0) return 0;
     const size_t stride = round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
@@ -1427,18 +1370,14 @@ int c12381_g1_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base96
     return g1_finish(c, n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, out, fmt);
 }
 int c12381_g1_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base96, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!base96 || !sc || !out || (fmt != 49 && fmt != 96)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g1_mul_args(base96, sc, out, fmt, 0u))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, sc, 32 * n, base96, 96, (size_t)fmt * n))) return rc;
-    if ((rc = c12381_g1_mul_fixed_batch_dev(c, n, s.in1, s.in0, s.out, fmt))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{base96, 96}, {sc, 32 * n}}, {{out, (size_t)fmt * n}})) || (rc = c12381_g1_mul_fixed_batch_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
 }
 int c12381_g2_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base192, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!base192 || !sc || !out || (fmt != 97 && fmt != 192)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g2_mul_args(base192, sc, out, fmt, 0u))) return rc;
     if (n == 0) return 0;
     const int32_t* skip = nullptr;
     const size_t stride = round_up(n, 64);
@@ -1454,14 +1393,11 @@ int c12381_g2_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base19
     return g2_finish(c, n, out, fmt);
 }
 int c12381_g2_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base192, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc) return rc;
-    if (!base192 || !sc || !out || (fmt != 97 && fmt != 192)) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = g2_mul_args(base192, sc, out, fmt, 0u))) return rc;
     if (n == 0) return 0;
-    staged s;
-    if ((rc = stage_in(c, s, sc, 32 * n, base192, 192, (size_t)fmt * n))) return rc;
-    if ((rc = c12381_g2_mul_fixed_batch_dev(c, n, s.in1, s.in0, s.out, fmt))) return rc;
-    if ((rc = stage_out(c, s, out, (size_t)fmt * n))) return rc;
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{base192, 192}, {sc, 32 * n}}, {{out, (size_t)fmt * n}})) || (rc = c12381_g2_mul_fixed_batch_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
 }
 
 // B_j = g1 + r_j h0 + sum_i m_ij h_i for a batch of BBS+ signatures (bbs+.cpp:51, :72): (nmsg + 1) columns of n scalar
@@ -1502,11 +1438,14 @@ static int bbs_message_points(c12381_ctx* c, size_t n, size_t nmsg, const uint8_
 // reference's examples/bbs-plus/src/bbs+.cpp:57-73, evaluated as liner_pair.hpp:339-350 does (two Miller loops,
 // one final exponentiation).  Message scalars are message-major: m[i*n + j] belongs to signature j.  All
 // pointers are DEVICE pointers; the public parameters are single points.
+static int bbs_verify_args(size_t nmsg, const void* g1_96, const void* g2_192, const void* h0_96, const void* h_96, const void* w_192, const void* A_96,
+                           const void* x_32, const void* r_32, const void* m_32, const void* ok) {
+    return (!g1_96 || !g2_192 || !h0_96 || !w_192 || !A_96 || !x_32 || !r_32 || !ok || (nmsg && (!h_96 || !m_32))) ? C12381_E_ARG : 0;
+}
 int c12381_bbs_plus_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g1_96, const uint8_t* g2_192, const uint8_t* h0_96,
                                      const uint8_t* h_96, const uint8_t* w_192, const uint8_t* A_96, const uint8_t* x_32, const uint8_t* r_32,
                                      const uint8_t* m_32, uint8_t* ok) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1_96 || !g2_192 || !h0_96 || !w_192 || !A_96 || !x_32 || !r_32 || !ok || (nmsg && (!h_96 || !m_32))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_verify_args(nmsg, g1_96, g2_192, h0_96, h_96, w_192, A_96, x_32, r_32, m_32, ok))) return rc;
     if (n == 0) return 0;
     // Q_j = w + x_j g2
     if ((rc = ensure(c, c12381_ctx::WS_BBS_Q, 192 * n))) return rc;
@@ -1568,26 +1507,13 @@ int c12381_bbs_plus_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const
 int c12381_bbs_plus_verify_batch(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g1_96, const uint8_t* g2_192, const uint8_t* h0_96,
                                  const uint8_t* h_96, const uint8_t* w_192, const uint8_t* A_96, const uint8_t* x_32, const uint8_t* r_32,
                                  const uint8_t* m_32, uint8_t* ok) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1_96 || !g2_192 || !h0_96 || !w_192 || !A_96 || !x_32 || !r_32 || !ok || (nmsg && (!h_96 || !m_32))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_verify_args(nmsg, g1_96, g2_192, h0_96, h_96, w_192, A_96, x_32, r_32, m_32, ok))) return rc;
     if (n == 0) return 0;
-    // one staging slab: public parameters, then the per-signature arrays
-    const size_t o_g1 = 0, o_g2 = 96, o_h0 = 288, o_w = 384, o_h = 576, o_A = round_up(o_h + 96 * nmsg, 256), o_x = o_A + 96 * n,
-                 o_r = o_x + 32 * n, o_m = o_r + 32 * n, o_ok = round_up(o_m + 32 * n * nmsg, 256), bytes = o_ok + round_up(n, 256);
-    if ((rc = ensure(c, c12381_ctx::WS_BBS_IN, bytes))) return rc;
-    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS_IN];
-    HIPCK(c, hipMemcpyAsync(d + o_g1, g1_96, 96, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_g2, g2_192, 192, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_h0, h0_96, 96, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_w, w_192, 192, hipMemcpyHostToDevice, c->stream));
-    if (nmsg) HIPCK(c, hipMemcpyAsync(d + o_h, h_96, 96 * nmsg, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_A, A_96, 96 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_x, x_32, 32 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_r, r_32, 32 * n, hipMemcpyHostToDevice, c->stream));
-    if (nmsg) HIPCK(c, hipMemcpyAsync(d + o_m, m_32, 32 * n * nmsg, hipMemcpyHostToDevice, c->stream));
-    if ((rc = c12381_bbs_plus_verify_batch_dev(c, n, nmsg, d + o_g1, d + o_g2, d + o_h0, d + o_h, d + o_w, d + o_A, d + o_x, d + o_r, d + o_m, d + o_ok))) return rc;
-    HIPCK(c, hipMemcpyAsync(ok, d + o_ok, n, hipMemcpyDeviceToHost, c->stream));
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{g1_96, 96}, {g2_192, 192}, {h0_96, 96}, {h_96, 96 * nmsg}, {w_192, 192}, {A_96, 96 * n}, {x_32, 32 * n}, {r_32, 32 * n},
+                           {m_32, 32 * n * nmsg}}, {{ok, n}}))) return rc;
+    if ((rc = c12381_bbs_plus_verify_batch_dev(c, n, nmsg, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.in[5], s.in[6], s.in[7], s.in[8], s.out[0]))) return rc;
+    return unstage(c, s);
 }
 
 // ---------------------------------------------------------------- BBS+ verification from the wire formats
@@ -1595,13 +1521,15 @@ int c12381_bbs_plus_verify_batch(c12381_ctx* c, size_t n, size_t nmsg, const uin
 // A (g1/g2_decompress_kernel), parse x and r, encode the message bytes (bbs_wire_prep_kernel), then the
 // verification pipeline above (f2).  Every message has msg_len bytes (ceil(msg_len / 31) units; more units than h entries is
 // the reference's "message is too long": C12381_E_ARG).  ok[j] = 1 / 0, or 0xff where the reference would throw.
+static int bbs_wire_args(size_t nh, size_t msg_len, const void* g1_g2_h0_195, const void* h_49, const void* pk_97, const void* sig_145, const void* msgs,
+                         const void* ok) {
+    return (!g1_g2_h0_195 || !pk_97 || !sig_145 || !ok || (nh && !h_49) || (msg_len && !msgs) || (msg_len + 30) / 31 > nh) ? C12381_E_ARG : 0;
+}
 int c12381_bbs_plus_verify_wire_batch_dev(c12381_ctx* c, size_t n, size_t nh, size_t msg_len, const uint8_t* g1_g2_h0_195, const uint8_t* h_49,
                                           const uint8_t* pk_97, const uint8_t* sig_145, const uint8_t* msgs, uint8_t* ok) {
-    int rc = bind(c); if (rc) return rc;
-    const size_t nblk = (msg_len + 30) / 31;
-    if (!g1_g2_h0_195 || !pk_97 || !sig_145 || !ok || (nh && !h_49) || (msg_len && !msgs) || nblk > nh) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_wire_args(nh, msg_len, g1_g2_h0_195, h_49, pk_97, sig_145, msgs, ok))) return rc;
     if (n == 0) return 0;
-    const size_t npub1 = 2 + nblk;
+    const size_t nblk = (msg_len + 30) / 31, npub1 = 2 + nblk;
     // slab: [pub G1 49s][pub G2 97s][pub G1 96s: g1, h0, h...][pub G2 192s: g2, w][status pub1][status pub2] | per signature: a49, A96, x, r, m, status x2
     const size_t o_p49 = 0, o_p97 = round_up(o_p49 + 49 * npub1, 16), o_p96 = round_up(o_p97 + 2 * 97, 256), o_p192 = o_p96 + 96 * npub1,
                  o_st1 = round_up(o_p192 + 384, 16), o_st2 = o_st1 + round_up(npub1, 16), o_a49 = round_up(o_st2 + 16, 256),
@@ -1632,22 +1560,12 @@ int c12381_bbs_plus_verify_wire_batch_dev(c12381_ctx* c, size_t n, size_t nh, si
 }
 int c12381_bbs_plus_verify_wire_batch(c12381_ctx* c, size_t n, size_t nh, size_t msg_len, const uint8_t* g1_g2_h0_195, const uint8_t* h_49,
                                       const uint8_t* pk_97, const uint8_t* sig_145, const uint8_t* msgs, uint8_t* ok) {
-    int rc = bind(c); if (rc) return rc;
-    const size_t nblk = (msg_len + 30) / 31;
-    if (!g1_g2_h0_195 || !pk_97 || !sig_145 || !ok || (nh && !h_49) || (msg_len && !msgs) || nblk > nh) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_wire_args(nh, msg_len, g1_g2_h0_195, h_49, pk_97, sig_145, msgs, ok))) return rc;
     if (n == 0) return 0;
-    const size_t o_pp = 0, o_pk = 256, o_h = 512, o_sig = round_up(o_h + 49 * nh, 256), o_msg = round_up(o_sig + 145 * n, 256),
-                 o_ok = round_up(o_msg + msg_len * n, 256), bytes = o_ok + round_up(n, 256);
-    if ((rc = ensure(c, c12381_ctx::WS_BBS_WIRE_IN, bytes))) return rc;
-    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS_WIRE_IN];
-    HIPCK(c, hipMemcpyAsync(d + o_pp, g1_g2_h0_195, 195, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_pk, pk_97, 97, hipMemcpyHostToDevice, c->stream));
-    if (nh) HIPCK(c, hipMemcpyAsync(d + o_h, h_49, 49 * nh, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_sig, sig_145, 145 * n, hipMemcpyHostToDevice, c->stream));
-    if (msg_len) HIPCK(c, hipMemcpyAsync(d + o_msg, msgs, msg_len * n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = c12381_bbs_plus_verify_wire_batch_dev(c, n, nh, msg_len, d + o_pp, d + o_h, d + o_pk, d + o_sig, d + o_msg, d + o_ok))) return rc;
-    HIPCK(c, hipMemcpyAsync(ok, d + o_ok, n, hipMemcpyDeviceToHost, c->stream));
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{g1_g2_h0_195, 195}, {h_49, 49 * nh}, {pk_97, 97}, {sig_145, 145 * n}, {msgs, msg_len * n}}, {{ok, n}}))) return rc;
+    if ((rc = c12381_bbs_plus_verify_wire_batch_dev(c, n, nh, msg_len, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.out[0]))) return rc;
+    return unstage(c, s);
 }
 
 // ---------------------------------------------------------------- BBS+ aggregate verification (optional)
@@ -1661,13 +1579,16 @@ int c12381_bbs_plus_verify_wire_batch(c12381_ctx* c, size_t n, size_t nh, size_t
 // 2^-k over k-bit uniform rho_j.  all_ok = 0 settles nothing: the caller then runs the per-signature entry.
 // The reference has no such mode (it verifies one signature at a time, bbs+.cpp:57-73); the booleans of
 // c12381_bbs_plus_verify_batch stay the parity surface.
+static int bbs_aggregate_args(size_t n, size_t nmsg, const void* g1_96, const void* g2_192, const void* h0_96, const void* h_96, const void* w_192,
+                              const void* A_96, const void* x_32, const void* r_32, const void* m_32, const void* rho_32, const void* all_ok) {
+    if (!g1_96 || !g2_192 || !h0_96 || !w_192 || !all_ok || (n && (!A_96 || !x_32 || !r_32 || !rho_32)) || (nmsg && (!h_96 || (n && !m_32)))) return C12381_E_ARG;
+    return n + nmsg + 2 > MSM_MAX_TERMS ? C12381_E_ARG : 0;          // split the batch: one bucket product per call
+}
 int c12381_bbs_plus_verify_aggregate_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g1_96, const uint8_t* g2_192, const uint8_t* h0_96,
                                          const uint8_t* h_96, const uint8_t* w_192, const uint8_t* A_96, const uint8_t* x_32, const uint8_t* r_32,
                                          const uint8_t* m_32, const uint8_t* rho_32, uint8_t* all_ok) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1_96 || !g2_192 || !h0_96 || !w_192 || !all_ok || (n && (!A_96 || !x_32 || !r_32 || !rho_32)) || (nmsg && (!h_96 || (n && !m_32)))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_aggregate_args(n, nmsg, g1_96, g2_192, h0_96, h_96, w_192, A_96, x_32, r_32, m_32, rho_32, all_ok))) return rc;
     const size_t terms = n + nmsg + 2;
-    if (terms > MSM_MAX_TERMS) return C12381_E_ARG;            // split the batch: one bucket product per call
     if (n == 0) { HIPCK(c, hipMemsetAsync(all_ok, 1, 1, c->stream)); return 0; }
     HIPCK(c, hipMemsetAsync(all_ok, 0, 1, c->stream));
     if ((rc = lines_table(c, c12381_ctx::WS_FQ_W, w_192, 1))) return rc;
@@ -1723,39 +1644,29 @@ int c12381_bbs_plus_verify_aggregate_dev(c12381_ctx* c, size_t n, size_t nmsg, c
 int c12381_bbs_plus_verify_aggregate(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g1_96, const uint8_t* g2_192, const uint8_t* h0_96,
                                      const uint8_t* h_96, const uint8_t* w_192, const uint8_t* A_96, const uint8_t* x_32, const uint8_t* r_32,
                                      const uint8_t* m_32, const uint8_t* rho_32, int* all_ok) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1_96 || !g2_192 || !h0_96 || !w_192 || !all_ok || (n && (!A_96 || !x_32 || !r_32 || !rho_32)) || (nmsg && (!h_96 || (n && !m_32)))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_aggregate_args(n, nmsg, g1_96, g2_192, h0_96, h_96, w_192, A_96, x_32, r_32, m_32, rho_32, all_ok))) return rc;
     *all_ok = 0;
     if (n == 0) { *all_ok = 1; return 0; }
-    const size_t o_g1 = 0, o_g2 = 96, o_h0 = 288, o_w = 384, o_h = 576, o_A = round_up(o_h + 96 * nmsg, 256), o_x = o_A + 96 * n,
-                 o_r = o_x + 32 * n, o_rho = o_r + 32 * n, o_m = o_rho + 32 * n, o_ok = round_up(o_m + 32 * n * nmsg, 256), bytes = o_ok + 256;
-    if ((rc = ensure(c, c12381_ctx::WS_BBS_IN, bytes))) return rc;
-    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS_IN];
-    HIPCK(c, hipMemcpyAsync(d + o_g1, g1_96, 96, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_g2, g2_192, 192, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_h0, h0_96, 96, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_w, w_192, 192, hipMemcpyHostToDevice, c->stream));
-    if (nmsg) HIPCK(c, hipMemcpyAsync(d + o_h, h_96, 96 * nmsg, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_A, A_96, 96 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_x, x_32, 32 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_r, r_32, 32 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_rho, rho_32, 32 * n, hipMemcpyHostToDevice, c->stream));
-    if (nmsg) HIPCK(c, hipMemcpyAsync(d + o_m, m_32, 32 * n * nmsg, hipMemcpyHostToDevice, c->stream));
-    if ((rc = c12381_bbs_plus_verify_aggregate_dev(c, n, nmsg, d + o_g1, d + o_g2, d + o_h0, d + o_h, d + o_w, d + o_A, d + o_x, d + o_r, d + o_m, d + o_rho,
-                                                   d + o_ok))) return rc;
     uint8_t verdict = 0;
-    HIPCK(c, hipMemcpyAsync(&verdict, d + o_ok, 1, hipMemcpyDeviceToHost, c->stream));
-    rc = read_flag(c);                                          // synchronises the stream
+    staging s;
+    if ((rc = stage(c, s, {{g1_96, 96}, {g2_192, 192}, {h0_96, 96}, {h_96, 96 * nmsg}, {w_192, 192}, {A_96, 96 * n}, {x_32, 32 * n}, {r_32, 32 * n},
+                           {m_32, 32 * n * nmsg}, {rho_32, 32 * n}}, {{&verdict, 1}}))) return rc;
+    if ((rc = c12381_bbs_plus_verify_aggregate_dev(c, n, nmsg, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.in[5], s.in[6], s.in[7], s.in[8], s.in[9],
+                                                   s.out[0]))) return rc;
+    rc = unstage(c, s);                                          // synchronises the stream
     *all_ok = (rc == 0 && verdict == 1) ? 1 : 0;
     return rc;
 }
 
 // BBS+ signing for a batch (bbs+.cpp:38-55): A_j = (g1 * h0^r_j * prod_i h_i^m_ij)^(1/(gamma + x_j)).  x_j, r_j are the
 // caller's random scalars (the reference draws them inside sign()); inverse(0) = 0 gives the point at infinity, as there.
+static int bbs_sign_args(size_t nmsg, const void* g1_96, const void* h0_96, const void* h_96, const void* gamma_32, const void* x_32, const void* r_32,
+                         const void* m_32, const void* A_out96) {
+    return (!g1_96 || !h0_96 || !gamma_32 || !x_32 || !r_32 || !A_out96 || (nmsg && (!h_96 || !m_32))) ? C12381_E_ARG : 0;
+}
 int c12381_bbs_plus_sign_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g1_96, const uint8_t* h0_96, const uint8_t* h_96,
                                    const uint8_t* gamma_32, const uint8_t* x_32, const uint8_t* r_32, const uint8_t* m_32, uint8_t* A_out96) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1_96 || !h0_96 || !gamma_32 || !x_32 || !r_32 || !A_out96 || (nmsg && (!h_96 || !m_32))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_sign_args(nmsg, g1_96, h0_96, h_96, gamma_32, x_32, r_32, m_32, A_out96))) return rc;
     if (n == 0) return 0;
     if ((rc = ensure(c, c12381_ctx::WS_BBS_B, 192 * n))) return rc;
     if ((rc = ensure(c, c12381_ctx::WS_BBS_Q, 192 * n))) return rc;
@@ -1769,23 +1680,13 @@ int c12381_bbs_plus_sign_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const u
 }
 int c12381_bbs_plus_sign_batch(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g1_96, const uint8_t* h0_96, const uint8_t* h_96,
                                const uint8_t* gamma_32, const uint8_t* x_32, const uint8_t* r_32, const uint8_t* m_32, uint8_t* A_out96) {
-    int rc = bind(c); if (rc) return rc;
-    if (!g1_96 || !h0_96 || !gamma_32 || !x_32 || !r_32 || !A_out96 || (nmsg && (!h_96 || !m_32))) return C12381_E_ARG;
+    int rc = bind(c); if (rc || (rc = bbs_sign_args(nmsg, g1_96, h0_96, h_96, gamma_32, x_32, r_32, m_32, A_out96))) return rc;
     if (n == 0) return 0;
-    const size_t o_g1 = 0, o_h0 = 96, o_gm = 192, o_h = 256, o_x = round_up(o_h + 96 * nmsg, 256), o_r = o_x + 32 * n, o_m = o_r + 32 * n,
-                 o_A = round_up(o_m + 32 * n * nmsg, 256), bytes = o_A + 96 * n;
-    if ((rc = ensure(c, c12381_ctx::WS_BBS_IN, bytes))) return rc;
-    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS_IN];
-    HIPCK(c, hipMemcpyAsync(d + o_g1, g1_96, 96, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_h0, h0_96, 96, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_gm, gamma_32, 32, hipMemcpyHostToDevice, c->stream));
-    if (nmsg) HIPCK(c, hipMemcpyAsync(d + o_h, h_96, 96 * nmsg, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_x, x_32, 32 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d + o_r, r_32, 32 * n, hipMemcpyHostToDevice, c->stream));
-    if (nmsg) HIPCK(c, hipMemcpyAsync(d + o_m, m_32, 32 * n * nmsg, hipMemcpyHostToDevice, c->stream));
-    if ((rc = c12381_bbs_plus_sign_batch_dev(c, n, nmsg, d + o_g1, d + o_h0, d + o_h, d + o_gm, d + o_x, d + o_r, d + o_m, d + o_A))) return rc;
-    HIPCK(c, hipMemcpyAsync(A_out96, d + o_A, 96 * n, hipMemcpyDeviceToHost, c->stream));
-    return read_flag(c);
+    staging s;
+    if ((rc = stage(c, s, {{g1_96, 96}, {h0_96, 96}, {h_96, 96 * nmsg}, {gamma_32, 32}, {x_32, 32 * n}, {r_32, 32 * n}, {m_32, 32 * n * nmsg}},
+                    {{A_out96, 96 * n}}))) return rc;
+    if ((rc = c12381_bbs_plus_sign_batch_dev(c, n, nmsg, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.in[5], s.in[6], s.out[0]))) return rc;
+    return unstage(c, s);
 }
 
 }  // extern "C"

@@ -1,11 +1,12 @@
-"""GPU test of the C ABI's contract (include/c12381_hip.h): argument errors, empty batches, invalid points reported as
-C12381_E_POINT with an all-0xff output lane while the other lanes stay valid, status collection through c12381_sync
-for the device-pointer entry points, and independence of contexts."""
+"""GPU test of the C ABI's contract (include/c12381_hip.h): argument errors and empty batches of every entry, invalid points
+reported as C12381_E_POINT with an all-0xff output lane while the other lanes stay valid, host forms that compute exactly
+what their _dev twins compute, status collection through c12381_sync for the device-pointer entry points, and independence
+of contexts."""
 import ctypes
 
 import pytest
 
-from util import cat, golden, scalars
+from util import P as P_MOD, cat, golden, prng, scalars
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,215 @@ def ctx():
     c.close()
 
 
+class In(bytes):
+    """an input buffer"""
+
+
+class OptIn(In):
+    """an input buffer the entry also accepts as NULL"""
+
+
+class Out(int):
+    """an output buffer of this many bytes"""
+
+
+class Fmt(int):
+    pass
+
+
+class Op(int):
+    pass
+
+
+class Flags(int):
+    pass
+
+
+class K(int):
+    pass
+
+
+class NH(int):
+    pass
+
+
+def _bad(rec):
+    """the record of one point with its last byte changed: off the curve (test_invalid_points_poison_only_their_lane)"""
+    return rec[:-1] + bytes([rec[-1] ^ 1])
+
+
+def _entries(n, bad=True):
+    """Every host entry of the C ABI with its _dev twin (None: no twin), the arguments after the context, and whether one lane holds an
+    off-curve point (then both forms report C12381_E_POINT).  With `bad`, lane 1 of the per-lane point inputs is off the curve."""
+    g1, g2, gp = golden("g1"), golden("g2"), golden("pairing")
+    lane1 = (lambda recs: recs[0] + _bad(recs[1]) + b"".join(recs[2:])) if bad else b"".join
+    P = [bytes.fromhex(h) for h in g1["points"]]
+    Q = [bytes.fromhex(h) for h in g2["points"]]
+    C1 = [bytes.fromhex(h) for h in g1["compressed"]]
+    C2 = [bytes.fromhex(h) for h in g2["compressed"]]
+    pts = (P * 4)[:n]
+    qts = (Q * 4)[:n]
+    p_n, q_n = lane1(pts), lane1(qts)
+    good_p, good_q = b"".join(pts), b"".join(qts)
+    c1 = b"".join((C1[:1] + C1[24:25] + C1[2:] if bad else C1)[:n])          # compressed lane 1: a rejected encoding
+    c2 = b"".join((C2[:1] + C2[16:17] + C2[2:] if bad else C2)[:n])
+    sc = scalars(301, n)
+    fp = b"".join((prng(302, j) % P_MOD).to_bytes(48, "big") for j in range(n))
+    gt = (cat(gp["gt"]) * 2)[:576 * n]
+    gt2 = (cat(gp["gt"])[576:] * 2)[:576 * n]
+    gen1, gen2 = bytes.fromhex(g1["generator"])[:96], bytes.fromhex(g2["generator"])[:192]
+    k, nmsg, nh, msg_len = 2, 2, 3, 40
+    prod_p = lane1((P * 4)[:n * k])
+    prod_q = b"".join((Q * 4)[:n * k])
+    h96 = b"".join(P[5:5 + nmsg])
+    pub195 = C1[3] + C2[3] + C1[4]
+    sigs = b"".join(C1[5 + j] + scalars(310 + j, 3) for j in range(n))
+    if bad:
+        sigs = sigs[:145] + C1[24] + sigs[145 + 49:]
+    digests = scalars(320, 2 * n)
+    E = [
+        ("fp_op_batch", "fp_op_batch_dev", [Op(0), n, In(fp), In(fp[::-1]), Out(48 * n)], False),
+        ("g1_mul_batch", "g1_mul_batch_dev", [n, In(p_n), In(sc), Out(49 * n), Fmt(49)], bad),
+        ("g1_mul_batch_flags", "g1_mul_batch_flags_dev", [n, In(c1), In(sc), Out(96 * n), Fmt(96), Flags(4)], bad),
+        ("g1_add_batch", None, [n, In(p_n), In(good_p), Out(96 * n), Fmt(96)], bad),
+        ("g1_msm", "g1_msm_dev", [n, In(p_n), In(sc), Out(49), Fmt(49)], bad),
+        ("g1_msm_flags", "g1_msm_flags_dev", [n, In(c1), In(sc), Out(96), Fmt(96), Flags(4)], bad),
+        ("g1_sum", "g1_sum_dev", [n, In(p_n), Out(49), Fmt(49)], bad),
+        ("g1_sum_of_products", "g1_sum_of_products_dev", [n, In(p_n), In(sc), Out(96), Fmt(96)], bad),
+        ("g2_mul_batch", "g2_mul_batch_dev", [n, In(q_n), In(sc), Out(97 * n), Fmt(97)], bad),
+        ("g2_mul_batch_flags", "g2_mul_batch_flags_dev", [n, In(c2), In(sc), Out(192 * n), Fmt(192), Flags(4)], bad),
+        ("g2_msm", "g2_msm_dev", [n, In(q_n), OptIn(sc), Out(97), Fmt(97)], bad),
+        ("g2_add_batch", None, [n, In(q_n), In(good_q), Out(192 * n), Fmt(192)], bad),
+        ("pair_batch", "pair_batch_dev", [n, In(p_n), In(good_q), Out(576 * n)], bad),
+        ("pair_batch_flags", "pair_batch_flags_dev", [n, In(c1), In(c2), Out(576 * n), Flags(4)], bad),
+        ("pair_product_batch", "pair_product_batch_dev", [n, K(k), In(prod_p), In(prod_q), Out(576 * n), Flags(0)], bad),
+        ("pair_eq_batch", "pair_eq_batch_dev", [n, In(p_n), In(good_q), In(good_p), In(good_q), Out(n)], bad),
+        ("g1_decompress_batch", "g1_decompress_batch_dev", [n, In(c1), Out(96 * n), Out(n)], False),
+        ("g2_decompress_batch", "g2_decompress_batch_dev", [n, In(c2), Out(192 * n), Out(n)], False),
+        ("miller_batch", "miller_batch_dev", [n, In(p_n), In(good_q), Out(576 * n)], bad),
+        ("fexp_batch", "fexp_batch_dev", [n, In(gt), Out(576 * n)], False),
+        ("gt_op_batch", "gt_op_batch_dev", [Op(0), n, In(gt), In(gt2), Out(576 * n)], False),
+        ("gt_op_batch", "gt_op_batch_dev", [Op(2), n, In(gt), In(sc), Out(576 * n)], False),
+        ("gt_is_unity_batch", "gt_is_unity_batch_dev", [n, In(gt), Out(n)], False),
+        ("pair_fixed_g2_batch", "pair_fixed_g2_batch_dev", [n, In(p_n), In(Q[0]), Out(576 * n)], bad),
+        ("g1_mul_fixed_batch", "g1_mul_fixed_batch_dev", [n, In(gen1), In(sc), Out(49 * n), Fmt(49)], False),
+        ("g2_mul_fixed_batch", "g2_mul_fixed_batch_dev", [n, In(gen2), In(sc), Out(97 * n), Fmt(97)], False),
+        ("bbs_plus_verify_batch", "bbs_plus_verify_batch_dev",
+         [n, nmsg, In(P[0]), In(Q[0]), In(P[1]), In(h96), In(Q[1]), In(p_n), In(sc), In(sc[::-1]), In(scalars(303, n * nmsg)), Out(n)], bad),
+        ("bbs_plus_verify_aggregate", "bbs_plus_verify_aggregate_dev",
+         [n, nmsg, In(P[0]), In(Q[0]), In(P[1]), In(h96), In(Q[1]), In(p_n), In(sc), In(sc[::-1]), In(scalars(303, n * nmsg)),
+          In(scalars(304, n, 1 << 64)), Out(4)], bad),
+        ("bbs_plus_verify_wire_batch", "bbs_plus_verify_wire_batch_dev",
+         [n, NH(nh), msg_len, In(pub195), In(b"".join(C1[8:8 + nh])), In(C2[4]), In(sigs), In(digests[:msg_len * n]), Out(n)], False),
+        ("bbs_plus_sign_batch", "bbs_plus_sign_batch_dev",
+         [n, nmsg, In(P[0]), In(P[1]), In(h96), In(scalars(305, 1)), In(sc), In(sc[::-1]), In(scalars(303, n * nmsg)), Out(96 * n)], False),
+        ("g1_from_hash_batch", "g1_from_hash_batch_dev", [n, In(digests), Out(96 * n), Fmt(96)], False),
+        ("g1_map_to_point_batch", None, [n, In(fp), Out(96 * n)], False),
+        ("g1_clear_cofactor_batch", None, [n, In(p_n), Out(96 * n)], bad),
+        ("zp_op_batch", "zp_op_batch_dev", [Op(0), n, In(sc), In(sc[::-1]), Out(32 * n)], False),
+        ("zp_op_batch", "zp_op_batch_dev", [Op(4), n, In(sc), OptIn(sc), Out(32 * n)], False),
+        ("zp_from_hash_batch", None, [n, In(digests), Out(32 * n)], False),
+        ("zp_inner_product", "zp_inner_product_dev", [n, In(sc), OptIn(sc[::-1]), Out(32)], False),
+    ]
+    return E
+
+
+def _run_host(ctx, host, args, fill=0):
+    """host form: returns (rc, [output bytes])"""
+    outs, cargs = [], []
+    for a in args:
+        if isinstance(a, Out):
+            outs.append(ctypes.create_string_buffer(bytes([fill]) * (int(a) or 64), int(a) or 64))
+            cargs.append(outs[-1])
+        elif isinstance(a, In):
+            cargs.append(bytes(a) or bytes(64))
+        else:
+            cargs.append(a)
+    rc = getattr(ctx.lib, "c12381_" + host)(ctx.h, *[_arg(a) for a in cargs])
+    return rc, [o.raw for o in outs]
+
+
+def _arg(a):
+    from crypto12381_amd.capi import _p
+    return a if isinstance(a, int) or a is None else _p(a)
+
+
+def _run_dev(ctx, dev, args, fill=0):
+    """_dev form on device copies of the same buffers: returns (return code, status from c12381_sync, [output bytes])"""
+    import torch
+    d = torch.device("cuda", 0)
+    outs, cargs, keep = [], [], []
+    for a in args:
+        if isinstance(a, Out):
+            outs.append(torch.full((int(a) or 64,), fill, dtype=torch.uint8, device=d))
+            cargs.append(outs[-1].data_ptr())
+        elif isinstance(a, In):
+            keep.append(torch.frombuffer(bytearray(bytes(a) or b"\0" * 64), dtype=torch.uint8).to(d))
+            cargs.append(keep[-1].data_ptr())
+        else:
+            cargs.append(a)
+    torch.cuda.synchronize(d)
+    rc = getattr(ctx.lib, "c12381_" + dev)(ctx.h, *[_arg(a) for a in cargs])
+    st = ctx.sync()
+    return rc, st, [bytes(o.cpu().numpy()) for o in outs]
+
+
+def _arg_error_cases(args):
+    """argument lists that each break one condition of the entry"""
+    for i, a in enumerate(args):
+        if isinstance(a, In) and not isinstance(a, OptIn) or isinstance(a, Out):
+            yield "null arg %d" % i, args[:i] + [None] + args[i + 1:]
+        elif isinstance(a, Fmt):
+            yield "fmt", args[:i] + [Fmt(50)] + args[i + 1:]
+        elif isinstance(a, Op):
+            yield "op 9", args[:i] + [Op(9)] + args[i + 1:]
+            yield "op -1", args[:i] + [Op(-1)] + args[i + 1:]
+        elif isinstance(a, Flags):
+            yield "flags", args[:i] + [Flags(int(a) | 0x100)] + args[i + 1:]
+        elif isinstance(a, K):
+            yield "k 0", args[:i] + [K(0)] + args[i + 1:]
+            yield "k MAX_PROD + 1", args[:i] + [K(4)] + args[i + 1:]
+        elif isinstance(a, NH):
+            yield "nblk > nh", args[:i] + [NH(1)] + args[i + 1:]
+
+
+_FORMS = [(host, dev) for host, dev, _, _ in _entries(3)]
+# host entries whose empty batch has a value: identity bytes of the output format, the zero scalar, a "valid" verdict
+_EMPTY_VALUES = {"g1_msm": bytes(49), "g1_msm_flags": bytes(96), "g1_sum": bytes(49), "g1_sum_of_products": bytes(96), "g2_msm": bytes(97),
+                 "zp_inner_product": bytes(32), "bbs_plus_verify_aggregate": (1).to_bytes(4, "little")}
+
+
+@pytest.mark.parametrize("i", [i for i, (_, dev) in enumerate(_FORMS) if dev])
+def test_host_form_equals_dev_form(ctx, i):
+    """a small golden batch, lane 1 off the curve where the entry takes per-lane points: the same bytes, the same 0xff lane and the same
+    status from both forms — the host form through its return, the _dev form through c12381_sync"""
+    host, dev, args, bad = _entries(3)[i]
+    assert ctx.sync() == 0
+    rc_h, out_h = _run_host(ctx, host, args)
+    rc_d, st, out_d = _run_dev(ctx, dev, args)
+    assert rc_d == 0, (dev, rc_d)
+    assert rc_h == st, (host, rc_h, st)
+    if bad:
+        assert rc_h == E_POINT, host
+    if host == "bbs_plus_verify_aggregate":
+        # the host form's verdict is an int that is 1 only when the call succeeded; the _dev form writes the verdict byte
+        assert out_h[0] == (0 if bad else out_d[0][0]).to_bytes(4, "little")
+        return
+    assert out_h == out_d, host
+    if bad and host in ("g1_mul_batch", "g2_mul_batch", "pair_batch", "pair_eq_batch"):
+        lane = len(out_h[0]) // 3
+        assert out_h[0][lane:2 * lane] == b"\xff" * lane, host
+
+
 def test_argument_errors(ctx):
+    # every host entry and its _dev twin, each argument condition on its own: C12381_E_ARG and nothing launched (the other pointers
+    # are real buffers of the right size, host or device, so a missed check computes garbage instead of faulting)
+    assert ctx.sync() == 0
+    for host, dev, args, _ in _entries(3, bad=False):
+        for what, bad_args in _arg_error_cases(args):
+            assert _run_host(ctx, host, bad_args)[0] == E_ARG, (host, what)
+            if dev:
+                assert _run_dev(ctx, dev, bad_args)[:2] == (E_ARG, 0), (dev, what)
     lib, h = ctx.lib, ctx.h
     buf = ctypes.create_string_buffer(4096)
     n = ctypes.c_size_t(1)
@@ -51,6 +260,12 @@ def test_empty_batches(ctx):
     dec, st = ctx.g1_decompress(b"")
     assert dec == b"" and st == b""
     assert ctx.g1_mul_fixed(bytes.fromhex(golden("g1")["generator"]), b"", 49) == b""
+    # every host entry: 0 without touching the stream and the outputs, or the value of the empty batch
+    for host, _, args, _ in _entries(0, bad=False):
+        rc, outs = _run_host(ctx, host, args, fill=0xab)
+        assert rc == 0, host
+        want = _EMPTY_VALUES.get(host)
+        assert outs[0] == want if want is not None else all(o == b"\xab" * len(o) for o in outs), host
 
 
 def test_invalid_points_poison_only_their_lane(ctx):
