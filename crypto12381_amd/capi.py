@@ -99,6 +99,10 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, ci]
         for name in ("c12381_pair_fixed_g2_batch", "c12381_pair_fixed_g2_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp]
+        for name in ("c12381_pair_product_fixed_g2_batch", "c12381_pair_product_fixed_g2_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, ci, vp, vp, vp, ctypes.c_uint]
+        for name in ("c12381_ps_verify_batch", "c12381_ps_verify_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 7
         for name in ("c12381_bbs_plus_sign_batch", "c12381_bbs_plus_sign_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         for name in ("c12381_g1_decompress_batch_dev", "c12381_g2_decompress_batch_dev"):
@@ -297,6 +301,28 @@ class Context:
 
     def pair_fixed_g2_dev(self, n, g1_ptr, g2_ptr, gt_ptr):
         self._ck(self.lib.c12381_pair_fixed_g2_batch_dev(self.h, n, _p(g1_ptr), _p(g2_ptr), _p(gt_ptr)))
+
+    def pair_product_fixed_g2(self, g1s: bytes, g2s: bytes, k: int, flags: int = 0, strict: bool = True) -> bytes:
+        """g1s: k argument-major arrays of n points, g2s: k points shared by the batch; returns n GT (or, with MILLER_ONLY, Miller) values"""
+        n = len(g1s) // (96 * k) if k > 0 else 0
+        out = ctypes.create_string_buffer(max(576 * n, 1))
+        self._ck(self.lib.c12381_pair_product_fixed_g2_batch(self.h, n, k, _p(g1s), _p(g2s), _p(out), flags), allow_point=not strict)
+        return out.raw[:576 * n]
+
+    def pair_product_fixed_g2_dev(self, n, k, g1s_ptr, g2s_ptr, gt_ptr, flags: int = 0):
+        self._ck(self.lib.c12381_pair_product_fixed_g2_batch_dev(self.h, n, k, _p(g1s_ptr), _p(g2s_ptr), _p(gt_ptr), flags))
+
+    def ps_verify(self, g2: bytes, X2: bytes, Y2: bytes, s1: bytes, s2: bytes, m: bytes, strict: bool = True) -> bytes:
+        """PS: Y2 holds nmsg points, m is message-major (scalar i of signature j at m[32*(i*n + j)]); one byte per signature"""
+        n = len(s1) // 96
+        nmsg = len(Y2) // 192
+        out = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ps_verify_batch(self.h, n, nmsg, _p(g2), _p(X2), _p(Y2) if nmsg else None, _p(s1), _p(s2),
+                                                 _p(m) if nmsg else None, _p(out)), allow_point=not strict)
+        return out.raw[:n]
+
+    def ps_verify_dev(self, n, nmsg, g2, X2, Y2, s1, s2, m, ok):
+        self._ck(self.lib.c12381_ps_verify_batch_dev(self.h, n, nmsg, _p(g2), _p(X2), _p(Y2), _p(s1), _p(s2), _p(m), _p(ok)))
 
     def pair_eq(self, a1: bytes, a2: bytes, b1: bytes, b2: bytes, strict: bool = True) -> bytes:
         n = len(a1) // 96

@@ -70,7 +70,8 @@ struct c12381_ctx {
     // WS_STAGE holds the caller's buffers of a host form (stage / unstage).  No _dev path uses it and no _dev path calls a host form
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
-           WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_G, WS_FQ_GATE, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW, WS_COUNT };
+           WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_G, WS_FQ_GATE, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;
@@ -1057,6 +1058,154 @@ int c12381_pair_fixed_g2_batch(c12381_ctx* c, size_t n, const uint8_t* g1, const
     if ((rc = stage(c, s, {{g1, 96 * n}, {g2_192, 192}}, {{gt, 576 * n}})) || (rc = c12381_pair_fixed_g2_batch_dev(c, n, s.in[0], s.in[1], s.out[0]))) return rc;
     return unstage(c, s);
 }
+// ---------------------------------------------------------------- K-way products against fixed G2 points (k_pairk.hip)
+static_assert(C12381_FIXED_G2_MAX == FIXED_G2_MAX, "public and device bound of k");
+// WS_FQ_K: [gate: FQK_GATE_DWORDS][table 0] ... [table FIXED_G2_MAX - 1], each table a header (fixed_cache_check_kernel protocol) and 69 lines
+constexpr size_t FQK_GATE_DWORDS = 128;
+constexpr size_t FQK_TAB_DWORDS = (FB_HEADER_DWORDS + (size_t)FQ_TABLE_DWORDS + 63) / 64 * 64;
+static_assert(FB_HEADER_DWORDS == HDR_DWORDS, "line tables: header in front of the lines");
+// Tables of the k points q.p[c] (rule: bit 0 need_g2, bit 1 raw records, k_pairk.hip g2_lines_tablek_kernel), each kept until its point
+// or rule changes, and the gate over all k.  Queued on the stream; nothing waits for the host.
+static int lines_tables_k(c12381_ctx* c, int k, const g2_cols& q, int rule, const int32_t*& gate, const int32_t*& lines) {
+    const size_t bytes = (FQK_GATE_DWORDS + (size_t)FIXED_G2_MAX * FQK_TAB_DWORDS) * 4;
+    int rc;
+    if (c->ws_bytes[c12381_ctx::WS_FQ_K] < bytes) {
+        if ((rc = ensure(c, c12381_ctx::WS_FQ_K, bytes))) return rc;
+        HIPCK(c, hipMemsetAsync(c->ws[c12381_ctx::WS_FQ_K], 0, bytes, c->stream));      // no magic yet: first use of every table is a miss
+    }
+    int32_t* base = (int32_t*)c->ws[c12381_ctx::WS_FQ_K];
+    int32_t* tabs = base + FQK_GATE_DWORDS;
+    for (int j = 0; j < k; ++j)
+        hipLaunchKernelGGL(fixed_cache_check_kernel, dim3(1), dim3(64), 0, c->stream, q.p[j], 192, tabs + (size_t)j * FQK_TAB_DWORDS);
+    hipLaunchKernelGGL(g2_lines_tablek_kernel, dim3(1), dim3(BLOCK), 0, c->stream, k, q, tabs, (int)FQK_TAB_DWORDS, rule);
+    hipLaunchKernelGGL(gatek_kernel, dim3(1), dim3(BLOCK), 0, c->stream, base, (const int32_t*)tabs, (int)FQK_TAB_DWORDS, k);
+    HIPCK(c, hipGetLastError());
+    gate = base;
+    lines = tabs + HDR_DWORDS;
+    return 0;
+}
+// The prep kernel (G1 columns -> records, skipped when prep_skip says so) and the K-way queue kernel: GT output (eq = false; gate[HDR_VALID]
+// = 0 poisons every lane) or the boolean (eq = true; runs only when gate[HDR_VALID] != 0).
+static int launch_prodk(c12381_ctx* c, size_t n, int k, const g1_cols& cols, uint32_t neg_mask, const int32_t* gate, const int32_t* lines, uint8_t* out,
+                        bool eq, bool miller_only, const int32_t* prep_skip) {
+    const size_t rec_bytes = round_up((size_t)k * n * FQK_PT_DWORDS * 4, 256);
+    int rc;
+    if ((rc = ensure(c, c12381_ctx::WS_FQK_PTS, rec_bytes + round_up(n * 4, 256)))) return rc;
+    int32_t* pts = (int32_t*)c->ws[c12381_ctx::WS_FQK_PTS];
+    uint32_t* mask = (uint32_t*)((uint8_t*)pts + rec_bytes);
+    hipLaunchKernelGGL(pairk_prep_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, k, cols, neg_mask, pts, mask, prep_skip);
+    HIPCK(c, hipGetLastError());
+    uint4* st; unsigned int *fl, *ct, ep; unsigned blocks;
+    if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
+    const size_t groups = (n + TRI_PER_WAVE - 1) / TRI_PER_WAVE;
+    const size_t ndirect = queue_direct_groups_host(groups, (size_t)blocks * (BLOCK / 64));
+    if (eq)
+        hipLaunchKernelGGL(pair3_prodk_fixed_eq_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines,
+                           (int)FQK_TAB_DWORDS, out, c->d_flag, st, fl, ct, gate, ndirect, pair_spin_limit(), ep);
+    else
+        hipLaunchKernelGGL(pair3_prodk_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines,
+                           (int)FQK_TAB_DWORDS, out, c->d_flag, st, fl, ct, gate, ndirect, miller_only ? 1 : 0, pair_spin_limit(), ep);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+// gt[i] = prod_{j < k} e(g1s[j * n + i], g2s[j]): the k line tables are built with need_g2 = 0 (exact for every point of the twist, infinity
+// included), raw under C12381_F_MILLER_ONLY (the Miller value itself is the output).
+static int pair_product_fixed_args(int k, const void* g1s, const void* g2s, const void* gt, unsigned flags) {
+    return (!g1s || !g2s || !gt || k < 1 || k > C12381_FIXED_G2_MAX || (flags & ~(unsigned)C12381_F_MILLER_ONLY)) ? C12381_E_ARG : 0;
+}
+int c12381_pair_product_fixed_g2_batch_dev(c12381_ctx* c, size_t n, int k, const uint8_t* g1s, const uint8_t* g2s, uint8_t* gt, unsigned flags) {
+    int rc = bind(c); if (rc || (rc = pair_product_fixed_args(k, g1s, g2s, gt, flags))) return rc;
+    if (n == 0) return 0;
+    const bool miller_only = (flags & C12381_F_MILLER_ONLY) != 0;
+    g1_cols cols = {};
+    g2_cols q = {};
+    for (int j = 0; j < k; ++j) { cols.p[j] = g1s + (size_t)96 * n * j; q.p[j] = g2s + (size_t)192 * j; }
+    const int32_t *gate, *lines;
+    if ((rc = lines_tables_k(c, k, q, miller_only ? 2 : 0, gate, lines))) return rc;
+    timed tm(c, 3);
+    return launch_prodk(c, n, k, cols, 0u, gate, lines, gt, false, miller_only, nullptr);
+}
+int c12381_pair_product_fixed_g2_batch(c12381_ctx* c, size_t n, int k, const uint8_t* g1s, const uint8_t* g2s, uint8_t* gt, unsigned flags) {
+    int rc = bind(c); if (rc || (rc = pair_product_fixed_args(k, g1s, g2s, gt, flags))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{g1s, 96 * n * (size_t)k}, {g2s, 192 * (size_t)k}}, {{gt, 576 * n}}))) return rc;
+    if ((rc = c12381_pair_product_fixed_g2_batch_dev(c, n, k, s.in[0], s.in[1], s.out[0], flags))) return rc;
+    return unstage(c, s);
+}
+
+// ---------------------------------------------------------------- PS batch verification
+// ok[j] = [ e(s1_j, X2 + sum_i m[i*n + j] Y2_i) == e(s2_j, g2) ]: the PS verification of the reference's examples/ps/src/ps.cpp:84-99
+// (nmsg = 1: :26-33), evaluated as liner_pair.hpp:336-350 (two Miller values, conjugate, multiply, one final exponentiation, is_unity).
+// Fast route — g2, X2 and every Y2_i elements of G2 other than infinity, nmsg + 2 <= C12381_FIXED_G2_MAX: the argument of the BBS+ path
+// (bilinearity in the G2 argument holds for every curve point s1, and the cofactor part of a GLV multiple m_i s1 pairs to 1 against G2)
+// turns the equation into  e(-s2, g2) * e(s1, X2) * prod_i e(m_i s1, Y2_i) == 1,  ONE K = nmsg + 2 way product over line tables.
+// Generic route — anything else: W_j = X2 + sum_i m_ij Y2_i by the G2 multiplication and addition kernels, then the pair_eq kernels.
+// The gate over the K tables picks the route on the device: every kernel of both routes is enqueued and the other route's return at once.
+static int ps_verify_args(size_t nmsg, const void* g2, const void* X2, const void* Y2, const void* s1, const void* s2, const void* m, const void* ok) {
+    return (!g2 || !X2 || !s1 || !s2 || !ok || (nmsg && (!Y2 || !m))) ? C12381_E_ARG : 0;
+}
+int c12381_ps_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                               const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok) {
+    int rc = bind(c); if (rc || (rc = ps_verify_args(nmsg, g2_192, X2_192, Y2_192, s1_96, s2_96, m_32, ok))) return rc;
+    if (n == 0) return 0;
+    const bool fast = nmsg + 2 <= (size_t)C12381_FIXED_G2_MAX;
+    const int k = (int)nmsg + 2;
+    const int32_t *gate_generic = nullptr, *gate_fast = nullptr, *lines = nullptr;
+    if (fast) {
+        g2_cols q = {};
+        q.p[0] = g2_192; q.p[1] = X2_192;
+        for (size_t i = 0; i < nmsg; ++i) q.p[2 + i] = Y2_192 + 192 * i;
+        const int32_t* gate;
+        if ((rc = lines_tables_k(c, k, q, 1, gate, lines))) return rc;
+        gate_generic = gate;                  // generic kernels: skip when every table is valid
+        gate_fast = gate + GATE_OTHER;        // fast-route kernels with a skip pointer: skip when one is not
+    }
+    // generic route: W = X2 + sum_i m_i Y2_i (WS_BBS_Q), each product in WS_BBS_B
+    if ((rc = ensure(c, c12381_ctx::WS_BBS_Q, 192 * n))) return rc;
+    uint8_t* d_w = (uint8_t*)c->ws[c12381_ctx::WS_BBS_Q];
+    if (nmsg == 0) {
+        hipLaunchKernelGGL(g2_bcast_kernel, dim3(grid_for(192 * n)), dim3(BLOCK), 0, c->stream, n, X2_192, d_w, gate_generic);
+        HIPCK(c, hipGetLastError());
+    } else {
+        if ((rc = ensure(c, c12381_ctx::WS_BBS_B, 192 * n))) return rc;
+        uint8_t* d_b = (uint8_t*)c->ws[c12381_ctx::WS_BBS_B];
+        for (size_t i = 0; i < nmsg; ++i) {
+            if ((rc = g2_mul_dev_strided(c, n, Y2_192 + 192 * i, 0, m_32 + 32 * n * i, d_b, 192, gate_generic))) return rc;
+            hipLaunchKernelGGL(g2_add_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, i == 0 ? X2_192 : (const uint8_t*)d_w, (size_t)(i == 0 ? 0 : 192),
+                               (const uint8_t*)d_b, d_w, 192, c->d_flag, gate_generic);
+            HIPCK(c, hipGetLastError());
+        }
+    }
+    if (fast) {
+        // fast route: the columns -s2 (against g2), s1 (X2), m_i s1 (Y2_i); m_i s1 by the generic G1 multiplication into WS_PROJ, then affine
+        g1_cols cols = {};
+        cols.p[0] = s2_96; cols.p[1] = s1_96;
+        if (nmsg) {
+            const size_t stride = round_up(nmsg * n, 64);
+            for (size_t i = 0; i < nmsg; ++i)
+                if ((rc = g1_mul_to_proj(c, n, s1_96, m_32 + 32 * n * i, stride, 96, i * n, gate_fast))) return rc;
+            if ((rc = ensure(c, c12381_ctx::WS_FQK_G1, 96 * nmsg * n))) return rc;
+            uint8_t* d_m = (uint8_t*)c->ws[c12381_ctx::WS_FQK_G1];
+            if ((rc = g1_finish(c, nmsg * n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, d_m, 96))) return rc;
+            for (size_t i = 0; i < nmsg; ++i) cols.p[2 + i] = d_m + 96 * n * i;
+        }
+        timed tm(c, 4);
+        if ((rc = launch_prodk(c, n, k, cols, 1u, gate_generic, lines, ok, true, false, gate_fast))) return rc;
+    }
+    timed tm(c, 4);
+    return launch_pair_eq(c, n, s1_96, d_w, s2_96, g2_192, (size_t)0, ok, gate_generic);
+}
+int c12381_ps_verify_batch(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                           const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok) {
+    int rc = bind(c); if (rc || (rc = ps_verify_args(nmsg, g2_192, X2_192, Y2_192, s1_96, s2_96, m_32, ok))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{g2_192, 192}, {X2_192, 192}, {Y2_192, 192 * nmsg}, {s1_96, 96 * n}, {s2_96, 96 * n}, {m_32, 32 * n * nmsg}}, {{ok, n}}))) return rc;
+    if ((rc = c12381_ps_verify_batch_dev(c, n, nmsg, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.in[5], s.out[0]))) return rc;
+    return unstage(c, s);
+}
+
 static int pair_eq_args(const void* a1, const void* a2, const void* b1, const void* b2, const void* ok) { return (!a1 || !a2 || !b1 || !b2 || !ok) ? C12381_E_ARG : 0; }
 int c12381_pair_eq_batch_dev(c12381_ctx* c, size_t n, const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, uint8_t* ok) {
     int rc = bind(c); if (rc || (rc = pair_eq_args(a1, a2, b1, b2, ok))) return rc;

@@ -4,6 +4,7 @@
 //   k_g2h.hip    G2 scalar multiplication with two lanes per point (half an Fp2 element per lane)
 //   k_pair3.hip  three-lanes-per-pairing Miller loop + final exponentiation
 //   k_hash_zp.hip  hash-to-G1 and the scalar-field (Zp) helpers
+//   k_pairk.hip  K-way pairing products against fixed G2 points (line tables, prep, work-queue kernels)
 //   k_fixed.hip  fixed-base tables and their evaluation (public-parameter columns of BBS+)
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
@@ -83,6 +84,16 @@ __global__ void __launch_bounds__(BLOCK, 2) g2_lines_table_kernel(const uint8_t*
 __global__ void __launch_bounds__(BLOCK, 2) gate_and_kernel(int32_t* gate, const int32_t* a, const int32_t* b);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_prod_fixed_queue_kernel(size_t n, const uint8_t* a96, const uint8_t* c96, const int32_t* tabw, const int32_t* tabg, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* run_if, int spin_limit, unsigned int epoch);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_fixed_queue_kernel(size_t n, const uint8_t* g1_96, const int32_t* buf, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch);
+// k_pairk.hip: K-way products of pairings against fixed G2 points (C12381_FIXED_G2_MAX = FIXED_G2_MAX); the point columns travel by value
+constexpr int FIXED_G2_MAX = 8;
+struct g1_cols { const uint8_t* p[FIXED_G2_MAX]; };
+struct g2_cols { const uint8_t* p[FIXED_G2_MAX]; };
+__global__ void __launch_bounds__(BLOCK, 2) g2_lines_tablek_kernel(int k, g2_cols q, int32_t* tabs, int tab_stride, int rule);
+__global__ void __launch_bounds__(BLOCK, 2) gatek_kernel(int32_t* gate, const int32_t* tabs, int tab_stride, int k);
+__global__ void __launch_bounds__(BLOCK, 2) pairk_prep_kernel(size_t n, int k, g1_cols cols, uint32_t neg_mask, int32_t* pts, uint32_t* mask, const int32_t* skip_if);
+__global__ void __launch_bounds__(BLOCK, 2) g2_bcast_kernel(size_t n, const uint8_t* src, uint8_t* dst, const int32_t* skip_if);
+__global__ void __launch_bounds__(BLOCK, 2) pair3_prodk_fixed_queue_kernel(size_t n, int k, const int32_t* pts, const uint32_t* mask, const int32_t* tabs, int tab_stride, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* gate, size_t ndirect, int miller_only, int spin_limit, unsigned int epoch);
+__global__ void __launch_bounds__(BLOCK, 2) pair3_prodk_fixed_eq_queue_kernel(size_t n, int k, const int32_t* pts, const uint32_t* mask, const int32_t* tabs, int tab_stride, uint8_t* ok, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* run_if, size_t ndirect, int spin_limit, unsigned int epoch);
 __global__ void __launch_bounds__(BLOCK, 2) miller3_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) gt3_op_kernel(int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, uint4* pow_tab);
 __global__ void __launch_bounds__(BLOCK, 2) gt3_pow_queue_kernel(size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, int* bad_flag, uint4* pow_tab, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit);

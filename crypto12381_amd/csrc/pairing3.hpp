@@ -1271,6 +1271,67 @@ C12381_HDN void miller3_range2_fixed(fp4& F, const fp& px1_, const fp& py1_, boo
     }
 }
 
+// iterations hi .. lo of the joint loop of K pairs (K <= FIXED_G2_MAX, kernels.hpp) whose G2 arguments are all fixed: one squaring per iteration, then for
+// each column c the doubling line of table c and, where N3 and N1 differ, its addition line.  Table c starts at tabs + c * tab_stride
+// (69 lines and the format word); a product of line factors does not depend on their order, so the value is exactly the
+// product of the K single-table loops (miller3_range_fixed); `tabs` points at the lines of table 0.  The G1 arguments are not held in registers: column c of this lane is one
+// record at pts + c * col_stride (FQK_PT_DWORDS: px, py in Montgomery limbs), written once by the prep kernel (k_pairk.hip), and a lane
+// loads only the coordinate its role multiplies (py for role 0, px for roles 1 and 2) before the column's lines.  Bit c of skip_mask
+// marks a G1 argument at infinity or off the curve.
+constexpr int FQK_PT_DWORDS = 32;                    // px (14) | pad (2) | py (14) | pad (2): each coordinate 16-byte aligned
+C12381_HD void fqk_load_coord(fp& v, const int32_t* src) {
+    int32_t w[16];
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __attribute__((address_space(1))) q4* s = (const __attribute__((address_space(1))) q4*)(const void*)src;
+#else
+    const q4* s = reinterpret_cast<const q4*>(src);
+#endif
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { q4 t = s[i]; w[4 * i] = t.v[0]; w[4 * i + 1] = t.v[1]; w[4 * i + 2] = t.v[2]; w[4 * i + 3] = t.v[3]; }
+#pragma unroll
+    for (int i = 0; i < NL; ++i) v.l[i] = w[i];
+    C12381_BOUNDS(v.lb = 268435456.0 + 8.0; v.vb = 2.0; check_actual(v, "fqk_load_coord");)
+}
+C12381_HD void fqk_store_pt(int32_t* dst, const fp& x, const fp& y) {
+    int32_t w[FQK_PT_DWORDS];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) { w[i] = x.l[i]; w[16 + i] = y.l[i]; }
+    w[NL] = w[NL + 1] = w[16 + NL] = w[16 + NL + 1] = 0;
+    q4* d = reinterpret_cast<q4*>(dst);
+#pragma unroll
+    for (int i = 0; i < FQK_PT_DWORDS / 4; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; d[i] = t; }
+}
+C12381_HDN void miller3_rangek_fixed(fp4& F, const int32_t* pts, size_t col_stride, uint32_t skip_mask, int K, const int32_t* tabs, int tab_stride,
+                                     int hi, int lo, const tri& t_) {
+    constexpr unsigned __int128 N1 = (unsigned __int128)BLS_X;
+    constexpr unsigned __int128 N3 = N1 * 3;
+    int k = 0;
+    tabs = wave_uniform(tabs);
+    K = wave_uniform(K); tab_stride = wave_uniform(tab_stride);
+    hi = wave_uniform(hi); lo = wave_uniform(lo);
+    const tri& t = *wave_uniform(&t_);
+    const int32_t* own = pts + (t.role == 0 ? 16 : 0);
+#pragma unroll 1
+    for (int j = 64; j > hi; --j) k += 1 + ((((N3 >> j) & 1) != ((N1 >> j) & 1)) ? 1 : 0);
+#pragma unroll 1
+    for (int i = hi; i >= lo; --i) {
+        C12381_FAIR_SHARE(i, F);
+        f12t_sqr_h(F, t);
+        const bool add = ((N3 >> i) & 1) != ((N1 >> i) & 1);        // wave-uniform: addition step of this iteration
+#pragma unroll 1
+        for (int c = 0; c < K; ++c) {
+            const int32_t* tab = wave_uniform(tabs + (size_t)c * tab_stride);
+            const bool norm = wave_uniform((int)tab[FQ_FMT_WORD]) != 0;
+            const bool skip = ((skip_mask >> c) & 1u) != 0;
+            fp ps;
+            fqk_load_coord(ps, own + (size_t)c * col_stride);
+            miller3_fixed_line(F, tab, norm, k, ps, ps, skip, t);
+            if (add) miller3_fixed_line(F, tab, norm, k + 1, ps, ps, skip, t);
+        }
+        k += add ? 2 : 1;
+    }
+}
+
 // f = conj(Miller_{|x|}(Q, P)) on a triple.  Returns this lane's coefficient.
 C12381_HDN void miller3_loop(fp4& F, const fp& px, const fp& py, bool p_inf, const fp2& qx, const fp2& qy, bool q_inf, const tri& t) {
     g2p Q;

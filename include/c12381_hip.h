@@ -238,6 +238,29 @@ int c12381_gt_is_unity_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* a576,
  * c12381_pair_batch on n copies of Q for every Q (infinity included); Q not on the twist poisons all outputs. */
 int c12381_pair_fixed_g2_batch(c12381_ctx* ctx, size_t n, const uint8_t* g1_96, const uint8_t* g2_192, uint8_t* gt576);
 int c12381_pair_fixed_g2_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* g1_96, const uint8_t* g2_192, uint8_t* gt576);
+/* gt[i] = prod_{j < k} e(g1s[j*n + i], g2s[j]) for 1 <= k <= C12381_FIXED_G2_MAX: the product of pairings whose G2 arguments are
+ * public points shared by the batch — the shape of every verification equation in the reference's examples (PS
+ * examples/ps/src/ps.cpp:32, :98, :145; BBS+ examples/bbs-plus/src/bbs+.cpp:72; bbs04 R3 examples/bbs04/src/bbs.cpp:45, :73).  g1s is
+ * argument-major as in c12381_pair_product_batch, g2s holds k points.  Each point gets a line table, kept until the point changes,
+ * and the k Miller loops share their squarings.  For k <= 3 bytes and status equal c12381_pair_product_batch with every G2 point
+ * repeated n times; for any k the result is the GT product of the k c12381_pair_fixed_g2_batch values.  flags: C12381_F_MILLER_ONLY
+ * (the product of the k c12381_miller_batch values).  A G1 point off the curve poisons its lane, a G2 point off the twist every lane
+ * (C12381_E_POINT). */
+#define C12381_FIXED_G2_MAX 8
+int c12381_pair_product_fixed_g2_batch(c12381_ctx* ctx, size_t n, int k, const uint8_t* g1s_96, const uint8_t* g2s_192, uint8_t* gt576, unsigned flags);
+int c12381_pair_product_fixed_g2_batch_dev(c12381_ctx* ctx, size_t n, int k, const uint8_t* g1s_96, const uint8_t* g2s_192, uint8_t* gt576, unsigned flags);
+
+/* PS batch verification: ok[j] = [ e(s1_j, X2 + sum_i m[i*n + j] * Y2_i) == e(s2_j, g2) ], the check of the reference's
+ * examples/ps/src/ps.cpp:84-99 (one message: :26-33; example_ps.cpp:39), evaluated as liner_pair.hpp:336-350 (two Miller values,
+ * conjugate, multiply, one final exponentiation, is_unity).  Y2 holds nmsg points, m is message-major; nmsg = 0 is allowed (Y2 and m
+ * may then be null); scalars are used as given.  ok[j] = 1 / 0, 0xff for a signature with a point off the curve; a public point off
+ * the twist poisons every lane (C12381_E_POINT).  When g2, X2 and every Y2_i are elements of G2 other than infinity and
+ * nmsg + 2 <= C12381_FIXED_G2_MAX, one (nmsg + 2)-way product over line tables serves the batch; otherwise W_j = X2 + sum m_ij Y2_i
+ * is formed as PAIR_G2mul does and paired; the device picks the route. */
+int c12381_ps_verify_batch(c12381_ctx* ctx, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                           const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok);
+int c12381_ps_verify_batch_dev(c12381_ctx* ctx, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                               const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok);
 
 /* one base for the whole batch ------------------------------------------------------------------ */
 /* out[i] = scalars[i] * base: g^x with one g — the reference's most common call shape (the cached default generators,
