@@ -5,15 +5,21 @@ Metric (BASELINE.json): G1 scalar-muls/s per MI355X on a batch of 2^20 random (p
 configs[1] — bit-exact vs the CPU path.  A "step" is one pass of the hot path (c12381_g1_mul_batch_dev: scalar-mul
 kernel + inversion/encode kernel) over one batch whose inputs are already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run (no --full) does only what the headline needs: it makes the inputs, runs W warm-up and K timed steps of the G1 leg and
+prints the line below with the headline's fields alone (`roofline` from the same steps' launch times, without an in-run clock).  With
+--dump-outputs it writes the same arrays as a --full run: the other legs then run once each for their outputs, and none of their
+numbers is reported.  Everything else described here — the other legs' numbers, the strong-scaled legs, the
+streamed legs, parity against the CPU oracle, the CPU baselines, the in-run clock probe and --all-configs — runs with --full, as before.
 
 Started plainly with --gpus N > 1 (no WORLD_SIZE in the environment) the script becomes the launcher: before anything touches the
 GPU it starts N ranks of itself under torch.distributed.run on 127.0.0.1, relays their output and exits with their status.  Under a
 launcher WORLD_SIZE must equal --gpus, otherwise the run stops (a silent 1-GPU run of an "N-GPU" command is the failure to avoid).
 
 Rank 0 prints ONE JSON line, kept short enough for a log tail (floats rounded to 6 significant digits, explanations once under
-`notes`, the pairing leg — the second half of BASELINE's metric — LAST).  Besides the headline it carries one object per remaining BASELINE config, each with its
+`notes`, the pairing leg — the second half of BASELINE's metric — LAST).  With --full, besides the headline it carries one object per remaining BASELINE config, each with its
 own timing, parity against the CPU oracle, `roofline` / `hbm_roofline` and (N = 1) `cpu_baseline`:
     pairing   configs[2]  2^16 ate pairings (the WHOLE batch is compared with the oracle at N = 1)
     g2_mul / miller / fexp   the G2 scalar multiplication, the Miller loop and the final exponentiation alone
@@ -225,6 +231,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other legs, streamed and sharded legs, parity vs the CPU oracle, CPU baselines, clock probe")
     ap.add_argument("--log2-batch", type=int, default=20)
     ap.add_argument("--log2-pairings", type=int, default=16)
     ap.add_argument("--pairings", type=int, default=0, help="exact pairing batch size (overrides --log2-pairings; experiments only)")
@@ -250,6 +258,8 @@ def main():
         raise SystemExit("bench.py: --gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.all_configs and not args.full:
+        raise SystemExit("bench.py: --all-configs times further configurations: it needs --full")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             # nothing in this process has touched the GPU yet (importing torch does not): become the launcher of N fresh ranks
@@ -262,17 +272,19 @@ def main():
                          % (args.gpus, world, world, args.gpus))
     # RCCL ("nccl") over xGMI on the GPU node; C12381_BENCH_BACKEND=gloo lets the N>1 path be rehearsed on one GPU
     backend = os.environ.get("C12381_BENCH_BACKEND", "nccl")
-    # CPU baseline workers: one PROCESS per host core, forked here — before anything in this process touches the GPU — so that no worker
+    # CPU baseline workers (--full): one PROCESS per host core, forked here — before anything in this process touches the GPU — so that no worker
     # ever holds a HIP context.  Processes, not threads: MIRACL's constant-time moves advance a function-level static on every call
     # (oracle/pool.py), which costs the reference's G1 / G2 / final-exponentiation paths half their rate across threads of one process.
     if torch.cuda.device_count() == 0:                        # counting devices does not initialise the GPU; nothing is forked on a box without one
         raise SystemExit("bench.py needs a HIP device: the product path has no CPU fallback")
-    from oracle.bindings import Oracle, have_reference
-    from oracle.pool import OraclePool, OracleThreads
-    kind = "reference" if have_reference() else "port"        # the compiled reference when it travelled with the snapshot, else the C port
-    cores = min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 16)   # the GPU box gives one GPU a 16-CPU share
-    do_cpu = world == 1 and not args.no_cpu_baseline
-    cpu_pool = OraclePool(kind, cores) if do_cpu else None
+    do_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    cpu_pool = None
+    if args.full:                                             # a plain run touches no oracle: parity and baselines are --full legs
+        from oracle.bindings import Oracle, have_reference
+        from oracle.pool import OraclePool, OracleThreads
+        kind = "reference" if have_reference() else "port"    # the compiled reference when it travelled with the snapshot, else the C port
+        cores = min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 16)   # one GPU's share: 16 CPUs
+        cpu_pool = OraclePool(kind, cores) if do_cpu else None
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device: the product path has no CPU fallback")
     ndev = torch.cuda.device_count()
@@ -341,7 +353,10 @@ def main():
             el = float(t.item())
         return el
 
-    probe = None if args.no_clock_probe else ClockProbe(dev_index, dev)
+    probe = ClockProbe(dev_index, dev) if args.full and not args.no_clock_probe else None
+    # --dump-outputs without --full: the other legs still run, for the arrays they dump and nothing else — their first call and ONE step each
+    # (every leg is deterministic: the arrays are those of a --full run), no streamed or strong-scaled leg, none of their numbers reported
+    legs = args.full or args.dump_outputs is not None
     clocks = {}                                       # kernel name -> GHz held inside it in THIS run (rank 0 reports them)
 
     xcd_clocks = {}                                   # kernel name -> (min, max) over the XCDs' samplers
@@ -405,7 +420,7 @@ def main():
 
     # ================================================================== configs[2]: pairings
     pair = None
-    if not args.no_pairing:
+    if legs and not args.no_pairing:
         npair = args.pairings if args.pairings > 0 else (1 << args.log2_pairings)
         t_sc = torch.from_numpy(reduced_scalars(3000 + rank, npair)).to(dev)
         gen2 = dev_bytes(G2_GEN, dev)
@@ -416,18 +431,19 @@ def main():
         ctx.g2_mul_fixed_dev(npair, gen2.data_ptr(), t_sc.data_ptr(), q2.data_ptr(), 192)   # Q_i = G2^{t_i} (untimed)
         if ctx.sync() != 0:
             raise SystemExit("bench: the fixed-base G2 multiplication reported an invalid point")
-        for _ in range(max(1, args.warmup)):
+        psteps = max(1, args.steps) if args.full else 1
+        for _ in range(max(1, args.warmup) if args.full else 1):
             ctx.pair_dev(npair, p1.data_ptr(), q2.data_ptr(), gt.data_ptr())
         torch.cuda.synchronize(dev)
         ctx.profile(True)
-        pel = timed(lambda: ctx.pair_dev(npair, p1.data_ptr(), q2.data_ptr(), gt.data_ptr()), max(1, args.steps), 0)
+        pel = timed(lambda: ctx.pair_dev(npair, p1.data_ptr(), q2.data_ptr(), gt.data_ptr()), psteps, 0)
         pk_ms, pk_launches = ctx.profile_read(3)
         ctx.profile(False)
         if ctx.sync() != 0:
             raise SystemExit("bench: invalid input reported by the pairing kernel")
         keep("pairing", gt, 576, npair, 1 << 11, 12)
         probe_clock("pair", lambda: ctx.pair_dev(npair, p1.data_ptr(), q2.data_ptr(), gt.data_ptr()))
-        pair = {"npair": npair, "steps": max(1, args.steps), "elapsed": pel, "kernel_ms": pk_ms, "launches": pk_launches,
+        pair = {"npair": npair, "steps": psteps, "elapsed": pel, "kernel_ms": pk_ms, "launches": pk_launches,
                 "p1": p1, "q2": q2, "gt": gt}
 
     # ================================================================== the remaining hot-path functions alone: G2 mul, Miller loop, final exponentiation
@@ -435,7 +451,7 @@ def main():
     if pair is not None and not args.no_split:
         npair = pair["npair"]
         ng2 = 1 << args.log2_g2
-        ssteps = min(max(1, args.steps), 5)
+        ssteps = min(max(1, args.steps), 5) if args.full else 1
         g2_sc_h = make_scalars(3500 + rank, ng2)
         g2_sc = torch.from_numpy(g2_sc_h).to(dev)
         reps2 = (ng2 + npair - 1) // npair
@@ -479,7 +495,7 @@ def main():
     # in which the older wavefront of every SIMD has left.  Same inputs, two output buffers, both compared with the serial leg's
     # output (itself checked against the CPU reference below).  The contract's legs above stay serial: their kernel times are launch times.
     streamed = None
-    if not args.no_streamed:
+    if args.full and not args.no_streamed:
         ctx2 = Context(dev_index)
         stream2 = torch.cuda.Stream(device=dev)
         ctx2.set_stream(stream2.cuda_stream)
@@ -521,7 +537,7 @@ def main():
 
     # ================================================================== configs[3]: MSM, n = 2^22 per GPU (weak) and sharded (strong)
     msm = None
-    if not args.no_msm:
+    if legs and not args.no_msm:
         nm = 1 << args.log2_msm
         reps = max(1, nm // n)
 
@@ -546,7 +562,7 @@ def main():
         ms_h = make_scalars(4000 + rank, nm)
         ms_ = torch.from_numpy(ms_h).to(dev)
         mo_ = torch.empty(96, dtype=torch.uint8, device=dev)
-        msteps = min(max(1, args.steps), 5)
+        msteps = min(max(1, args.steps), 5) if args.full else 1
         inputs_ready()                                      # mp_ and ms_ come from torch copies on torch's stream
         ctx.g1_msm_dev(nm, mp_.data_ptr(), ms_.data_ptr(), mo_.data_ptr(), 96)
         torch.cuda.synchronize(dev)
@@ -558,7 +574,7 @@ def main():
         probe_clock("msm_bucket_kernel", lambda: ctx.g1_msm_dev(nm, mp_.data_ptr(), ms_.data_ptr(), mo_.data_ptr(), 96))
         msm = {"n": nm, "steps": msteps, "elapsed": mel, "bucket_ms": bk_ms, "bucket_launches": bk_launches, "out": mo_.cpu().numpy().tobytes(),
                "reps": reps, "scalars": ms_h, "bases": msm_base_h}
-        if world > 1:
+        if world > 1 and args.full:
             # strong scaling: ONE product for the whole job — identical terms on every rank (seed without the rank), each rank takes its shard
             gs_h = make_scalars(4100, nm)
             gb_h = make_scalars(1000, n)                               # the points of rank 0's batch: P_i = G^{s_i}
@@ -613,7 +629,7 @@ def main():
 
     # ================================================================== configs[4]: BBS+ verifications
     bbs = None
-    if not args.no_bbs:
+    if legs and not args.no_bbs:
         nb = 1 << args.log2_bbs
         # public parameters and key as setup(16) / key_gen make them (bbs+.cpp:7-36, examples/bbs-plus/test.cpp:11-14): g1, h0 and SIXTEEN h_i,
         # multiples of the generators; one-block messages use h_1 only, the wire leg decodes all sixteen (pp.h)
@@ -648,7 +664,7 @@ def main():
         def bbs_step(count=nb, A=dA, x=dx, r=dr, m=dm, ok=okb):
             ctx.bbs_plus_verify_dev(count, 1, dpub[0].data_ptr(), dpub[1].data_ptr(), dpub[2].data_ptr(), dpub[3].data_ptr(), dpub[4].data_ptr(),
                                     A.data_ptr(), x.data_ptr(), r.data_ptr(), m.data_ptr(), ok.data_ptr())
-        bsteps = min(max(1, args.steps), 5)
+        bsteps = min(max(1, args.steps), 5) if args.full else 1
         bbs_step()
         torch.cuda.synchronize(dev)
         ctx.profile(True)
@@ -695,7 +711,7 @@ def main():
             raise SystemExit("bench: wire-format BBS+ verdicts differ from the construction (valid signatures / corrupted lanes) — number withheld")
         bbs["wire"] = {"elapsed": wel, "pp": pp195, "h49": h49, "pk": pk97, "sig": sig.cpu().numpy(), "raw": raw_h, "ok": okw_h}
         del sig, draw, okw
-        if world > 1:
+        if world > 1 and args.full:
             gA, gx, gr, gm, gbad = make_sigs(5200, nb)[:5] if rank != 0 else (A_h, xs_h, rs_h, mm_h, bad_lanes)
             lo, hi = shard_bounds(nb, rank, world)
             sA, sx, sr, sm = (torch.from_numpy(np.ascontiguousarray(a[lo:hi])).to(dev) for a in (gA, gx, gr, gm))
@@ -758,15 +774,10 @@ def main():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print("bench.py: %d arrays, %d bytes -> %s" % (len(dumps), total, args.dump_outputs), file=sys.stderr, flush=True)
         dumps.clear()
+    if not args.full:                                 # the legs of a plain run with --dump-outputs ran for their arrays alone
+        pair = split = msm = bbs = None
 
-    # ================================================================== parity and CPU baselines (outside every timed region)
-    # kind: the compiled reference (oracle/_ref) or the C port — said on every parity object, never silent
-    pinned = kind == "reference"
-    orc = Oracle(kind)
-    cpuN = cpu_pool if cpu_pool is not None else OracleThreads(orc, cores)      # `cores` workers: processes with the baseline, threads without
-    if rank == 0 and not pinned:
-        print("bench.py: oracle/_ref/libc12381_ref.so is absent: parity is checked against the C port (parity.pinned = false)", file=sys.stderr, flush=True)
-
+    # ================================================================== parity and CPU baselines (outside every timed region; --full only)
     def cpu_time(fn):
         """CPU legs: a sample shorter than 2 s rides the host's CPU-quota burst and then its throttle — such a sample is run three times and
         the MEDIAN time counts (a longer one once); returns (output, seconds)"""
@@ -777,14 +788,22 @@ def main():
             ts.append(time.perf_counter() - t)
             if ts[0] >= 2.0 or len(ts) >= 3 or not do_cpu:         # parity-only runs (--no-cpu-baseline, N > 1): once
                 return o, float(np.median(ts))
-    pts_h = pts.cpu().numpy().reshape(n, 96)
-    out_h = out.cpu().numpy().reshape(n, 96)
-    # G1: with the CPU baseline the first 2^17 lanes are compared in full, otherwise 64 sampled lanes incl. every edge lane
-    idx = list(range(8)) + [int(x) for x in np.random.Generator(np.random.PCG64(7)).integers(0, n, size=56)]
-    exp = orc.g1_mul(pts_h[idx].tobytes(), sc_h[idx].tobytes(), 96, min(cores, 8))
-    if exp != out_h[idx].tobytes():
-        raise SystemExit("bench: GPU results differ from the CPU oracle — number withheld")
-    g1_checked = len(idx)
+
+    if args.full:
+        # kind: the compiled reference (oracle/_ref) or the C port — said on every parity object, never silent
+        pinned = kind == "reference"
+        orc = Oracle(kind)
+        cpuN = cpu_pool if cpu_pool is not None else OracleThreads(orc, cores)      # `cores` workers: processes with the baseline, threads without
+        if rank == 0 and not pinned:
+            print("bench.py: oracle/_ref/libc12381_ref.so is absent: parity is checked against the C port (parity.pinned = false)", file=sys.stderr, flush=True)
+        pts_h = pts.cpu().numpy().reshape(n, 96)
+        out_h = out.cpu().numpy().reshape(n, 96)
+        # G1: with the CPU baseline the first 2^17 lanes are compared in full, otherwise 64 sampled lanes incl. every edge lane
+        idx = list(range(8)) + [int(x) for x in np.random.Generator(np.random.PCG64(7)).integers(0, n, size=56)]
+        exp = orc.g1_mul(pts_h[idx].tobytes(), sc_h[idx].tobytes(), 96, min(cores, 8))
+        if exp != out_h[idx].tobytes():
+            raise SystemExit("bench: GPU results differ from the CPU oracle — number withheld")
+        g1_checked = len(idx)
 
     def par(head=False, **kw):
         """parity object of a leg; the oracle's kind is named on the headline's (and in notes.cpu_baseline), `pinned` on every one"""
@@ -875,7 +894,8 @@ def main():
             result["cpu_baseline"] = {"value": sample / cpu_s, "unit": "scalar-muls/s", "cores": cores, "workers": "processes", "kind": kind,
                                       "sample": "first %d lanes; all equal" % sample,
                                       "one_thread": 4096 / cpu1_s, "eff_cores": (sample / cpu_s) / (4096 / cpu1_s), "threads_value": nt / cput_s}
-        result["parity"] = par(head=True, checked_lanes=g1_checked)
+        if args.full:
+            result["parity"] = par(head=True, checked_lanes=g1_checked)
 
         def cpu_b(v, unit, sample, one=None, full_keys=False):
             """one = the same routine's rate on ONE thread (its own short sample): eff_cores = what `cores` threads deliver on this box"""
@@ -1064,10 +1084,16 @@ def main():
                         "traffic = FETCH_SIZE x2 + WRITE_SIZE passes (profiles/traffic.json)",
             "issue": "issue_ms = SQ_INSTS_VALU per launch (profiles/issue.json) x 4.06 cycles / 1024 SIMDs / the clock held inside the kernel in THIS "
                      "run (one sampler per XCD, mean; xcd_clock_min_max); ref_mac32_per_inst = reference MAC32 per issued lane-instruction",
-            "bbs_plus": "MAC32 = the pipeline's own op sequence (wire: + decode of A); reference_sequence_gmac32_per_s: the reference's over this time",
-            "cpu_baseline": "%s, %d worker processes (not threads: oracle/pool.py), same inputs; under 2 s: median of 3; eff_cores = value / one_thread (own sample)"
-                            % ("oracle/_ref = the reference's sources compiled here" if pinned else "C port (oracle/_ref absent)", cores),
         }
+        if args.full:
+            result["notes"].update({
+                "bbs_plus": "MAC32 = the pipeline's own op sequence (wire: + decode of A); reference_sequence_gmac32_per_s: the reference's over this time",
+                "cpu_baseline": "%s, %d worker processes (not threads: oracle/pool.py), same inputs; under 2 s: median of 3; eff_cores = value / one_thread (own sample)"
+                                % ("oracle/_ref = the reference's sources compiled here" if pinned else "C port (oracle/_ref absent)", cores),
+            })
+        else:
+            result["notes"]["run"] = ("plain: the headline's steps alone; --full adds the other configs, parity vs the CPU oracle, CPU baselines "
+                                      "and the in-run clock (issue.clock_GHz_in_run)")
         # the pairing leg goes LAST: the second half of BASELINE's metric survives any truncation of the line's head
         if pair is not None:
             avg_s = pair["kernel_ms"] / max(pair["launches"], 1) * 1e-3

@@ -75,6 +75,18 @@ def test_bench_gpus_flag_without_a_gpu():
     assert r.returncode != 0 and "refusing" in r.stderr + r.stdout
 
 
+def test_bench_all_configs_needs_full():
+    """The extra configurations are part of the --full run: asked for in a plain run, bench.py stops before it touches a device."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update({"HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": "", "ROCR_VISIBLE_DEVICES": ""})
+    r = subprocess.run([sys.executable, "bench.py", "--all-configs"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "needs --full" in r.stderr and "HIP device" not in r.stderr, r.stderr[-2000:]
+    r = subprocess.run([sys.executable, "bench.py", "--all-configs", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "needs a HIP device" in r.stderr, r.stderr[-2000:]
+
+
 def test_build_refuses_a_compiler_it_was_not_validated_with(monkeypatch):
     """crypto12381_amd/build.py: 3-4 % of every kernel hang on an LLVM pass gate of one compiler and the wrong-lanes event of round 1 was a build-variant
     effect, so another `hipcc --version` stops the build unless the caller says it will run the every-lane tests; the pass gate is probed."""

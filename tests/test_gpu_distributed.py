@@ -174,7 +174,7 @@ def test_bench_two_ranks_on_one_gpu_dry_run():
     env.pop("C12381_LIB", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29547",
            "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--log2-batch", "14", "--log2-pairings", "10", "--log2-g2", "12", "--log2-msm", "14",
-           "--log2-bbs", "12", "--no-cpu-baseline", "--sampled-parity"]
+           "--log2-bbs", "12", "--no-cpu-baseline", "--sampled-parity", "--full"]
     t0 = time.perf_counter()
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     wall = time.perf_counter() - t0
@@ -201,7 +201,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     small = ["--steps", "1", "--warmup", "1", "--log2-batch", "14", "--log2-pairings", "10", "--log2-g2", "12", "--log2-msm", "14", "--log2-bbs", "12",
-             "--no-cpu-baseline", "--sampled-parity", "--no-clock-probe"]
+             "--no-cpu-baseline", "--sampled-parity", "--no-clock-probe", "--full"]
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + small, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -220,7 +220,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
 
 
 def test_bench_single_gpu_line_with_cpu_baseline_and_streamed_legs():
-    """`python3 bench.py` at N = 1 as the driver runs it (small sizes here): the CPU baseline comes from the process pool that is forked
+    """`python3 bench.py --full` at N = 1 (small sizes here): the CPU baseline comes from the process pool that is forked
     before the GPU is touched (oracle/pool.py), every leg carries its own baseline with a one-thread rate, the streamed legs are present and
     equal to the serial ones (bench.py withholds the line otherwise), `pairing` closes the line and the line fits the driver's log tail."""
     import json
@@ -229,7 +229,8 @@ def test_bench_single_gpu_line_with_cpu_baseline_and_streamed_legs():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    small = ["--steps", "2", "--warmup", "1", "--log2-batch", "14", "--log2-pairings", "12", "--log2-g2", "12", "--log2-msm", "14", "--log2-bbs", "12"]
+    small = ["--steps", "2", "--warmup", "1", "--log2-batch", "14", "--log2-pairings", "12", "--log2-g2", "12", "--log2-msm", "14", "--log2-bbs", "12",
+             "--full"]
     r = subprocess.run([sys.executable, "bench.py"] + small, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -248,3 +249,55 @@ def test_bench_single_gpu_line_with_cpu_baseline_and_streamed_legs():
     assert d["streamed"]["g1_per_s"] > 0 and d["streamed"]["pairings_per_s"] > 0
     assert list(d)[-1] == "pairing"
     assert len(lines[0]) < 8000, "the JSON line outgrew the driver's log tail: %d characters" % len(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path, oracle_port):
+    """`python3 bench.py` without --full (small sizes here): ONE line with the headline's fields and none of the --full legs, at most 30 s
+    spent outside the warm-up and timed steps; with --dump-outputs the same arrays as a --full run, file for file (the G1 leg's also checked
+    against the CPU oracle on edge and sampled lanes: the plain run itself compares nothing)."""
+    import json
+    import subprocess
+    import sys
+    import time
+    import numpy as np
+    from bench import G1_GEN, make_scalars
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    steps, warmup, log2n = 2, 1, 14
+    small = ["--steps", str(steps), "--warmup", str(warmup), "--log2-batch", str(log2n), "--log2-pairings", "10", "--log2-g2", "12",
+             "--log2-msm", "14", "--log2-bbs", "12"]
+
+    def run(*extra):
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable, "bench.py"] + small + list(extra), cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        wall = time.perf_counter() - t0
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0]), wall
+
+    plain_dir, full_dir = tmp_path / "plain", tmp_path / "full"
+    for extra in ((), ("--dump-outputs", str(plain_dir))):
+        d, wall = run(*extra)
+        assert d["metric"].startswith("G1 scalar-muls/s per MI355X") and d["unit"] == "scalar-muls/s" and d["higher_is_better"] is True
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == steps and d["warmup"] == warmup and d["dtype"]
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - (1 << log2n)) < 1e-3 * (1 << log2n)
+        assert d["roofline"]["bound"] == "int-valu" and d["roofline"]["frac"] > 0
+        for leg in ("pairing", "g2_mul", "miller", "fexp", "msm", "bbs_plus", "bbs_plus_wire", "streamed", "cpu_baseline", "parity", "extra_configs"):
+            assert leg not in d, leg
+        if not extra:
+            outside = wall - (steps + warmup) * d["ms_per_step"] / 1e3
+            assert outside < 30, "the plain run spent %.1f s outside its steps" % outside
+    run("--full", "--no-cpu-baseline", "--sampled-parity", "--no-streamed", "--no-clock-probe", "--dump-outputs", str(full_dir))
+    names = sorted(os.listdir(full_dir))
+    assert sorted(os.listdir(plain_dir)) == names and "g1_mul.npy" in names and "bbs_plus_wire.npy" in names
+    for name in names:
+        assert np.array_equal(np.load(plain_dir / name), np.load(full_dir / name)), name
+    got = np.load(plain_dir / "g1_mul.npy")
+    assert got.shape == (1 << log2n, 96)
+    idx = list(range(8)) + [int(x) for x in np.random.Generator(np.random.PCG64(5)).integers(0, 1 << log2n, size=24)]
+    orc = oracle_port
+    base, sc = make_scalars(1000, 1 << log2n)[idx], make_scalars(2000, 1 << log2n)[idx]
+    pts = orc.g1_mul(G1_GEN * len(idx), base.tobytes(), 96, 4)
+    assert orc.g1_mul(pts, sc.tobytes(), 96, 4) == got[idx].astype(np.uint8).tobytes()

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $1; do
   unset C12381_LIB C12381_FQ_RAW
   if [ $v = raw ]; then export C12381_FQ_RAW=1; elif [ $v != base ]; then export C12381_LIB=$ROOT/crypto12381_amd/lib/exp/lib$v.so; fi
-  rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d "$ROOT/$OUT/$v" -o p -- python3 "$ROOT/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-msm --no-pairing --sampled-parity > "$ROOT/$OUT/$v.log" 2>&1
+  rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d "$ROOT/$OUT/$v" -o p -- python3 "$ROOT/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline --no-msm --no-pairing --sampled-parity > "$ROOT/$OUT/$v.log" 2>&1
   echo "variant $v rc=$?"
 done
 cd "$ROOT"

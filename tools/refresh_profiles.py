@@ -35,7 +35,7 @@ stats = F + "/prof/p_kernel_stats.csv"
 if os.path.exists(stats):
     rows = list(csv.DictReader(open(stats)))
     with open("profiles/%s_kernel_stats_bench.csv" % R, "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --sampled-parity  (MI355X, final build of the "
+        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --sampled-parity  (MI355X, final build of the "
                 "round, tools/gpu_pass.sh %s prof; rocPRIM / torch kernel names shortened; bench line of the same run: profiles/%s_bench_under_rocprof.json)\n" % (TAG, R))
         f.write("Name,Calls,TotalDurationNs,AverageNs,MinNs,MaxNs\n")
         for r in rows:
