@@ -121,6 +121,12 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, sz] + [vp] * 6
         for name in ("c12381_bbs_plus_verify_aggregate", "c12381_bbs_plus_verify_aggregate_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 11
+        for name in ("c12381_sha3_512_batch", "c12381_sha3_512_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, vp, vp]
+        for name in ("c12381_bbs04_verify_batch", "c12381_bbs04_verify_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp]
+        for name in ("c12381_bbs04_open_batch", "c12381_bbs04_open_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, vp]
         _lib = lib
     return _lib
 
@@ -461,6 +467,42 @@ class Context:
     def bbs_plus_verify_dev(self, n, nmsg, g1, g2, h0, h, w, A, x, r, m, ok):
         self._ck(self.lib.c12381_bbs_plus_verify_batch_dev(self.h, n, nmsg, _p(g1), _p(g2), _p(h0), _p(h), _p(w), _p(A), _p(x), _p(r),
                                                            _p(m), _p(ok)))
+
+    def sha3_512(self, msgs: bytes, n: int, length: int) -> bytes:
+        """n messages of `length` bytes each, contiguous (length 0 allowed) -> n 64-byte SHA3-512 digests (hash_state's SHA3)"""
+        out = ctypes.create_string_buffer(max(64 * n, 1))
+        self._ck(self.lib.c12381_sha3_512_batch(self.h, n, length, _p(msgs) if length else None, _p(out)))
+        return out.raw[:64 * n]
+
+    def sha3_512_dev(self, n, length, msgs_ptr, out_ptr):
+        self._ck(self.lib.c12381_sha3_512_batch_dev(self.h, n, length, _p(msgs_ptr), _p(out_ptr)))
+
+    def bbs04_verify(self, gpk390: bytes, sigs435: bytes, msgs: bytes, msg_len: int, strict: bool = True) -> bytes:
+        """bbs04 verify from the wire formats: gpk (390 B), signatures (435 B each), messages of msg_len bytes each.  One byte per
+        signature: 1 / 0, or 0xff where the reference would terminate.  A gpk that does not decode is C12381_E_POINT (every byte
+        0xff): raised when strict, returned as bytes otherwise."""
+        n = len(sigs435) // 435
+        out = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_bbs04_verify_batch(self.h, n, msg_len, _p(gpk390), _p(sigs435), _p(msgs) if msg_len else None, _p(out)),
+                 allow_point=not strict)
+        return out.raw[:n]
+
+    def bbs04_verify_dev(self, n, msg_len, gpk_ptr, sig_ptr, msg_ptr, ok_ptr):
+        self._ck(self.lib.c12381_bbs04_verify_batch_dev(self.h, n, msg_len, _p(gpk_ptr), _p(sig_ptr), _p(msg_ptr), _p(ok_ptr)))
+
+    def bbs04_open(self, gmsk96: bytes, sigs435: bytes, strict: bool = True):
+        """bbs04 open: (n x 49-byte points T3 / (T1^xi1 T2^xi2), n status bytes: 0, or 0xff where the reference would terminate).
+        A gmsk scalar >= r is C12381_E_ARG (every status 0xff): raised when strict, returned otherwise."""
+        n = len(sigs435) // 435
+        out = ctypes.create_string_buffer(max(49 * n, 1))
+        st = ctypes.create_string_buffer(max(n, 1))
+        rc = self.lib.c12381_bbs04_open_batch(self.h, n, _p(gmsk96), _p(sigs435), _p(out), _p(st))
+        if not (rc == E_ARG and not strict and len(gmsk96) == 96 and n):
+            self._ck(rc)
+        return out.raw[:49 * n], st.raw[:n]
+
+    def bbs04_open_dev(self, n, gmsk_ptr, sig_ptr, out_ptr, status_ptr):
+        self._ck(self.lib.c12381_bbs04_open_batch_dev(self.h, n, _p(gmsk_ptr), _p(sig_ptr), _p(out_ptr), _p(status_ptr)))
 
     # ---- device-pointer entry points (ints = device addresses, e.g. torch tensor.data_ptr())
     def bbs_plus_sign(self, g1, h0, h, gamma32, x, r, m) -> bytes:

@@ -71,7 +71,7 @@ struct c12381_ctx {
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
            WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_G, WS_FQ_GATE, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
-           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_COUNT };
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;
@@ -171,7 +171,8 @@ int g1_finish(c12381_ctx* c, size_t n, const int32_t* proj, size_t stride, uint8
     return 0;
 }
 // Status words raised by the kernels since the last read: [0] an input point was not on the curve (its outputs are 0xff),
-// [1] a library-internal failure (a work-queue hand-over timed out: the affected outputs are 0xff as well).  Every host
+// [1] a library-internal failure (a work-queue hand-over timed out: the affected outputs are 0xff as well), [2] a device-side argument
+// check failed (bbs04 open: a gmsk scalar >= r; its status bytes are 0xff).  Every host
 // entry point ends here, so a word raised by an earlier asynchronous _dev call is reported by the next host call or
 // c12381_sync() on the same context, whichever comes first — _dev callers separate logical operations with c12381_sync().
 int read_flag(c12381_ctx* c) {
@@ -181,6 +182,10 @@ int read_flag(c12381_ctx* c) {
     if (c->h_flag[1]) {
         std::snprintf(c->err, sizeof c->err, "internal: a pairing work-queue hand-over timed out; the affected outputs are 0xff");
         return C12381_E_INTERNAL;
+    }
+    if (c->h_flag[2]) {
+        std::snprintf(c->err, sizeof c->err, "a secret scalar is not below r (bbs04 open: gmsk)");
+        return C12381_E_ARG;
     }
     return c->h_flag[0] ? C12381_E_POINT : 0;
 }
@@ -1838,4 +1843,156 @@ int c12381_bbs_plus_sign_batch(c12381_ctx* c, size_t n, size_t nmsg, const uint8
     return unstage(c, s);
 }
 
+
+// ---------------------------------------------------------------- SHA3-512 (k_bbs04.hip, sha3.hpp)
+// out[i] = SHA3-512 of the i-th len-byte message: hash_state's SHA3_init(64) / SHA3_process / SHA3_hash (set.hpp:317-392), one lane per message
+static int sha3_args(size_t len, const void* msgs, const void* out) { return (!out || (len && !msgs)) ? C12381_E_ARG : 0; }
+static int launch_sha3(c12381_ctx* c, size_t n, size_t len, const uint8_t* msgs, uint8_t* out) {
+    hipLaunchKernelGGL(sha3_512_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, len, msgs, out);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+int c12381_sha3_512_batch_dev(c12381_ctx* c, size_t n, size_t len, const uint8_t* msgs, uint8_t* out64) {
+    int rc = bind(c); if (rc || (rc = sha3_args(len, msgs, out64))) return rc;
+    if (n == 0) return 0;
+    return launch_sha3(c, n, len, msgs, out64);
+}
+int c12381_sha3_512_batch(c12381_ctx* c, size_t n, size_t len, const uint8_t* msgs, uint8_t* out64) {
+    int rc = bind(c); if (rc || (rc = sha3_args(len, msgs, out64))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{len ? msgs : nullptr, len * n}}, {{out64, 64 * n}})) || (rc = launch_sha3(c, n, len, s.in[0], s.out[0]))) return rc;
+    return unstage(c, s);
+}
+
+// ---------------------------------------------------------------- bbs04 group signatures (examples/bbs04/src/bbs.cpp)
+// verify (:61-78), per signature: decode T1..T3 and range-check the six Zp fields (bbs04_prep_kernel), thirteen scalar multiplications by
+// the G1 kernels — six variable-base in one launch, seven against u, v, h, g1 through their fixed-base tables (generic kernel when a base
+// is not a subgroup point) — complete additions (bbs04_combine_kernel), affine conversion, R3 by the k = 2 fixed-G2 product, the
+// transcript, SHA3-512 mod r against c (bbs04_check_kernel).  Batches run in chunks of BBS04_CHUNK signatures.  WS_BBS04 holds
+// BBS04_PUB_BYTES of decoded public points and, per signature of a chunk, bbs04_sig_bytes(msg_len) bytes (T records, 13 scalar columns,
+// statuses, R and P points, GT value, transcript); the shared scalar-multiplication workspaces hold 13 projective points per signature.
+constexpr size_t BBS04_CHUNK = (size_t)1 << 18;
+constexpr size_t BBS04_PUB_BYTES = 2048;       // [0] 4 x 49 G1 wire | [256] 2 x 97 G2 wire | [512] g1, h, u, v (96 B) | [1024] g2, w (192 B) | [1536] 6 statuses
+struct bbs04_slab { uint8_t *t49, *t96, *sc, *c32, *st, *st_t, *r49, *p96, *gt, *tr; size_t bytes; };
+static bbs04_slab bbs04_layout(uint8_t* base, size_t m, size_t msg_len) {
+    bbs04_slab s;
+    size_t o = BBS04_PUB_BYTES;
+    auto take = [&](uint8_t*& p, size_t bytes) { p = base ? base + o : nullptr; o = round_up(o + bytes, 256); };
+    take(s.t49, 3 * 49 * m); take(s.t96, 6 * 96 * m); take(s.sc, 13 * 32 * m); take(s.c32, 32 * m); take(s.st, m); take(s.st_t, 3 * m);
+    take(s.r49, 4 * 49 * m); take(s.p96, 2 * 96 * m); take(s.gt, 576 * m); take(s.tr, (msg_len + 919) * m);
+    s.bytes = o;
+    return s;
+}
+// the public points on the side stream (two short square-root chains beside the per-signature work on the context's stream)
+static int bbs04_pub(c12381_ctx* c, const uint8_t* gpk, uint8_t* d) {
+    int rc;
+    if ((rc = ensure_fork_event(c))) return rc;
+    HIPCK(c, hipEventRecord(c->ev_chunk[0], c->stream));
+    HIPCK(c, hipStreamWaitEvent(c->side, c->ev_chunk[0], 0));
+    hipLaunchKernelGGL(bbs04_pub_kernel, dim3(grid_for(4 * 49 + 2 * 97)), dim3(BLOCK), 0, c->side, gpk, d, d + 256);
+    hipLaunchKernelGGL(g1_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)4, d, d + 512, d + 1536, 0);
+    hipLaunchKernelGGL(g2_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)2, d + 256, d + 1024, d + 1540, 0);
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipEventRecord(c->ev_side, c->side));
+    return 0;
+}
+static int bbs04_verify_args(size_t msg_len, const void* gpk, const void* sig, const void* msgs, const void* ok) {
+    return (!gpk || !sig || !ok || (msg_len && !msgs)) ? C12381_E_ARG : 0;
+}
+int c12381_bbs04_verify_batch_dev(c12381_ctx* c, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* sig_435, const uint8_t* msgs,
+                                  uint8_t* ok) {
+    int rc = bind(c); if (rc || (rc = bbs04_verify_args(msg_len, gpk_390, sig_435, msgs, ok))) return rc;
+    if (n == 0) return 0;
+    const size_t ch = n < BBS04_CHUNK ? n : BBS04_CHUNK, L = msg_len + 919;
+    if ((rc = ensure(c, c12381_ctx::WS_BBS04, bbs04_layout(nullptr, ch, msg_len).bytes))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS04];
+    if ((rc = bbs04_pub(c, gpk_390, d))) return rc;
+    const uint8_t *g1 = d + 512, *h = d + 512 + 96, *u = d + 512 + 192, *v = d + 512 + 288;
+    const bool fb = fixed_base_enabled();
+    for (size_t off = 0; off < n; off += ch) {
+        const size_t m = n - off < ch ? n - off : ch;
+        const bbs04_slab s = bbs04_layout(d, m, msg_len);
+        hipLaunchKernelGGL(bbs04_prep_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, sig_435 + 435 * off, s.t49, s.sc, s.c32, s.st);
+        hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(3 * m)), dim3(BLOCK), 0, c->stream, 3 * m, s.t49, s.t96, s.st_t, 0);
+        HIPCK(c, hipGetLastError());
+        // variable bases T1, T2, T3, T1, T2, T3 against scalar columns 0-5: one launch of 6 m lanes
+        HIPCK(c, hipMemcpyAsync(s.t96 + 3 * 96 * m, s.t96, 3 * 96 * m, hipMemcpyDeviceToDevice, c->stream));
+        if (off == 0) HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        const size_t stride = round_up(13 * m, 64);
+        if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+        if ((rc = g1_mul_to_proj(c, 6 * m, s.t96, s.sc, stride))) return rc;
+        // fixed bases: columns 6-12 (u, v, u, v, h, g1, h); table slots u -> 0, v -> 1, h -> 2, g1 -> 3
+        const uint8_t* base[7] = {u, v, u, v, h, g1, h};
+        const int slot[7] = {0, 1, 0, 1, 2, 3, 2};
+        if (fb)
+            for (int t = 0; t < 4; ++t)
+                if ((rc = fixed_table(c, c12381_ctx::WS_FB_G1_0 + t, t == 0 ? u : (t == 1 ? v : (t == 2 ? h : g1)), false))) return rc;
+        for (int k = 0; k < 7; ++k) {
+            const size_t col = 6 + (size_t)k;
+            const int32_t* skip = nullptr;
+            if (fb) {
+                skip = (const int32_t*)c->ws[c12381_ctx::WS_FB_G1_0 + slot[k]];
+                hipLaunchKernelGGL(g1_fixed_eval_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, skip, s.sc + 32 * col * m,
+                                   (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, col * m);
+                HIPCK(c, hipGetLastError());
+            }
+            if ((rc = g1_mul_to_proj(c, m, base[k], s.sc + 32 * col * m, stride, 0, col * m, skip))) return rc;
+        }
+        int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
+        hipLaunchKernelGGL(bbs04_combine_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, proj, stride);
+        HIPCK(c, hipGetLastError());
+        if ((rc = g1_finish(c, 4 * m, proj, stride, s.r49, 49))) return rc;
+        if ((rc = g1_finish(c, 2 * m, proj + 4 * m, stride, s.p96, 96))) return rc;
+        if ((rc = c12381_pair_product_fixed_g2_batch_dev(c, m, 2, s.p96, d + 1024, s.gt, 0u))) return rc;
+        const size_t bytes = m * L;
+        hipLaunchKernelGGL(bbs04_transcript_kernel, dim3(grid_for(bytes)), dim3(BLOCK), 0, c->stream, m, msg_len, msg_len ? msgs + msg_len * off : msgs,
+                           s.t49, s.t96, s.r49, s.gt, s.tr);
+        hipLaunchKernelGGL(bbs04_check_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, L, s.tr, s.c32, s.st, s.st_t, d + 1536, ok + off, c->d_flag);
+        HIPCK(c, hipGetLastError());
+    }
+    return 0;
+}
+int c12381_bbs04_verify_batch(c12381_ctx* c, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* sig_435, const uint8_t* msgs, uint8_t* ok) {
+    int rc = bind(c); if (rc || (rc = bbs04_verify_args(msg_len, gpk_390, sig_435, msgs, ok))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{gpk_390, 390}, {sig_435, 435 * n}, {msg_len ? msgs : nullptr, msg_len * n}}, {{ok, n}}))) return rc;
+    if ((rc = c12381_bbs04_verify_batch_dev(c, n, msg_len, s.in[0], s.in[1], s.in[2], s.out[0]))) return rc;
+    return unstage(c, s);
+}
+// open (:80-86): a = T3 - (T1^xi1 + T2^xi2), `^` = PAIR_G1mul by the generic G1 kernel (both columns in one launch of 2 m lanes)
+static int bbs04_open_args(const void* gmsk, const void* sig, const void* out, const void* status) { return (!gmsk || !sig || !out || !status) ? C12381_E_ARG : 0; }
+int c12381_bbs04_open_batch_dev(c12381_ctx* c, size_t n, const uint8_t* gmsk_96, const uint8_t* sig_435, uint8_t* out49, uint8_t* status) {
+    int rc = bind(c); if (rc || (rc = bbs04_open_args(gmsk_96, sig_435, out49, status))) return rc;
+    if (n == 0) return 0;
+    const size_t ch = n < BBS04_CHUNK ? n : BBS04_CHUNK;
+    if ((rc = ensure(c, c12381_ctx::WS_BBS04, bbs04_layout(nullptr, ch, 0).bytes))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS04];
+    for (size_t off = 0; off < n; off += ch) {
+        const size_t m = n - off < ch ? n - off : ch;
+        const bbs04_slab s = bbs04_layout(d, m, 0);
+        hipLaunchKernelGGL(bbs04_open_prep_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, gmsk_96, sig_435 + 435 * off, s.t49, s.sc, s.st, c->d_flag);
+        hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(3 * m)), dim3(BLOCK), 0, c->stream, 3 * m, s.t49, s.t96, s.st_t, 0);
+        HIPCK(c, hipGetLastError());
+        const size_t stride = round_up(2 * m, 64);
+        if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+        if ((rc = g1_mul_to_proj(c, 2 * m, s.t96, s.sc, stride))) return rc;
+        int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
+        hipLaunchKernelGGL(bbs04_open_combine_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, proj, stride, (const uint8_t*)s.t96 + 2 * 96 * m);
+        HIPCK(c, hipGetLastError());
+        if ((rc = g1_finish(c, m, proj, stride, out49 + 49 * off, 49))) return rc;
+        hipLaunchKernelGGL(bbs04_open_status_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, s.st, s.st_t, status + off);
+        HIPCK(c, hipGetLastError());
+    }
+    return 0;
+}
+int c12381_bbs04_open_batch(c12381_ctx* c, size_t n, const uint8_t* gmsk_96, const uint8_t* sig_435, uint8_t* out49, uint8_t* status) {
+    int rc = bind(c); if (rc || (rc = bbs04_open_args(gmsk_96, sig_435, out49, status))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{gmsk_96, 96}, {sig_435, 435 * n}}, {{out49, 49 * n}, {status, n}}))) return rc;
+    if ((rc = c12381_bbs04_open_batch_dev(c, n, s.in[0], s.in[1], s.out[0], s.out[1]))) return rc;
+    return unstage(c, s);
+}
 }  // extern "C"

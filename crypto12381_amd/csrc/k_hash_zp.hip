@@ -204,22 +204,6 @@ __global__ void __launch_bounds__(BLOCK, 2) bbs_wire_pub_kernel(size_t nblk, con
         g2s97[u] = e == 0 ? g1_g2_h0[49 + b] : pk97[b];
     }
 }
-__device__ __forceinline__ bool wire_zp(uint8_t* out32, const uint8_t* b48) {
-    uint32_t hi = 0, w[8];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) hi |= b48[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {                     // w[0] = least significant word
-        const uint8_t* q = b48 + 16 + 4 * (7 - i);
-        w[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | (uint32_t)q[3];
-    }
-    uint64_t bw = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)w[i] - ORDER_R[i] - bw; bw = (t >> 32) & 1; }
-#pragma unroll
-    for (int i = 0; i < 32; ++i) out32[i] = b48[16 + i];
-    return hi == 0 && bw == 1;                         // value < r
-}
 __global__ void __launch_bounds__(BLOCK, 2) bbs_wire_prep_kernel(size_t n, size_t msg_len, size_t nblk, const uint8_t* sig145, const uint8_t* msgs,
                                                               uint8_t* a49, uint8_t* x32, uint8_t* r32, uint8_t* m32, uint8_t* status) {
     const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;

@@ -6,6 +6,7 @@
 //   k_hash_zp.hip  hash-to-G1 and the scalar-field (Zp) helpers
 //   k_pairk.hip  K-way pairing products against fixed G2 points (line tables, prep, work-queue kernels)
 //   k_fixed.hip  fixed-base tables and their evaluation (public-parameter columns of BBS+)
+//   k_bbs04.hip  SHA3-512 (sha3.hpp) and the bbs04 group-signature stages around the scalar multiplications and the pairing product
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -111,6 +112,16 @@ constexpr int ZP_INV_RUN = 16;
 __global__ void __launch_bounds__(BLOCK, 2) zp_batch_inv_kernel(size_t n, size_t T, const uint8_t* x, const uint8_t* gamma, uint8_t* out, uint32_t* pref);
 __global__ void __launch_bounds__(BLOCK, 2) zp_from_hash_kernel(size_t n, const uint8_t* digests, uint8_t* out);
 __global__ void __launch_bounds__(BLOCK, 2) zp_fold_kernel(size_t n, const uint8_t* a, const uint8_t* b, size_t T, uint8_t* out);
+// k_bbs04.hip: SHA3-512 and the bbs04 group-signature kernels
+__global__ void __launch_bounds__(BLOCK, 2) sha3_512_kernel(size_t n, size_t len, const uint8_t* msgs, uint8_t* out64);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_pub_kernel(const uint8_t* gpk390, uint8_t* g1s49, uint8_t* g2s97);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_prep_kernel(size_t n, const uint8_t* sig435, uint8_t* t49, uint8_t* sc, uint8_t* c32, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_combine_kernel(size_t n, int32_t* proj, size_t stride);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_transcript_kernel(size_t n, size_t msg_len, const uint8_t* msgs, const uint8_t* t49, const uint8_t* t96, const uint8_t* r49, const uint8_t* gt576, uint8_t* out);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_check_kernel(size_t n, size_t L, const uint8_t* tr, const uint8_t* c32, const uint8_t* st_sig, const uint8_t* st_t, const uint8_t* st_pub, uint8_t* ok, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_open_prep_kernel(size_t n, const uint8_t* gmsk96, const uint8_t* sig435, uint8_t* t49, uint8_t* sc, uint8_t* st, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_open_combine_kernel(size_t n, int32_t* proj, size_t stride, const uint8_t* t3_96);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_open_status_kernel(size_t n, const uint8_t* st_sig, const uint8_t* st_t, uint8_t* status);
 __global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(const uint8_t* base, int nbytes, int32_t* header);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_table_kernel(const uint8_t* base96, int32_t* buf);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_eval_kernel(size_t n, const int32_t* buf, const uint8_t* scalars, int32_t* proj, size_t proj_stride, size_t proj_off);

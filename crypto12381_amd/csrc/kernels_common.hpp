@@ -171,4 +171,22 @@ __device__ __noinline__ void gt_load576(fp12& f, const uint8_t* p) {
     }
 }
 
+// parse<Zp> of a 48-byte wire field (zp_number.hpp:226-236): the 32-byte scalar (its low 32 bytes) and whether the value is below r
+__device__ __forceinline__ bool wire_zp(uint8_t* out32, const uint8_t* b48) {
+    uint32_t hi = 0, w[8];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) hi |= b48[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                     // w[0] = least significant word
+        const uint8_t* q = b48 + 16 + 4 * (7 - i);
+        w[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | (uint32_t)q[3];
+    }
+    uint64_t bw = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)w[i] - ORDER_R[i] - bw; bw = (t >> 32) & 1; }
+#pragma unroll
+    for (int i = 0; i < 32; ++i) out32[i] = b48[16 + i];
+    return hi == 0 && bw == 1;                         // value < r
+}
+
 }  // namespace

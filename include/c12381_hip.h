@@ -309,7 +309,7 @@ int c12381_bbs_plus_verify_aggregate_dev(c12381_ctx* ctx, size_t n, size_t nmsg,
 /* G1Point::from_hash (include/crypto12381/g1_point.hpp:219-234) from the 64-byte SHA3-512 digest on: the digest as a
  * big-endian integer mod p (fixed_time_mod :55 -> 94-97), residue (:110 -> 149-152 -> FP_nres), map_to_point
  * (:113 -> 154-157 -> ECP_map2point: simplified SWU + 11-isogeny), multiply_cofactor (:116 -> 159-162 -> ECP_cfp),
- * encoded like to_bytes.  Hashing the caller's serialisation (hash_state, set.hpp:317-392) stays on the host.
+ * encoded like to_bytes.  Hashing the caller's serialisation (hash_state, set.hpp:317-392): c12381_sha3_512_batch.
  * out_fmt 49 or 96.  Not RFC 9380 hash_to_curve: one field element per digest, as the reference defines it. */
 int c12381_g1_from_hash_batch(c12381_ctx* ctx, size_t n, const uint8_t* digests64, uint8_t* out, int out_fmt);
 int c12381_g1_from_hash_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* digests64, uint8_t* out, int out_fmt);
@@ -354,6 +354,48 @@ int c12381_bbs_plus_sign_batch(c12381_ctx* ctx, size_t n, size_t nmsg, const uin
                                const uint8_t* gamma_32, const uint8_t* x_32, const uint8_t* r_32, const uint8_t* m_32, uint8_t* A_out96);
 int c12381_bbs_plus_sign_batch_dev(c12381_ctx* ctx, size_t n, size_t nmsg, const uint8_t* g1_96, const uint8_t* h0_96, const uint8_t* h_96,
                                    const uint8_t* gamma_32, const uint8_t* x_32, const uint8_t* r_32, const uint8_t* m_32, uint8_t* A_out96);
+
+/* SHA3-512 (the hash in front of hash-to-G1 / Zp from_hash) ------------------------------------------------------ */
+/* out[i] = SHA3-512(msgs[i*len .. i*len + len)): what hash_state computes over the bytes it is fed (include/crypto12381/set.hpp:317-392
+ * -> miracl_core::sha3_init(64) / sha3_process / sha3_hash, MIRACL SHA3_init / SHA3_process / SHA3_hash: FIPS 202 SHA3-512, rate 72
+ * bytes, padding 0x06 ... 0x80).  len = 0 is allowed (msgs may then be NULL).  One lane per message.  The device reads each message
+ * in aligned 32-bit words: up to 3 bytes either side of a message are read (never used) when it does not start or end on a 4-byte
+ * boundary, never beyond the words that hold its bytes. */
+int c12381_sha3_512_batch(c12381_ctx* ctx, size_t n, size_t len, const uint8_t* msgs, uint8_t* out64);
+int c12381_sha3_512_batch_dev(c12381_ctx* ctx, size_t n, size_t len, const uint8_t* msgs, uint8_t* out64);
+
+/* bbs04 group signatures (examples/bbs04/src/bbs.cpp) from the WIRE formats -------------------------------------------------------- */
+/* Wire layouts (examples/bbs04/include/bbs.hpp):
+ *   gpk        serialize(g1, g2, h, u, v, w)                        49 + 97 + 49 + 49 + 49 + 97 = 390 bytes
+ *   gmsk       serialize(xi1, xi2)                                   2 x 48 = 96 bytes
+ *   signature  serialize(T1, T2, T3, c, s_alpha, s_beta, s_x, s_delta1, s_delta2)   3 x 49 + 6 x 48 = 435 bytes
+ *   messages   msg_len raw bytes each, contiguous (msg_len = 0 allowed, msgs may then be NULL)
+ * Decoding is from_bytes with the header layer's "leading 0x00 = infinity" (g1_point.hpp:87-111; ECP_fromOctet: x taken mod p, no
+ * subgroup check) and parse<Zp>'s range check (48 big-endian bytes below r, zp_number.hpp:226-236).
+ *
+ * c12381_bbs04_verify_batch: ok[j] = verify(gpk, msg_j, sig_j) (bbs.cpp:61-78).  Per signature, `^` being multiply (PAIR_G1mul, the
+ * library's G1 kernels, exact for every curve point) and negations Zp negations mod r (-0 = 0):
+ *   R1 = u^sa T1^-c   R2 = v^sb T2^-c   R4 = T1^sx u^-sd1   R5 = T2^sx v^-sd2
+ *   R3 = e(T3^sx h^(-sd1 + -sd2) / g1^c, g2) * e(h^-(sa + sb) T3^c, w)     (c12381_pair_product_fixed_g2_batch with k = 2)
+ *   ok = [ c == SHA3-512(msg | T1 | T2 | T3 | R1 | R2 | R3 | R4 | R5) mod r ]   (hash(...).to(Zp), zp_number.hpp:540-548)
+ * The transcript is msg_len + 919 bytes: G1 elements 49-byte compressed (infinity = 49 zeros), R3 576 bytes (FP12_toOctet).  T1..T3 are
+ * hashed re-encoded from the parsed points, as hash() serialises them: a leading 0x00 hashes as 49 zeros whatever follows, an x >= p
+ * as its residue.
+ * Status: ok[j] = 1 / 0 as verify returns; 0xff where the reference would terminate (verify is noexcept): T1, T2 or T3 does not decode
+ * (bad tag, x not on the curve) or a Zp field is >= r.  A gpk that does not decode makes every lane 0xff and returns C12381_E_POINT.
+ * Workspace (c12381_trim releases it): per signature of a chunk of up to 2^18, 2139 + (msg_len + 919) bytes plus 13 projective G1 points
+ * (1872 bytes) in the scalar-multiplication workspace, whose window tables take 2816 bytes per lane of six variable-base columns
+ * (at most 2.95 GB); 2^18 signatures with 32-byte messages: about 1.5 GB besides the tables. */
+int c12381_bbs04_verify_batch(c12381_ctx* ctx, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* sig_435, const uint8_t* msgs,
+                              uint8_t* ok);
+int c12381_bbs04_verify_batch_dev(c12381_ctx* ctx, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* sig_435, const uint8_t* msgs,
+                                  uint8_t* ok);
+/* c12381_bbs04_open_batch: out49[j] = serialize(T3 / (T1^xi1 * T2^xi2)) (open, bbs.cpp:80-86), the signer's A_i for a valid signature.
+ * status[j] = 0, or 0xff where the reference would terminate on signature j (parse<G1^3 | Zp^6>: T1, T2 or T3 does not decode, or a
+ * Zp field >= r); out49[j] is then unspecified.  xi1 or xi2 >= r sets every status byte to 0xff and returns C12381_E_ARG (the _dev form
+ * reports it at the next c12381_sync). */
+int c12381_bbs04_open_batch(c12381_ctx* ctx, size_t n, const uint8_t* gmsk_96, const uint8_t* sig_435, uint8_t* out49, uint8_t* status);
+int c12381_bbs04_open_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* gmsk_96, const uint8_t* sig_435, uint8_t* out49, uint8_t* status);
 
 #ifdef __cplusplus
 }
