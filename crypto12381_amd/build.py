@@ -21,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 UNITS = ["c12381_hip.hip", "k_g1.hip", "k_g2gt.hip", "k_g2h.hip", "k_pair3.hip", "k_hash_zp.hip", "k_fixed.hip", "k_pairk.hip", "k_bbs04.hip"]
 EXP_UNITS = ["c12381_hip.hip", "k_g2gt.hip"]                # the units that test C12381_EXPERIMENTS
+EXP_ONLY_UNITS = ["k_fp_raw.hip"]                           # linked into the experiments library alone: the raw-limb test kernel of the Fp / Fp2 leaf
 LIB = os.path.join(HERE, "lib", "libc12381_hip.so")
 LIB_EXP = os.path.join(HERE, "lib", "libc12381_hip_exp.so")
 # bench-only: the one-lane clock probe bench.py runs beside each dominant kernel (csrc/microbench/clock_probe.hip); not linked into the product
@@ -130,7 +131,7 @@ def _stamp_ok(unit: str, exp: bool) -> bool:
 
 
 def _jobs():
-    return [(u, False) for u in UNITS] + [(u, True) for u in EXP_UNITS]
+    return [(u, False) for u in UNITS] + [(u, True) for u in EXP_UNITS + EXP_ONLY_UNITS]
 
 
 def needs_build() -> bool:
@@ -143,7 +144,7 @@ def needs_build() -> bool:
                 print("crypto12381_amd.build: no compiler and no prebuilt %s (bench-only clock probe): continuing without it" % LIB_PROBE, flush=True)
             return False
         raise RuntimeError("crypto12381_amd.build: %s not found and no prebuilt %s — build the library where hipcc is available" % (HIPCC, ", ".join(missing)))
-    srcs = _headers() + [os.path.join(CSRC, u) for u in UNITS]
+    srcs = _headers() + [os.path.join(CSRC, u) for u in UNITS + EXP_ONLY_UNITS]
     return (_stale(LIB, srcs) or _stale(LIB_EXP, srcs) or _stale(LIB_PROBE, [PROBE_SRC])
             or not all(_stamp_ok(u, e) and os.path.exists(os.path.join(OBJ, _obj_name(u, e) + ".o")) for u, e in _jobs()))
 
@@ -196,7 +197,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         with ThreadPoolExecutor(max_workers=8) as ex:
             objs = dict(zip(jobs, ex.map(lambda j: _compile(j[0], j[1], force, verbose), jobs)))
         for lib, exp in ((LIB, False), (LIB_EXP, True)):
-            link = [objs[(u, exp and u in EXP_UNITS)] for u in UNITS]
+            link = [objs[(u, exp and u in EXP_UNITS)] for u in UNITS] + ([objs[(u, True)] for u in EXP_ONLY_UNITS] if exp else [])
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *link]
             if verbose:
                 print(" ".join(cmd), flush=True)

@@ -127,6 +127,8 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp]
         for name in ("c12381_bbs04_open_batch", "c12381_bbs04_open_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, vp]
+        if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
+            lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
     return _lib
 
@@ -553,6 +555,14 @@ class Context:
 
     def fp_op_dev(self, op, n, a_ptr, b_ptr, out_ptr):
         self._ck(self.lib.c12381_fp_op_batch_dev(self.h, self.FP_OPS[op], n, _p(a_ptr), _p(b_ptr), _p(out_ptr)))
+
+    def exp_fp_raw(self, op: int, n: int, arity: int, outputs: int, limbs: bytes, k: bytes) -> bytes:
+        """Experiments library only: the raw-limb test kernel (n x arity x 14 int32 in, n x 4 int32 multipliers, n x outputs x 14 int32 out)."""
+        if not hasattr(self.lib, "c12381_exp_fp_raw_batch"):
+            raise RuntimeError("c12381_exp_fp_raw_batch: only the experiments library exports the raw-limb test entry")
+        out = ctypes.create_string_buffer(max(56 * outputs * n, 1))
+        self._ck(self.lib.c12381_exp_fp_raw_batch(self.h, op, n, arity, outputs, _p(limbs), _p(k), _p(out)))
+        return out.raw[:56 * outputs * n]
 
     def g1_mul_dev(self, n, pts_ptr, sc_ptr, out_ptr, fmt=49):
         self._ck(self.lib.c12381_g1_mul_batch_dev(self.h, n, _p(pts_ptr), _p(sc_ptr), _p(out_ptr), fmt))

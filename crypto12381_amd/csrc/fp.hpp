@@ -15,6 +15,8 @@
 //     |value| < (VBa*VBb*p/R + 1) p, i.e. within (-p, 2p) whenever VBa*VBb <= 2^11.  Builds with C12381_CHECK_BOUNDS (host
 //     simulation used by the CPU tests) carry the bounds at run time and assert them; the
 //     bounds depend only on the operation sequence, never on the data.
+//     Operands AT these bounds (limbs +-L, 2^31 - 1 against its partner, VBa*VBb = 10^6, 2^11 and 1), with every raw result limb predicted
+//     from integers: tests/test_host_sim_fp_raw.py and tests/test_gpu_fp_raw.py, test_raw_limbs_at_the_bounds[MUL] and the other ops.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -91,7 +93,7 @@ inline void bounds_fail(const char* what, double a, double b) {
     backtrace_symbols_fd(frames, nf, 2);      // resolve with addr2line -e libsim.so <offsets> (build with -g)
     std::abort();
 }
-constexpr double P_OVER_R = 0.000396;          // p / 2^392 < this
+constexpr double P_OVER_R = 0.000397;          // p / 2^392 = 0.00039679... < this (0.000396 was BELOW it: tests/test_host_sim_fp_raw.py, operands at VBa VBb = 10^6)
 constexpr double TOP_PER_P = 106514.0;         // p / 2^364 < this: |top limb| <= VB * TOP_PER_P + 1
 inline void check_actual(const fp& a, const char* where) {
     for (int i = 0; i < NL; ++i)
@@ -285,7 +287,8 @@ C12381_HD void fp_sqr(fp& r, const fp& a) {
 // `col(k, acc)` ADDS the k-th column  sum_{i+j=k} (...)  of the un-reduced form to the running accumulator, k = 0..26
 // (straight into it: a column that is summed on the side and then added costs a 64-bit add per column and form);
 // the engine interleaves the reduction exactly like fp_mul.  Column sums must stay below 2^63:
-// with |limbs| <= LBa, LBb that is  14 * T * LBa * LBb + 14 * 2^56 + 2^40 < 2^63  for T products.
+// with |limbs| <= LBa, LBb that is  14 * T * LBa * LBb + 14 * 2^56 + 2^40 < 2^63  for T products
+// (pinned for T = 1..4 by test_raw_limbs_at_the_bounds[RED1..RED4, REDS1..REDS4], tests/test_host_sim_fp_raw.py and test_gpu_fp_raw.py).
 // Differences are formed by negating one operand's limbs once (fp_raw_neg), squares use a pre-doubled copy.
 C12381_HD void fp_col_acc(int64_t& acc, const fp& a, const fp& b, int k) {
     C12381_COUNT(1, 0);
@@ -394,9 +397,11 @@ C12381_HD void fp_reduce_cols_static(fp& r, ColFn col) {
 // by the checker through the callers' declarations); the VALUE bound of the result is declared by the caller (set_inj_bounds).
 C12381_HD void fp_inj(int64_t& acc, const fp& c, int i, int32_t k) { acc += (int64_t)c.l[i] * k; }
 C12381_HD void fp_inj_p(int64_t& acc, int i, int32_t k) { acc += (int64_t)FP_P[i] * k; }
-// round(top / (p / 2^364)) for a value whose lower limbs are normalised: the multiple of p nearest to the value (within 2 p / 106513);
-// the same estimate fp_weak_reduce uses
-C12381_HD int32_t fp_quot_top(int32_t top) { return (int32_t)(((int64_t)top * 40324 + ((int64_t)1 << 31)) >> 32); }
+// round(top / (p / 2^364)) for a value whose lower limbs are normalised: the multiple of p nearest to the value — |top 2^364 - q p| <=
+// (1/2 + 2/106513) p for EVERY top limb in [-2^28, 2^28) (tests/test_host_sim_fp_raw.py::test_quot_top_every_top_limb runs them all).
+// 2^47 / (p / 2^364) = 1321315991.6: 31 bits of the reciprocal.  The 16-bit estimate fp_weak_reduce keeps (40324 / 2^32, 1.6e-5 too
+// large) drifts by 0.04 p at the top limbs of 2500 p and missed that figure (worst 0.5397 p at top limb -268355573).
+C12381_HD int32_t fp_quot_top(int32_t top) { return (int32_t)(((int64_t)top * 1321315992 + ((int64_t)1 << 46)) >> 47); }
 // a small integer the optimiser cannot see through: multipliers of injected terms must reach instruction selection as REGISTER operands
 // of v_mad_i64_i32 (a literal 2 or -1 is strength-reduced into sign extension + 64-bit shift / add: two or three instructions)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -556,7 +561,7 @@ C12381_HD void fp_from_mont_canonical(fp& r, const fp& a) {
     one.l[0] = 1;
     C12381_BOUNDS(one.lb = 1; one.vb = 1e-100;)
     fp t;
-    fp_mul(t, a, one);            // value in [0, p], limbs normalised, top limb >= 0
+    fp_mul(t, a, one);            // value in [0, p], limbs normalised, top limb >= 0 (test_raw_limbs_at_the_bounds[CANON]: k p + e, k = -19000..19000)
     // t == p ?  (only when a is a non-zero multiple of p)
     bool eqp = true;
 #pragma unroll

@@ -450,7 +450,7 @@ C12381_HDN void f12t_usqr3_h(fp4& H, const tri& t) {
                                [&](int i, int64_t& acc) { fp_inj(acc, yb.a, i, mu); fp_inj_p(acc, i, nq_re); });
             fp_reduce_cols_inj(S.b, [&](int k, int64_t& acc) { fp_col_acc(acc, ys.a.a, ys.b.b, k); fp_col_acc(acc, ys.a.b, ys.b.a, k); },
                                [&](int i, int64_t& acc) { fp_inj(acc, yb.b, i, mu); fp_inj_p(acc, i, nq_im); });
-            // |mu y.b - q p| <= (0.5 + 2 / 106513 + 1e-5 |y.b| / p) p: the nearest multiple of p by the top limb (fp_quot_top)
+            // |mu y.b - q p| <= (0.5 + 2 / 106513) p: the nearest multiple of p by the top limb (fp_quot_top; the 1e-5 |y.b| / p of drift its 16-bit estimate had is gone)
             C12381_BOUNDS({ set_inj_bounds(S.a, ys.a.a.lb * ys.b.a.lb + ys.a.b.lb * ys.b.b.lb, ys.a.a.vb * ys.b.a.vb + ys.a.b.vb * ys.b.b.vb, 0.501,
                                            yb.a.lb + 8.0 * 268435456.0, "usqr3 S.a"); check_actual_vb(S.a, "usqr3 S.a value");
                             set_inj_bounds(S.b, ys.a.a.lb * ys.b.b.lb + ys.a.b.lb * ys.b.a.lb, ys.a.a.vb * ys.b.b.vb + ys.a.b.vb * ys.b.a.vb, 0.501,

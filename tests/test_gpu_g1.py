@@ -23,6 +23,9 @@ def test_fp_ops_golden(ctx):
 
 
 def test_fp_mul_random_vs_python(ctx):
+    """Random residues through c12381_fp_op_batch.  NOT covered here: every operand is normalised by fp_from_words_be (limbs in
+    [0, 2^28), value below 10 p), so negative limbs, limbs above 2^28 and values outside [0, p) never reach fp_mul this way —
+    test_gpu_fp_raw.py feeds the kernel raw limbs at the documented bounds."""
     n = 4096
     a = [prng(101, i, 48) % P for i in range(n)]
     b = [prng(102, i, 48) % P for i in range(n)]

@@ -1,0 +1,96 @@
+"""CPU tests of the Fp / Fp2 leaf (csrc/fp.hpp, fp2.hpp) on worst-case lazy limbs: every routine with a bound comment, run on RAW limbs
+under the bounds checker (tests/host_sim/fp_raw.cpp, C12381_CHECK_BOUNDS) with operands AT the documented limits (fp_raw_vectors.py),
+each raw result limb compared with plain integer mathematics, each promised post-condition asserted, the bounds the routines declare
+for their results checked against the data.  The device twin is test_gpu_fp_raw.py (same vectors, same expectations).
+Vectors per op: fp_raw_vectors.COUNTS (asserted at generation; every vector is run, none is skipped)."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+
+import fp_raw_vectors as V
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SIM_DIR = os.path.join(HERE, "host_sim")
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "crypto12381_amd", "csrc")
+LIBDIR = os.path.join(ROOT, "crypto12381_amd", "lib")
+sz = ctypes.c_size_t
+
+
+@pytest.fixture(scope="module")
+def sim():
+    so = os.path.join(SIM_DIR, "libsim_fp_raw.so")
+    src = os.path.join(SIM_DIR, "fp_raw.cpp")
+    srcs = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-DC12381_CHECK_BOUNDS", "-fPIC", "-shared", "-pthread", "-o", so, src], check=True)
+    lib = ctypes.CDLL(so)
+    lib.sim_fp_quot_top_worst.restype = ctypes.c_double
+    lib.sim_fp_quot_top_worst.argtypes = [ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int32)]
+    return lib
+
+
+def run_host(sim, name, vecs):
+    """-> (raw outputs, declared (lb, vb) per output) per vector"""
+    n = len(vecs)
+    limbs, bnd, k = V.pack(name, vecs)
+    no = V.OUTPUTS[name]
+    out = ctypes.create_string_buffer(56 * no * n)
+    ob = (ctypes.c_double * (2 * no * n))()
+    bad = ctypes.c_longlong(-1)
+    rc = sim.sim_fp_raw_batch(V.OPS[name], sz(n), limbs, bnd, k, out, ob, ctypes.byref(bad))
+    assert rc == 0, "%s: harness returned %d at lane %d (1 = outside the routine's precondition: a generator bug)" % (name, rc, bad.value)
+    outs = V.unpack(name, out.raw, n)
+    return outs, [[(ob[2 * (i * no + e)], ob[2 * (i * no + e) + 1]) for e in range(no)] for i in range(n)]
+
+
+@pytest.mark.parametrize("name", V.ALL_OPS)
+def test_raw_limbs_at_the_bounds(sim, name):
+    vecs = V.vectors(name)
+    assert len(vecs) == V.COUNTS[name]
+    outs, bounds = run_host(sim, name, vecs)
+    ran = 0
+    for v, o, b in zip(vecs, outs, bounds):
+        V.check_outputs(name, v, o, b)
+        ran += 1
+    assert ran == V.COUNTS[name]
+    print("%s: %d vectors" % (name, ran))
+
+
+def test_harness_reports_a_lane_outside_the_precondition(sim):
+    """the harness must refuse, not run, what the checker would abort on: limbs above the column limit of one product"""
+    o = V.Operand([V.T31] * 13 + [0])
+    limbs, bnd, k = V.pack("MUL", [V.Vec([o, o])])
+    out = ctypes.create_string_buffer(56)
+    ob = (ctypes.c_double * 2)()
+    bad = ctypes.c_longlong(-1)
+    assert sim.sim_fp_raw_batch(V.OPS["MUL"], sz(1), limbs, bnd, k, out, ob, ctypes.byref(bad)) == 1 and bad.value == 0
+
+
+def test_quot_top_every_top_limb(sim):
+    """fp_quot_top over EVERY top limb in [-2^28, 2^28): the worst |top 2^364 - q p| / p, against the 1/2 + 2/106513 = 0.500018777 that
+    fp.hpp states.  Measured: 0.500000628 p, at top limb -260371321 (31-bit reciprocal 1321315992 / 2^47).  The 16-bit estimate
+    40324 / 2^32 that this test found in place measured 0.539732600 p, at top limb -268355573, and failed this assertion."""
+    wt = ctypes.c_int32(0)
+    worst = sim.sim_fp_quot_top_worst(-(1 << 28), 1 << 28, ctypes.byref(wt))
+    print("fp_quot_top: worst error %.9f p at top limb %d" % (worst, wt.value))
+    assert worst <= 0.5 + 2.0 / 106513, (worst, wt.value)
+
+
+def test_closure_lazy_ops_between_products(sim):
+    kinds = V.closure(lambda name, vecs: run_host(sim, name, vecs)[0], 3000)
+    print("closure steps:", kinds)
+    assert sum(kinds.values()) == 3000 and all(kinds.get(k, 0) > 100 for k in ("ADD", "SUB", "NEG", "MUL", "SQR")) and kinds.get("NORM1", 0) > 0
+
+
+def test_raw_entry_is_exported_by_the_experiments_library_only():
+    import crypto12381_amd.build as b
+    b.build()                                  # a no-op when the libraries are current (test_capi_symbols.py does the same)
+    product = ctypes.CDLL(os.path.join(LIBDIR, "libc12381_hip.so"))
+    experiments = ctypes.CDLL(os.path.join(LIBDIR, "libc12381_hip_exp.so"))
+    assert not hasattr(product, "c12381_exp_fp_raw_batch")
+    assert hasattr(experiments, "c12381_exp_fp_raw_batch")
+    with open(os.path.join(ROOT, "include", "c12381_hip.h")) as f:
+        assert "fp_raw" not in f.read()
