@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-UNITS = ["c12381_hip.hip", "k_g1.hip", "k_g2gt.hip", "k_g2h.hip", "k_pair3.hip", "k_hash_zp.hip", "k_fixed.hip", "k_pairk.hip", "k_bbs04.hip"]
+UNITS = ["c12381_hip.hip", "k_g1.hip", "k_g1sum.hip", "k_g2gt.hip", "k_g2h.hip", "k_pair3.hip", "k_hash_zp.hip", "k_fixed.hip", "k_pairk.hip", "k_bbs04.hip"]
 EXP_UNITS = ["c12381_hip.hip", "k_g2gt.hip"]                # the units that test C12381_EXPERIMENTS
 EXP_ONLY_UNITS = ["k_fp_raw.hip"]                           # linked into the experiments library alone: the raw-limb test kernel of the Fp / Fp2 leaf
 LIB = os.path.join(HERE, "lib", "libc12381_hip.so")
@@ -49,7 +49,8 @@ CFLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-fno-optimize-
 # With the linear chains of -opt-disable=reassociate the G1 scalar-multiplication kernels no longer gain from max-ilp: the default
 # strategy is 1.2 % faster there (three interleaved rounds, digests equal, profiles/r04_ab_sched_per_unit.txt: G1 2^20 24.63 -> 24.33 ms
 # mean, MSM unchanged), while G2 (+1.4 %), the Miller loop and the final exponentiation (+1.6 %) still lose without it.
-DEFAULT_SCHED_UNITS = ("k_g1.hip",)
+# k_g1sum.hip runs the same G1 loop with more additions per window and follows k_g1.hip (not measured on its own).
+DEFAULT_SCHED_UNITS = ("k_g1.hip", "k_g1sum.hip")
 
 
 def unit_cflags(unit: str):

@@ -77,6 +77,8 @@ def load_library() -> ctypes.CDLL:
         for name in ("c12381_g1_mul_batch_flags", "c12381_g1_mul_batch_flags_dev", "c12381_g2_mul_batch_flags", "c12381_g2_mul_batch_flags_dev",
                      "c12381_g1_msm_flags", "c12381_g1_msm_flags_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, ci, ctypes.c_uint]
+        for name in ("c12381_g1_mul_sum_batch", "c12381_g1_mul_sum_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, ci, vp, vp, vp, ci, ctypes.c_uint]
         for name in ("c12381_pair_batch_flags", "c12381_pair_batch_flags_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, ctypes.c_uint]
         for name in ("c12381_pair_batch", "c12381_pair_batch_dev"):
@@ -251,6 +253,18 @@ class Context:
 
     def g2_mul_flags_dev(self, n, pts_ptr, sc_ptr, out_ptr, fmt=97, flags=0):
         self._ck(self.lib.c12381_g2_mul_batch_flags_dev(self.h, n, _p(pts_ptr), _p(sc_ptr), _p(out_ptr), fmt, flags))
+
+    def g1_mul_sum(self, pts: bytes, scalars: bytes, k: int, fmt: int = 49, flags: int = 0, strict: bool = True) -> bytes:
+        """out[i] = sum over j < k of scalars[j n + i] * pts[j n + i]: k powers per lane under one doubling chain (the reference's
+        g^x * h^y, double_multiply).  pts / scalars: k argument-major arrays of n records; 1 <= k <= 4; returns n points of `fmt` bytes.
+        Every lane equals multiply on each term followed by add; flags: F_IN_SUBGROUP only"""
+        n = len(scalars) // (32 * k) if k > 0 else 0
+        out = ctypes.create_string_buffer(max(fmt * n, 1))
+        self._ck(self.lib.c12381_g1_mul_sum_batch(self.h, n, k, _p(pts), _p(scalars), _p(out), fmt, flags), allow_point=not strict)
+        return out.raw[:fmt * n]
+
+    def g1_mul_sum_dev(self, n, k, pts_ptr, sc_ptr, out_ptr, fmt=49, flags=0):
+        self._ck(self.lib.c12381_g1_mul_sum_batch_dev(self.h, n, k, _p(pts_ptr), _p(sc_ptr), _p(out_ptr), fmt, flags))
 
     def g1_add(self, a: bytes, b: bytes, fmt: int = 96, strict: bool = True) -> bytes:
         n = len(a) // 96

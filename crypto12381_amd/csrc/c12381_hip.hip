@@ -440,7 +440,7 @@ static bool msm_use_buckets(size_t n) {
 
 extern "C" {
 
-int c12381_version(void) { return (0 << 16) | 1; }
+int c12381_version(void) { return (0 << 16) | 2; }
 
 int c12381_create(int device, c12381_ctx** out) {
     if (!out) return C12381_E_ARG;
@@ -634,6 +634,41 @@ int c12381_g1_mul_batch_flags(c12381_ctx* c, size_t n, const uint8_t* pts, const
 }
 int c12381_g1_mul_batch(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt) {
     return c12381_g1_mul_batch_flags(c, n, pts, sc, out, fmt, 0u);
+}
+// Per-lane sums of k products under one doubling chain (k_g1sum.hip).  One term is g1_mul_kernel itself, so k = 1 returns the bytes of
+// c12381_g1_mul_batch_flags.  The table workspace is k records per lane: a launch covers CHUNK_ROUNDS / k machine rounds (4, 2, 2 for
+// k = 2, 3, 4 — 524 288, 262 144, 262 144 lanes), so the slab of a 2^20 batch is 2.95, 2.21, 2.95 GB: never more than g1_mul_to_proj's.
+// C12381_F_COMPRESSED_IN is refused: the loop re-reads the inputs of an exceptional lane and must not repeat k square roots there.
+static int g1_mul_sum_args(size_t n, int k, const void* pts, const void* sc, const void* out, int fmt, unsigned flags) {
+    static_assert(C12381_G1_MUL_SUM_MAX == G1_MUL_SUM_MAX, "C12381_G1_MUL_SUM_MAX");
+    return (k < 1 || k > C12381_G1_MUL_SUM_MAX || !g1_fmt(fmt) || (flags & ~(unsigned)C12381_F_IN_SUBGROUP) || (n && (!pts || !sc || !out))) ? C12381_E_ARG : 0;
+}
+int c12381_g1_mul_sum_batch_dev(c12381_ctx* c, size_t n, int k, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
+    int rc = bind(c); if (rc || (rc = g1_mul_sum_args(n, k, pts, sc, out, fmt, flags))) return rc;
+    if (n == 0) return 0;
+    if (k == 1) return c12381_g1_mul_batch_flags_dev(c, n, pts, sc, out, fmt, flags);
+    const size_t stride = round_up(n, 64);
+    const size_t full = (size_t)65536 * G1_OCC * (CHUNK_ROUNDS / (size_t)k);
+    const size_t chunk = n < full ? stride : full;
+    if ((rc = ensure(c, c12381_ctx::WS_TAB, (size_t)k * G1_TAB_DWORDS * chunk * 4))) return rc;
+    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+    auto kernel = k == 2 ? g1_mul_sum2_kernel : (k == 3 ? g1_mul_sum3_kernel : g1_mul_sum4_kernel);
+    for (size_t off = 0; off < n; off += chunk) {
+        const size_t m = n - off < chunk ? n - off : chunk;
+        timed tm(c, 0);
+        hipLaunchKernelGGL(kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, pts + 96 * off, sc + 32 * off, n, (int32_t*)c->ws[c12381_ctx::WS_TAB],
+                           (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, off, c->d_flag, (flags & C12381_F_IN_SUBGROUP) ? 0 : 1);
+        HIPCK(c, hipGetLastError());
+    }
+    return g1_finish(c, n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, out, fmt);
+}
+int c12381_g1_mul_sum_batch(c12381_ctx* c, size_t n, int k, const uint8_t* pts, const uint8_t* sc, uint8_t* out, int fmt, unsigned flags) {
+    int rc = bind(c); if (rc || (rc = g1_mul_sum_args(n, k, pts, sc, out, fmt, flags))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{pts, 96 * n * (size_t)k}, {sc, 32 * n * (size_t)k}}, {{out, (size_t)fmt * n}}))) return rc;
+    if ((rc = c12381_g1_mul_sum_batch_dev(c, n, k, s.in[0], s.in[1], s.out[0], fmt, flags))) return rc;
+    return unstage(c, s);
 }
 static int g1_add_dev(c12381_ctx* c, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, int fmt) {
     const size_t stride = round_up(n, 64);

@@ -685,6 +685,216 @@ C12381_HD bool g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf
     if (exc) g1_scalar_mul_complete(acc, px, py, p_is_inf, kin, lane_tab);
     return exc;
 }
+// ------------------------------------------------------------------ sum of K products under one doubling chain
+// sum_j [k_j]P_j per lane (the reference fuses g^x * h^y the same way: double_multiply -> ECP_mul2): K co-Z tables, ONE accumulator, per
+// window 5 doublings and 2K mixed additions.  `lane_tab` = K consecutive table records (K * G1_TAB_DWORDS); table j is built exactly as
+// g1_scalar_mul builds it, on its own Z_T,j.  The mixed additions need every entry affine on ONE curve y^2 = x^3 + 4 Z^6, so the
+// backward pass of table j starts its mu chain from f_j = prod_(l != j) Z_T,l instead of from 1: all tables land on Z = prod_j Z_T,j
+// without an inversion, and the end of the loop multiplies by that Z once.  Per table this costs 14 products for Z_T,j ahead of the
+// backward pass and 8 for entries 16 and 1, which the single table leaves as they are.
+// A term at infinity (or not on the curve: the kernel poisons the lane) takes part with all digits 0 and Z_T,j = 1.
+// Exceptional lanes: with several terms the accumulator meets +-T_j[d] for RELATED inputs too (Q = +-P, Q = 2P, Q = phi(P), products that
+// cancel to infinity), not only for torsion points.  Every such case leaves Jacobian Z = 0 (Z3 = Z1 H with H = 0; no point has order 2, so
+// a doubling never does), Z = 0 is absorbing, and a degenerate table has Z_T,j = 0: the one test at the end still suffices, and the lane
+// recomputes its K products with g1_scalar_mul_complete and adds them with the complete formulas.
+// The pads of entries 1..7 of each record carry Z_T,j as in the single table, those of entries 8..12 the ten biased digit words of the term
+// between the table passes (a loop over the terms, so the table code exists once per kernel; the main loop holds all 2K x 5 words in registers).
+C12381_HD void tab_store_kb(int32_t* lane_tab, const uint32_t (&kb0)[5], const uint32_t (&kb1)[5]) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { d2 t; t.v[0] = (int32_t)kb0[j]; t.v[1] = (int32_t)kb1[j]; *reinterpret_cast<d2*>(lane_tab + (NL / 2 + j) * G1_ENT_DWORDS + 42) = t; }
+}
+C12381_HD void tab_load_kb(uint32_t (&kb0)[5], uint32_t (&kb1)[5], const int32_t* lane_tab) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { const d2 t = *reinterpret_cast<const d2*>(lane_tab + (NL / 2 + j) * G1_ENT_DWORDS + 42); kb0[j] = (uint32_t)t.v[0]; kb1[j] = (uint32_t)t.v[1]; }
+}
+// tab_store_rec that leaves the record's two pad dwords as they are
+C12381_HD void tab_store_rec_keep_pads(int32_t* ent, const fp& a, const fp& b, const fp& c, double vb_cap) {
+    (void)vb_cap;
+    C12381_BOUNDS(for (const fp* e : {&a, &b, &c}) { if (e->vb > vb_cap) bounds_fail("tab_store_rec value bound", e->vb, vb_cap);
+                                                      if (e->lb > G1_REC_LB) bounds_fail("tab_store_rec limb bound", e->lb, G1_REC_LB); })
+    int32_t w[G1_ENT_DWORDS];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) { w[i] = a.l[i]; w[NL + i] = b.l[i]; w[2 * NL + i] = c.l[i]; }
+    q4* dst = reinterpret_cast<q4*>(ent);
+#pragma unroll
+    for (int i = 0; i < G1_ENT_DWORDS / 4 - 1; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; dst[i] = t; }
+    d2 t; t.v[0] = w[40]; t.v[1] = w[41];
+    *reinterpret_cast<d2*>(ent + 40) = t;
+}
+
+// `in(j, px, py, inf, k)` hands out term j: the affine point, whether it counts as infinity, the scalar words.  It is called again for
+// the terms of an exceptional lane, so the inputs do not stay in registers across the loop.  Returns true for a lane that took the
+// complete path.
+template <int K, class In>
+C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
+    static_assert(K >= 1 && K <= 4, "terms per lane");
+    fp beta;
+    fp_set_const(beta, FP_BETA_A);
+#pragma unroll 1
+    for (int t = 0; t < K; ++t) {                               // digits, forward co-Z pass and Z_T,t of every term
+        int32_t* tab = lane_tab + t * G1_TAB_DWORDS;
+        fp px, py;
+        bool p_is_inf;
+        uint32_t k[8], k0[4], k1[4], kb0[5], kb1[5];
+        in(t, px, py, p_is_inf, k);
+        scalar_mod_r(k);
+        scalar_glv_split(k0, k1, k);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { k0[i] = p_is_inf ? 0u : k0[i]; k1[i] = p_is_inf ? 0u : k1[i]; }
+        glv_bias(kb0, k0);
+        glv_bias(kb1, k1);
+        fp x1, y1, xj, yj, xn, yn, h, hn, bx, zrun, zt, y2, one;
+        g1j_dblu(xj, yj, x1, y1, px, py);                       // 2P and P on Z_2 = 2y
+#pragma unroll 1
+        for (int j = 2; j < G1_TAB; ++j) {
+            g1j_zaddu(xn, yn, x1, y1, h, xj, yj);               // (j+1)P and P on Z_(j+1) = Z_j h_j
+            fp_norm1(hn, h);
+            tab_store_rec(tab + (j - 1) * G1_ENT_DWORDS, xj, yj, hn, 32.0);
+            if (j == 2) zrun = hn; else fp_mul(zrun, zrun, hn);    // wave-uniform
+            xj = xn; yj = yn;
+        }
+        fp_mul(bx, xj, beta);
+        tab_store_rec(tab + (G1_TAB - 1) * G1_ENT_DWORDS, xj, yj, bx, 4.0);
+        fp_mul(bx, x1, beta);
+        tab_store_rec(tab, x1, y1, bx, 4.0);
+        fp_raw_dbl(y2, py);
+        fp_mul(zt, zrun, y2);                                   // Z_T = Z_2 h_2 ... h_15
+        fp_one(one);
+        fp_select(zt, p_is_inf, one, zt);
+        tab_store_zt(tab, zt);
+        tab_store_kb(tab, kb0, kb1);
+    }
+#pragma unroll 1
+    for (int t = 0; t < K; ++t) {                               // backward passes onto the common Z
+        int32_t* tab = lane_tab + t * G1_TAB_DWORDS;
+        fp mu, m2, m3, x, y, h, bx;
+        if (K > 1) {
+            bool first = true;
+#pragma unroll 1
+            for (int l = 0; l < K; ++l) {                       // f_t = prod_(l != t) Z_T,l (wave-uniform control flow)
+                if (l == t) continue;
+                tab_load_zt(h, lane_tab + l * G1_TAB_DWORDS);
+                if (first) mu = h; else fp_mul(mu, mu, h);
+                first = false;
+            }
+            fp_sqr(m2, mu);
+            fp_mul(m3, m2, mu);
+#pragma unroll 1
+            for (int e = 0; e < 2; ++e) {                       // entries 1 and 16 are on Z_T,t already
+                int32_t* ent = tab + (e == 0 ? 0 : G1_TAB - 1) * G1_ENT_DWORDS;
+                tab_load_rec(x, y, bx, ent, 4.0);
+                fp_mul(x, x, m2);
+                fp_mul(y, y, m3);
+                fp_mul(bx, bx, m2);
+                tab_store_rec_keep_pads(ent, x, y, bx, 4.0);
+            }
+        }
+#pragma unroll 1
+        for (int j = G1_TAB - 1; j >= 2; --j) {                 // entry j times mu_j^2, mu_j^3 with mu_j = f_t h_j ... h_15
+            int32_t* ent = tab + (j - 1) * G1_ENT_DWORDS;
+            tab_load_rec(x, y, h, ent, 32.0);
+            if (K == 1 && j == G1_TAB - 1) mu = h; else fp_mul(mu, mu, h);
+            fp_sqr(m2, mu);
+            fp_mul(m3, m2, mu);
+            fp_mul(x, x, m2);
+            fp_mul(y, y, m3);
+            fp_mul(bx, x, beta);
+            tab_store_rec_keep_pads(ent, x, y, bx, 4.0);
+        }
+    }
+
+    uint32_t kb[2 * K][5];
+#pragma unroll
+    for (int t = 0; t < K; ++t) tab_load_kb(kb[2 * t], kb[2 * t + 1], lane_tab + t * G1_TAB_DWORDS);
+    // One loop over the windows and, inside it, one over the terms whose body is the two additions of g1_scalar_mul's window: the code
+    // of a window is as long as the single loop's whatever K is.  The digit words rotate by one term per pass (2 x 5 moves per term
+    // against two additions), so the term at work is always rows 0 and 1 and no row is indexed by the term counter.
+    // As in g1_scalar_mul, the record of an addition is requested one operation ahead: a window's first before its doublings, every
+    // other one before the addition in front of its own.  The accumulator starts at infinity (acc_inf; its coordinates are then
+    // placeholders that every formula accepts) and the top window has no doublings.
+    g1j a;
+    fp_one(a.x); a.y = a.x; a.z = a.x;
+    bool acc_inf = true;
+#pragma unroll 1
+    for (int w = G1_WINDOWS - 1; w >= 0; --w) {
+        fp x0, y0, x1, y1;
+        int d0 = glv_digit(kb[0], w);
+        tab_load_xy(x0, y0, g1_digit_entry(lane_tab, d0));
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);               // the loads stay in front of the doublings
+#endif
+        if (w < G1_WINDOWS - 1) {                        // wave-uniform
+            g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); g1j_dbl(a);
+            if (G1_WIN == 5) g1j_dbl(a);
+        }
+        const int32_t* tab = lane_tab;
+#pragma unroll 1
+        for (int t = 0; t < K; ++t) {
+            const int d1 = glv_digit(kb[1], w);
+            tab_load_ybx(y1, x1, g1_digit_entry(tab, d1));
+#if defined(__HIP_DEVICE_COMPILE__)
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+            g1j_add_digit(a, acc_inf, x0, y0, d0, false);
+            if (K > 1) {
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    const uint32_t r0 = kb[0][i], r1 = kb[1][i];
+#pragma unroll
+                    for (int j = 0; j + 2 < 2 * K; ++j) kb[j][i] = kb[j + 2][i];
+                    kb[2 * K - 2][i] = r0; kb[2 * K - 1][i] = r1;
+                }
+                tab += G1_TAB_DWORDS;
+                if (t + 1 < K) {                         // wave-uniform
+                    d0 = glv_digit(kb[0], w);
+                    tab_load_xy(x0, y0, g1_digit_entry(tab, d0));
+#if defined(__HIP_DEVICE_COMPILE__)
+                    __builtin_amdgcn_sched_barrier(0);
+#endif
+                }
+            }
+            g1j_add_digit(a, acc_inf, x1, y1, d1, true);
+        }
+    }
+
+    // back to E and to homogeneous coordinates: (X Z : Y : Z^3) with Z = Z_acc prod_j Z_T,j
+    fp zc, z, z2;
+    tab_load_zt(zc, lane_tab);
+#pragma unroll 1
+    for (int t = 1; t < K; ++t) {
+        tab_load_zt(z, lane_tab + t * G1_TAB_DWORDS);
+        fp_mul(zc, zc, z);
+    }
+    fp_mul(z, a.z, zc);
+    const bool inf = acc_inf;                            // every digit of every term was 0
+    const bool exc = !inf && fp_is_zero(z);
+    fp_sqr(z2, z);
+    fp_mul(acc.x, a.x, z);
+    acc.y = a.y;
+    fp_mul(acc.z, z2, z);
+    {
+        g1p o;
+        g1_set_inf(o);
+        fp_select(acc.x, inf, o.x, acc.x); fp_select(acc.y, inf, o.y, acc.y); fp_select(acc.z, inf, o.z, acc.z);
+    }
+    if (exc) {
+#pragma unroll 1
+        for (int t = 0; t < K; ++t) {
+            fp px, py;
+            bool p_is_inf;
+            uint32_t k[8];
+            in(t, px, py, p_is_inf, k);
+            g1p term, n;
+            g1_scalar_mul_complete(term, px, py, p_is_inf, k, lane_tab);
+            g1_norm1(n, term);
+            if (t == 0) { acc = n; continue; }
+            g1_add(acc, n);
+            g1_norm1(n, acc);
+            acc = n;
+        }
+    }
+    return exc;
+}
 // k mod r < x^2, i.e. k div x^2 == 0: the lanes that owe g1_glv_small_scalar_term (evaluated by a separate, almost always
 // empty fix-up kernel so that the main loop's register allocation does not pay for the rare branch)
 C12381_HD bool scalar_below_x2(const uint32_t (&kin)[8]) {

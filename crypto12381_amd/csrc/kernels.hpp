@@ -1,5 +1,6 @@
 // Kernel entry points of the backend, one translation unit per family so the families compile in parallel:
 //   k_g1.hip     Fp hooks, G1 scalar multiplication / addition / finish / tree sum, MSM stages, G1 decompression
+//   k_g1sum.hip  per-lane sums of K G1 products under one doubling chain (K co-Z tables on one common Z)
 //   k_g2gt.hip   G2 scalar multiplication (one lane per point) / addition / finish / decompression, one-lane pairing kernels, GT arithmetic
 //   k_g2h.hip    G2 scalar multiplication with two lanes per point (half an Fp2 element per lane)
 //   k_pair3.hip  three-lanes-per-pairing Miller loop + final exponentiation
@@ -34,6 +35,11 @@ constexpr int G1_OCC = 2, MSM_OCC = 2, G2H_OCC = 2;
 __global__ void __launch_bounds__(BLOCK, 2) fp_op_kernel(int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 __global__ void __launch_bounds__(BLOCK, 2) fp_mulchain_kernel(size_t n, int iters, const uint8_t* a, const uint8_t* b, uint8_t* out);
 __global__ void __launch_bounds__(BLOCK, G1_OCC) g1_mul_kernel(size_t n, const uint8_t* pts, size_t pt_stride, const uint8_t* scalars, int32_t* tab, int32_t* proj, size_t proj_stride, size_t proj_off, int* bad_flag, const int32_t* skip_if, int small_term);
+// k_g1sum.hip: out[i] = sum_(j < K) [k_(j col + i)]P_(j col + i), K = 2, 3, 4 terms per lane (one term is g1_mul_kernel); tab holds K records per lane
+constexpr int G1_MUL_SUM_MAX = 4;
+__global__ void __launch_bounds__(BLOCK, G1_OCC) g1_mul_sum2_kernel(size_t n, const uint8_t* pts, const uint8_t* scalars, size_t col, int32_t* tab, int32_t* proj, size_t proj_stride, size_t proj_off, int* bad_flag, int small_term);
+__global__ void __launch_bounds__(BLOCK, G1_OCC) g1_mul_sum3_kernel(size_t n, const uint8_t* pts, const uint8_t* scalars, size_t col, int32_t* tab, int32_t* proj, size_t proj_stride, size_t proj_off, int* bad_flag, int small_term);
+__global__ void __launch_bounds__(BLOCK, G1_OCC) g1_mul_sum4_kernel(size_t n, const uint8_t* pts, const uint8_t* scalars, size_t col, int32_t* tab, int32_t* proj, size_t proj_stride, size_t proj_off, int* bad_flag, int small_term);
 __global__ void __launch_bounds__(BLOCK, 2) g1_rsub_kernel(size_t n, int32_t* acc, size_t acc_stride, const int32_t* other, size_t other_stride, size_t other_off, const int32_t* run_if);
 __global__ void __launch_bounds__(BLOCK, 2) g1_add_kernel(size_t n, const uint8_t* a, const uint8_t* b, int32_t* proj, size_t proj_stride, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) g1_finish_kernel(size_t n, const int32_t* proj, size_t stride, int32_t* pref, uint8_t* out, int fmt, size_t T);

@@ -127,6 +127,27 @@ int c12381_g1_mul_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* pts96, con
 #define C12381_F_COMPRESSED_IN 4u
 int c12381_g1_mul_batch_flags(c12381_ctx* ctx, size_t n, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out, int out_fmt, unsigned flags);
 int c12381_g1_mul_batch_flags_dev(c12381_ctx* ctx, size_t n, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out, int out_fmt, unsigned flags);
+/* out[i] = sum_(j < k) scalars[j n + i] * pts[j n + i]: a product of k powers PER LANE under one doubling chain — the shape of the
+ * Schnorr-type equations that end the reference's proof checks (examples/bbs04/src/bbs.cpp:70-75 u^sa * T1^-c, examples/AC-rps/src/
+ * verify.cpp:16, examples/MHAC-bbs/src/verify_pres.cpp:43) and of the header layer's fused g^x * h^y (double_multiply,
+ * g1_point.hpp:317-353 -> src/miracl_core_interface.cpp:179-182 -> ECP_mul2; Π[n] walks its range in such pairs, g1_point.hpp:391-401).
+ * pts / scalars are argument-major arrays of k n records as in c12381_pair_product_batch; 1 <= k <= C12381_G1_MUL_SUM_MAX; out_fmt = 49 or 96.
+ * The value of every lane is multiply(point1&, const big&) on each term (PAIR_G1mul: scalar mod r, GLV form, with the [r]phi(P) term of
+ * k mod r < x^2) followed by add(point1&, point1&), for EVERY curve point and every 256-bit scalar — the contract of c12381_g1_mul_batch
+ * and c12381_g1_msm; k = 1 returns the bytes of c12381_g1_mul_batch_flags.  For points of G1 this equals double_multiply / ECP_mul2 and
+ * the header-level Π; off the subgroup the two differ because ECP_mul2 forms the true multiples [k_i mod r]P_i where this entry goes
+ * through multiply()'s GLV form: that case stays with c12381_g1_sum_of_products.
+ * The k tables of a lane share one accumulator: 125 doublings per lane instead of 125 k, one projective result and one affine
+ * conversion.  The loop's additions are incomplete; a lane that meets an exceptional one recomputes its k products with the complete
+ * formulas.  No lane of independent random points does, but lanes built from RELATED points (Q = +-P, Q = 2P, Q = phi(P), a product
+ * that cancels to infinity) and from points of small order do: such a batch is correct and runs at the complete path's speed.
+ * Status: a point that is not on the curve makes its lane 0xff and the call return C12381_E_POINT, the other lanes are unaffected;
+ * n = 0 returns C12381_OK and touches nothing.  flags: C12381_F_IN_SUBGROUP (see c12381_g1_mul_batch_flags);
+ * C12381_F_COMPRESSED_IN and every other flag are refused (C12381_E_ARG), as are k outside its range, a bad out_fmt and null pointers.
+ * Workspace: k table records of 2816 B per lane of a launch, at most 2.95 GB for any n (launches of 4, 2, 2 machine rounds for k = 2, 3, 4). */
+#define C12381_G1_MUL_SUM_MAX 4
+int c12381_g1_mul_sum_batch(c12381_ctx* ctx, size_t n, int k, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out, int out_fmt, unsigned flags);
+int c12381_g1_mul_sum_batch_dev(c12381_ctx* ctx, size_t n, int k, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out, int out_fmt, unsigned flags);
 /* out[i] = a[i] + b[i].  Batched add(point1&, point1&) (:129-132 -> ECP_add). */
 int c12381_g1_add_batch(c12381_ctx* ctx, size_t n, const uint8_t* a96, const uint8_t* b96, uint8_t* out, int out_fmt);
 /* out = sum_i scalars[i] * pts[i]  (the reference's Π[n](g[i]^x[i]), g1_point.hpp:371-404, and
