@@ -8,8 +8,8 @@
 // data-dependent branch and no wavefront divergence (P+P, P+(-P), infinity operands and
 // zero digits all go through the same instruction stream) — for the MSM, the additions and the fallback; the batched scalar
 // multiplication runs Jacobian formulas over a co-Z affine table (g1_scalar_mul).  GLV: k = k0 + k1*x^2 with
-// [x^2](x,y) = (beta*x, -y), so both 128-bit halves share ONE table of 8 multiples of P (signed
-// 4-bit windows) that lives in HBM as one contiguous 1408-byte record per lane.
+// [x^2](x,y) = (beta*x, -y), so both 128-bit halves share ONE table of 16 multiples of P (signed
+// 5-bit windows) that lives in HBM as one contiguous 2816-byte record per lane.
 #pragma once
 #include "fp.hpp"
 
@@ -20,6 +20,13 @@ struct g1p { fp x, y, z; };      // (X:Y:Z), infinity = (0:1:0)
 C12381_HD void g1_set_inf(g1p& p) { fp_zero(p.x); fp_one(p.y); fp_zero(p.z); }
 C12381_HD bool g1_is_inf(const g1p& p) { return fp_is_zero(p.z); }
 C12381_HD void g1_norm1(g1p& r, const g1p& p) { fp_norm1(r.x, p.x); fp_norm1(r.y, p.y); fp_norm1(r.z, p.z); }
+C12381_HD void g1_norm1(g1p& p) { g1_norm1(p, p); }
+// r = c ? a : b, the same instruction stream for both
+C12381_HD void g1_select(g1p& r, bool c, const g1p& a, const g1p& b) { fp_select(r.x, c, a.x, b.x); fp_select(r.y, c, a.y, b.y); fp_select(r.z, c, a.z, b.z); }
+// The result of a lane whose input was rejected: Z = 0 like the point at infinity, but X = 1 (Montgomery) where infinity has X = 0.  The
+// kernels that write projective results set it, the finish kernel (k_g1.hip) tells the two apart with g1_is_invalid.
+C12381_HD void g1_set_invalid(g1p& p) { fp_one(p.x); fp_zero(p.y); fp_zero(p.z); }
+C12381_HD bool g1_is_invalid(const g1p& p) { return fp_is_zero(p.z) && !fp_is_zero(p.x); }
 
 // P = 2P.  6M + 2S with 7 reductions (Y3 is a lazily reduced sum of two products).
 // Operand limb bound: <= 2^29.
@@ -278,74 +285,115 @@ C12381_HD void soa_load_g1(g1p& p, const int32_t* base, size_t stride, size_t id
 }
 
 // ------------------------------------------------------------------ per-lane window table
-// Signed 5-bit windows: entries 1..16 of multiples of P (4-bit: 1..8), each entry X|Y|Z = 42 dwords padded to 44 (176 B,
+// Signed 5-bit windows: entries 1..16 of multiples of P, each entry X|Y|Z = 42 dwords padded to 44 (176 B,
 // eleven 16-byte accesses).  A lane's whole table is one contiguous 2816-byte record, so a gather of one
 // entry touches 176 consecutive bytes of HBM instead of 42 scattered dwords (the limb-major layout of the
 // first version moved ~16x the algorithmic bytes: profiles/r01_pmc_summary_before_table_fix.txt).
-// Per scalar multiplication: 8 + 125 doublings and 7 + 52 additions (4-bit windows: 4 + 128 and 3 + 66).
-constexpr int G1_WIN = 5;                               // 4 or 5; A/B on MI355X (profiles/r02_ab_g1_window5.txt): 5 is 3.5 % faster
-static_assert(G1_WIN == 4 || G1_WIN == 5, "window width");
-constexpr int G1_TAB = 1 << (G1_WIN - 1);              // entries 1..8 (1..16)
-constexpr int G1_WINDOWS = G1_WIN == 4 ? 33 : 26;      // 4: 32 biased nibbles + the carry nibble; 5: 26 biased fields cover 130 bits
+// Per scalar multiplication: 8 + 125 doublings and 7 + 52 additions.
+constexpr int G1_WIN = 5;                               // against 4-bit windows on MI355X (profiles/r02_ab_g1_window5.txt): 3.5 % faster
+constexpr int G1_TAB = 1 << (G1_WIN - 1);              // entries 1..16
+constexpr int G1_WINDOWS = 26;                          // 26 biased fields cover 130 bits
 constexpr int G1_ENT_DWORDS = 44;
-constexpr int G1_TAB_DWORDS = G1_TAB * G1_ENT_DWORDS;  // 352 dwords = 1408 B per lane (5-bit windows: 2816 B)
+constexpr int G1_TAB_DWORDS = G1_TAB * G1_ENT_DWORDS;  // 704 dwords = 2816 B per lane
 struct alignas(16) q4 { int32_t v[4]; };
+struct alignas(8) d2 { int32_t v[2]; };
 
-C12381_HD void tab_store_g1(int32_t* ent, const g1p& p) {
+// 16-byte words [Q0, Q0 + NQ) of a record between memory and dwords [4 Q0, 4 (Q0 + NQ)) of w.  P = pointer to q4, in whatever address
+// space the caller knows the record to live in.
+template <int Q0, int NQ, class P>
+C12381_HD void rec_store_q4(P dst, const int32_t* w) {
+#pragma unroll
+    for (int i = Q0; i < Q0 + NQ; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; dst[i] = t; }
+}
+template <int Q0, int NQ, class P>
+C12381_HD void rec_load_q4(int32_t* w, P src) {
+#pragma unroll
+    for (int i = Q0; i < Q0 + NQ; ++i) { q4 t = src[i]; w[4 * i] = t.v[0]; w[4 * i + 1] = t.v[1]; w[4 * i + 2] = t.v[2]; w[4 * i + 3] = t.v[3]; }
+}
+
+// A table record holds three fields: X | Y | Z of the complete path, x | y | beta x (or X_j | Y_j | h_j while the table is built) of the
+// co-Z path.  Stores write the two pad dwords as zero, or (KEEP_PADS) leave them as they are: the co-Z tables keep Z_T and digit words there.
+constexpr double G1_REC_LB = 268435456.0 + 8.0;
+template <bool KEEP_PADS = false>
+C12381_HD void tab_store_fields(int32_t* ent, const fp& a, const fp& b, const fp& c) {
     int32_t w[G1_ENT_DWORDS];
 #pragma unroll
-    for (int i = 0; i < NL; ++i) { w[i] = p.x.l[i]; w[NL + i] = p.y.l[i]; w[2 * NL + i] = p.z.l[i]; }
+    for (int i = 0; i < NL; ++i) { w[i] = a.l[i]; w[NL + i] = b.l[i]; w[2 * NL + i] = c.l[i]; }
     w[42] = 0; w[43] = 0;
-    q4* dst = reinterpret_cast<q4*>(ent);
-#pragma unroll
-    for (int i = 0; i < G1_ENT_DWORDS / 4; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; dst[i] = t; }
+    rec_store_q4<0, G1_ENT_DWORDS / 4 - (KEEP_PADS ? 1 : 0)>(reinterpret_cast<q4*>(ent), w);
+    if (KEEP_PADS) { d2 t; t.v[0] = w[40]; t.v[1] = w[41]; *reinterpret_cast<d2*>(ent + 40) = t; }
 }
-C12381_HD void tab_load_g1(g1p& p, const int32_t* ent) {
+template <bool KEEP_PADS = false>
+C12381_HD void tab_store_rec(int32_t* ent, const fp& a, const fp& b, const fp& c, double vb_cap) {
+    (void)vb_cap;
+    C12381_BOUNDS(for (const fp* e : {&a, &b, &c}) { if (e->vb > vb_cap) bounds_fail("tab_store_rec value bound", e->vb, vb_cap);
+                                                      if (e->lb > G1_REC_LB) bounds_fail("tab_store_rec limb bound", e->lb, G1_REC_LB); })
+    tab_store_fields<KEEP_PADS>(ent, a, b, c);
+}
+// dwords [4 q0, 4 q0 + 4 nq) of a record into w
+template <int Q0, int NQ>
+C12381_HD void tab_load_q4(int32_t (&w)[G1_ENT_DWORDS], const int32_t* ent) { rec_load_q4<Q0, NQ>(w, reinterpret_cast<const q4*>(ent)); }
+C12381_HD void rec_field(fp& a, const int32_t (&w)[G1_ENT_DWORDS], int off, double vb_cap) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) a.l[i] = w[off + i];
+    (void)vb_cap;
+    C12381_BOUNDS(a.lb = G1_REC_LB; a.vb = vb_cap; check_actual(a, "rec_field");)
+}
+C12381_HD void tab_load_rec(fp& a, fp& b, fp& c, const int32_t* ent, double vb_cap) {
     int32_t w[G1_ENT_DWORDS];
-    const q4* src = reinterpret_cast<const q4*>(ent);
-#pragma unroll
-    for (int i = 0; i < G1_ENT_DWORDS / 4; ++i) { q4 t = src[i]; w[4 * i] = t.v[0]; w[4 * i + 1] = t.v[1]; w[4 * i + 2] = t.v[2]; w[4 * i + 3] = t.v[3]; }
-#pragma unroll
-    for (int i = 0; i < NL; ++i) { p.x.l[i] = w[i]; p.y.l[i] = w[NL + i]; p.z.l[i] = w[2 * NL + i]; }
-    C12381_BOUNDS(p.x.lb = p.y.lb = p.z.lb = 268435456.0 + 8.0; p.x.vb = p.y.vb = p.z.vb = 4.0;
-                  check_actual(p.x, "tab_load_g1"); check_actual(p.y, "tab_load_g1"); check_actual(p.z, "tab_load_g1");)
+    tab_load_q4<0, G1_ENT_DWORDS / 4>(w, ent);
+    rec_field(a, w, 0, vb_cap); rec_field(b, w, NL, vb_cap); rec_field(c, w, 2 * NL, vb_cap);
 }
-// signed digit of window w of k' = k + 0x888...8 (32 nibbles): d = nibble - 8 in [-8, 7]; window 32 is the
-// carry nibble (0 or 1, no bias).  Sum_w d_w 16^w = k.
-// 5-bit windows: k' = k + sum_w 16 * 32^w (w < 26; k < 2^128, so k' < 2^130 and there is no carry window):
-// d = field - 16 in [-16, 15].
+// a projective point as a record (the complete path, the MSM's buckets, g2h.hpp)
+C12381_HD void tab_store_g1(int32_t* ent, const g1p& p) { tab_store_fields(ent, p.x, p.y, p.z); }
+C12381_HD void tab_load_g1(g1p& p, const int32_t* ent) { tab_load_rec(p.x, p.y, p.z, ent, 4.0); }
+
+// 5-bit windows of k' = k + sum_w 16 * 32^w (w < 26; k < 2^128, so k' < 2^130 and there is no carry window): the signed digit of window w
+// is d = field - 16 in [-16, 15], and Sum_w d_w 32^w = k.
 constexpr uint32_t glv_bias_word5(int i) {
     uint32_t v = 0;
     for (int w = 0; w < 26; ++w) { const int bit = 5 * w + 4; if ((bit >> 5) == i) v |= 1u << (bit & 31); }
     return v;
 }
 C12381_HD int glv_digit(const uint32_t (&kb)[5], int w) {
-    if (G1_WIN == 4) {
-        const int nib = (int)((kb[w >> 3] >> ((w & 7) * 4)) & 15u);
-        return w == 32 ? nib : nib - 8;
-    }
     const int bit = 5 * w, word = bit >> 5, sh = bit & 31;
     uint32_t v = kb[word] >> sh;
     if (sh > 27) v |= kb[word + 1] << (32 - sh);
     return (int)(v & 31u) - 16;
 }
 C12381_HD void glv_bias(uint32_t (&kb)[5], const uint32_t (&k)[4]) {
+    constexpr uint32_t B[5] = {glv_bias_word5(0), glv_bias_word5(1), glv_bias_word5(2), glv_bias_word5(3), glv_bias_word5(4)};
     uint64_t c = 0;
-    if (G1_WIN == 4) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { c += (uint64_t)k[i] + 0x88888888u; kb[i] = (uint32_t)c; c >>= 32; }
-        kb[4] = (uint32_t)c;
-    } else {
-        constexpr uint32_t B[5] = {glv_bias_word5(0), glv_bias_word5(1), glv_bias_word5(2), glv_bias_word5(3), glv_bias_word5(4)};
+    for (int i = 0; i < 4; ++i) { c += (uint64_t)k[i] + B[i]; kb[i] = (uint32_t)c; c >>= 32; }
+    kb[4] = (uint32_t)c + B[4];
+}
+// scalar words (any value < 2^256) -> the biased digit strings of the two GLV halves of k mod r.  `zero` (a term that takes no part:
+// g1_scalar_mul_sum) replaces both halves by 0, i.e. every digit by 0.
+C12381_HD void glv_scalar_digits(uint32_t (&kb0)[5], uint32_t (&kb1)[5], const uint32_t (&kin)[8], bool zero = false) {
+    uint32_t k[8], k0[4], k1[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { c += (uint64_t)k[i] + B[i]; kb[i] = (uint32_t)c; c >>= 32; }
-        kb[4] = (uint32_t)c + B[4];
-    }
+    for (int i = 0; i < 8; ++i) k[i] = kin[i];
+    scalar_mod_r(k);
+    scalar_glv_split(k0, k1, k);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { k0[i] = zero ? 0u : k0[i]; k1[i] = zero ? 0u : k1[i]; }
+    glv_bias(kb0, k0);
+    glv_bias(kb1, k1);
 }
 // the table record a digit selects (|d| = 0 reads entry 1 and is replaced by the point at infinity afterwards)
 C12381_HD const int32_t* g1_digit_entry(const int32_t* lane_tab, int d) {
     const int mag = d < 0 ? -d : d;
     return lane_tab + ((mag == 0 ? 1 : mag) - 1) * G1_ENT_DWORDS;
+}
+// (round 4, profiles/r04_ab_g1_prefetch.txt) In the window loops the record of an addition is requested one operation ahead — a window's
+// first before its doublings, every other one before the addition in front of its own — instead of at the head of the addition that needs
+// it, where the whole latency of the gather (a 176-byte record somewhere in a slab of gigabytes) was exposed twice per window.  This fence
+// keeps the request there: nothing is scheduled across it.
+C12381_HD void g1_sched_fence() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
 }
 // q = sign(d) * T[|d|], or its image under the endomorphism; d == 0 gives the point at infinity (same instruction stream)
 C12381_HD void g1_digit_fix(g1p& r, g1p q, int d, bool endo);
@@ -356,12 +404,12 @@ C12381_HD void g1_digit_point(g1p& r, const int32_t* lane_tab, int d, bool endo)
 }
 C12381_HD void g1_digit_fix(g1p& r, g1p q, int d, bool endo) {
     const int mag = d < 0 ? -d : d;
-    fp ny, zero, one;
+    fp ny;
+    g1p inf;
     fp_neg(ny, q.y);
     fp_select(q.y, d < 0, ny, q.y);
-    fp_zero(zero); fp_one(one);
-    const bool isz = mag == 0;
-    fp_select(q.x, isz, zero, q.x); fp_select(q.y, isz, one, q.y); fp_select(q.z, isz, zero, q.z);
+    g1_set_inf(inf);
+    g1_select(q, mag == 0, inf, q);
     C12381_BOUNDS(q.x.lb = q.y.lb = q.z.lb = 268435456.0 + 8.0;)
     if (endo) g1_endo_x2(r, q); else r = q;          // compile-time constant at every call site
 }
@@ -421,14 +469,8 @@ C12381_HDN void g1_glv_small_scalar_term(g1p& acc, const g1p& base) {
 // record (G1_TAB_DWORDS).  Out of line: g1_scalar_mul falls back to it for the rare lanes its incomplete formulas cannot serve, and
 // the main loop's register allocation does not pay for the second copy.
 C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, bool p_is_inf, const uint32_t (&kin)[8], int32_t* lane_tab) {
-    uint32_t k[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k[i] = kin[i];
-    scalar_mod_r(k);
-    uint32_t k0[4], k1[4], kb0[5], kb1[5];
-    scalar_glv_split(k0, k1, k);
-    glv_bias(kb0, k0);
-    glv_bias(kb1, k1);
+    uint32_t kb0[5], kb1[5];
+    glv_scalar_digits(kb0, kb1, kin);
 
     // table T[j] = j*P, j = 1..G1_TAB, stored normalised (limb bound 2^28 + slack)
     g1p base, t;
@@ -436,19 +478,13 @@ C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, boo
     {   // infinity input: use (0:1:0) as the base so every multiple is infinity
         g1p inf;
         g1_set_inf(inf);
-        fp_select(base.x, p_is_inf, inf.x, base.x);
-        fp_select(base.y, p_is_inf, inf.y, base.y);
-        fp_select(base.z, p_is_inf, inf.z, base.z);
+        g1_select(base, p_is_inf, inf, base);
     }
     tab_store_g1(lane_tab, base);                               // T[1]
     t = base;
     g1_dbl(t);
-    {
-        g1p n;
-        g1_norm1(n, t);
-        tab_store_g1(lane_tab + G1_ENT_DWORDS, n);              // T[2]
-        t = n;
-    }
+    g1_norm1(t);
+    tab_store_g1(lane_tab + G1_ENT_DWORDS, t);                  // T[2]
     // even multiples by doubling the entry half as large (8 products + 7 reductions against 12 + 9 for an addition; the entry comes
     // back from the lane's own record), odd ones by adding P to the previous entry: 8 doublings + 7 additions for 16 entries
 #pragma unroll 1
@@ -459,48 +495,33 @@ C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, boo
         } else {
             g1_add(t, base);
         }
-        g1p n;
-        g1_norm1(n, t);
-        tab_store_g1(lane_tab + (j - 1) * G1_ENT_DWORDS, n);
-        t = n;
+        g1_norm1(t);
+        tab_store_g1(lane_tab + (j - 1) * G1_ENT_DWORDS, t);
     }
 
     // the top window starts the accumulator with its first digit's entry (an addition to the point at infinity would compute the same
     // point): 51 + 7 additions in all
     g1_digit_point(acc, lane_tab, glv_digit(kb0, G1_WINDOWS - 1), false);
-    {
-        g1p n;
-        g1_norm1(n, acc);
-        acc = n;
-    }
+    g1_norm1(acc);
     g1_add_digit(acc, lane_tab, glv_digit(kb1, G1_WINDOWS - 1), true);
-    // (round 4, profiles/r04_ab_g1_prefetch.txt) the record of an addition is requested one operation ahead — the first digit's before the window's
-    // doublings (44 registers across them), the second digit's before the first addition — instead of at the head of the addition that needs
-    // it, where the whole latency of the gather (a 176-byte record somewhere in a slab of gigabytes) was exposed twice per window.
+    // records requested one operation ahead (g1_sched_fence): 44 registers across the doublings
 #pragma unroll 1
     for (int w = G1_WINDOWS - 2; w >= 0; --w) {
-#if defined(__HIP_DEVICE_COMPILE__)
         const int d0 = glv_digit(kb0, w), d1 = glv_digit(kb1, w);
         g1p q0, q1, e;
         tab_load_g1(q0, g1_digit_entry(lane_tab, d0));
-        __builtin_amdgcn_sched_barrier(0);               // the loads stay in front of the doublings
+        g1_sched_fence();                                // the loads stay in front of the doublings
         // a loop, not G1_WIN copies: this function is called, and a loop body beyond the reach of s_cbranch (+-128 KiB) gets long
         // branches whose expansion (ROCm 7.2 clang) takes s[30:31], the return address, so the call never came back and the lane
         // ran wild (an illegal memory access on the first fallback lane)
 #pragma unroll 1
         for (int j = 0; j < G1_WIN; ++j) g1_dbl(acc);
         tab_load_g1(q1, g1_digit_entry(lane_tab, d1));
-        __builtin_amdgcn_sched_barrier(0);
+        g1_sched_fence();
         g1_digit_fix(e, q0, d0, false);
         g1_add(acc, e);
         g1_digit_fix(e, q1, d1, true);
         g1_add(acc, e);
-#else
-        g1_dbl(acc); g1_dbl(acc); g1_dbl(acc); g1_dbl(acc);
-        if (G1_WIN == 5) g1_dbl(acc);
-        g1_add_digit(acc, lane_tab, glv_digit(kb0, w), false);
-        g1_add_digit(acc, lane_tab, glv_digit(kb1, w), true);
-#endif
     }
 }
 
@@ -508,37 +529,6 @@ C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, boo
 // Record of entry j: x | y | beta x | 2 pad dwords (44 dwords, as the complete path's X | Y | Z).  The pads of entries 1..7 carry the
 // 14 limbs of Z_T, the shared Z of the table.  While the table is built, entry j holds (X_j, Y_j, h_j) instead: jP on its own Z and the
 // factor h_j that carries Z_j to Z_(j+1).
-constexpr double G1_REC_LB = 268435456.0 + 8.0;
-C12381_HD void tab_store_rec(int32_t* ent, const fp& a, const fp& b, const fp& c, double vb_cap) {
-    (void)vb_cap;
-    C12381_BOUNDS(for (const fp* e : {&a, &b, &c}) { if (e->vb > vb_cap) bounds_fail("tab_store_rec value bound", e->vb, vb_cap);
-                                                      if (e->lb > G1_REC_LB) bounds_fail("tab_store_rec limb bound", e->lb, G1_REC_LB); })
-    int32_t w[G1_ENT_DWORDS];
-#pragma unroll
-    for (int i = 0; i < NL; ++i) { w[i] = a.l[i]; w[NL + i] = b.l[i]; w[2 * NL + i] = c.l[i]; }
-    w[42] = 0; w[43] = 0;
-    q4* dst = reinterpret_cast<q4*>(ent);
-#pragma unroll
-    for (int i = 0; i < G1_ENT_DWORDS / 4; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; dst[i] = t; }
-}
-// dwords [4 q0, 4 q0 + 4 nq) of a record into w
-template <int Q0, int NQ>
-C12381_HD void tab_load_q4(int32_t (&w)[G1_ENT_DWORDS], const int32_t* ent) {
-    const q4* src = reinterpret_cast<const q4*>(ent);
-#pragma unroll
-    for (int i = Q0; i < Q0 + NQ; ++i) { q4 t = src[i]; w[4 * i] = t.v[0]; w[4 * i + 1] = t.v[1]; w[4 * i + 2] = t.v[2]; w[4 * i + 3] = t.v[3]; }
-}
-C12381_HD void rec_field(fp& a, const int32_t (&w)[G1_ENT_DWORDS], int off, double vb_cap) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) a.l[i] = w[off + i];
-    (void)vb_cap;
-    C12381_BOUNDS(a.lb = G1_REC_LB; a.vb = vb_cap; check_actual(a, "rec_field");)
-}
-C12381_HD void tab_load_rec(fp& a, fp& b, fp& c, const int32_t* ent, double vb_cap) {
-    int32_t w[G1_ENT_DWORDS];
-    tab_load_q4<0, G1_ENT_DWORDS / 4>(w, ent);
-    rec_field(a, w, 0, vb_cap); rec_field(b, w, NL, vb_cap); rec_field(c, w, 2 * NL, vb_cap);
-}
 // what an addition reads: x and y (dwords 0..27), or y and beta x (dwords 12..43)
 C12381_HD void tab_load_xy(fp& x, fp& y, const int32_t* ent) {
     int32_t w[G1_ENT_DWORDS];
@@ -550,7 +540,9 @@ C12381_HD void tab_load_ybx(fp& y, fp& bx, const int32_t* ent) {
     tab_load_q4<3, 8>(w, ent);
     rec_field(y, w, NL, 4.0); rec_field(bx, w, 2 * NL, 4.0);
 }
-struct alignas(8) d2 { int32_t v[2]; };
+// the same for the entry digit d selects, requested here and not later (g1_sched_fence)
+C12381_HD void tab_fetch_xy(fp& x, fp& y, const int32_t* lane_tab, int d) { tab_load_xy(x, y, g1_digit_entry(lane_tab, d)); g1_sched_fence(); }
+C12381_HD void tab_fetch_ybx(fp& y, fp& bx, const int32_t* lane_tab, int d) { tab_load_ybx(y, bx, g1_digit_entry(lane_tab, d)); g1_sched_fence(); }
 C12381_HD void tab_store_zt(int32_t* lane_tab, const fp& zt) {
 #pragma unroll
     for (int j = 0; j < NL / 2; ++j) { d2 t; t.v[0] = zt.l[2 * j]; t.v[1] = zt.l[2 * j + 1]; *reinterpret_cast<d2*>(lane_tab + j * G1_ENT_DWORDS + 42) = t; }
@@ -560,6 +552,42 @@ C12381_HD void tab_load_zt(fp& zt, const int32_t* lane_tab) {
     for (int j = 0; j < NL / 2; ++j) { const d2 t = *reinterpret_cast<const d2*>(lane_tab + j * G1_ENT_DWORDS + 42); zt.l[2 * j] = t.v[0]; zt.l[2 * j + 1] = t.v[1]; }
     C12381_BOUNDS(zt.lb = G1_REC_LB; zt.vb = 4.0; check_actual(zt, "tab_load_zt");)
 }
+
+// Forward co-Z pass over the table of P = (px, py): DBLU and fourteen ZADDUs.  Leaves entries 2..15 as (X_j, Y_j, h_j), entries 1 and 16
+// finished on Z_16 = Z_T = 2y h_2 ... h_15.  `on_h(j, h_j)` sees every factor as it is stored.
+template <class OnH>
+C12381_HD void g1_coz_forward(int32_t* lane_tab, const fp& px, const fp& py, const fp& beta, const OnH& on_h) {
+    fp x1, y1, xj, yj, xn, yn, h, hn, bx;
+    g1j_dblu(xj, yj, x1, y1, px, py);                           // 2P and P on Z_2 = 2y
+#pragma unroll 1
+    for (int j = 2; j < G1_TAB; ++j) {
+        g1j_zaddu(xn, yn, x1, y1, h, xj, yj);                   // (j+1)P and P on Z_(j+1) = Z_j h_j
+        fp_norm1(hn, h);
+        tab_store_rec(lane_tab + (j - 1) * G1_ENT_DWORDS, xj, yj, hn, 32.0);
+        on_h(j, hn);
+        xj = xn; yj = yn;
+    }
+    fp_mul(bx, xj, beta);
+    tab_store_rec(lane_tab + (G1_TAB - 1) * G1_ENT_DWORDS, xj, yj, bx, 4.0);
+    fp_mul(bx, x1, beta);
+    tab_store_rec(lane_tab, x1, y1, bx, 4.0);
+}
+// One step of the backward pass: mu <- mu h_j (mu = h_j where the chain starts: `first`, wave-uniform), and entry j = (X_j, Y_j, h_j)
+// becomes (mu^2 X_j, mu^3 Y_j, beta mu^2 X_j), the point on Z_j mu.
+template <bool KEEP_PADS>
+C12381_HD void g1_coz_backward(int32_t* ent, fp& mu, bool first, const fp& beta) {
+    fp m2, m3, x, y, h, bx;
+    tab_load_rec(x, y, h, ent, 32.0);
+    if (first) mu = h; else fp_mul(mu, mu, h);
+    fp_sqr(m2, mu);
+    fp_mul(m3, m2, mu);
+    fp_mul(x, x, m2);
+    fp_mul(y, y, m3);
+    fp_mul(bx, x, beta);
+    tab_store_rec<KEEP_PADS>(ent, x, y, bx, 4.0);
+}
+// the G1_WIN doublings of one window
+C12381_HD void g1j_dbl_window(g1j& a) { g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); }
 
 // acc += sign(d) T[|d|], or its image (beta x, -y) under the endomorphism, given the entry's x (beta x) and y.  d = 0 keeps acc (the
 // addition with entry 1 is computed and dropped); an accumulator at infinity (acc_inf) takes the looked-up point with Z = 1.
@@ -575,6 +603,21 @@ C12381_HD void g1j_add_digit(g1j& acc, bool& acc_inf, const fp& x, const fp& y, 
     fp_select(acc.x, keep, acc.x, r.x); fp_select(acc.y, keep, acc.y, r.y); fp_select(acc.z, keep, acc.z, r.z);
     acc_inf = acc_inf && keep;
 }
+// The end of the loop: a on E' (Z = zc, the shared Z of the table or tables) back to E and to homogeneous coordinates, (X Z : Y : Z^3) with
+// Z = Z_a zc; the point at infinity where `inf`.  Returns true for an exceptional lane: Z = 0 mod p although the result is not infinity.
+C12381_HD bool g1_coz_finish(g1p& acc, const g1j& a, const fp& zc, bool inf) {
+    fp z, z2;
+    fp_mul(z, a.z, zc);
+    const bool exc = !inf && fp_is_zero(z);
+    fp_sqr(z2, z);
+    fp_mul(acc.x, a.x, z);
+    acc.y = a.y;
+    fp_mul(acc.z, z2, z);
+    g1p o;
+    g1_set_inf(o);
+    g1_select(acc, inf, o, acc);
+    return exc;
+}
 
 // [k]P for an AFFINE input point (x, y) or infinity, result in homogeneous coordinates.  `lane_tab` = this lane's table record
 // (G1_TAB_DWORDS).  Returns true for a lane that took the complete path.
@@ -586,46 +629,16 @@ C12381_HD void g1j_add_digit(g1j& acc, bool& acc_inf, const fp& x, const fp& y, 
 // and Z = 0 survives every later step.  So one test at the end suffices: a lane whose final Z is 0 mod p while the accumulator is
 // not the point at infinity recomputes its product with g1_scalar_mul_complete.  No lane of a random subgroup batch does.
 C12381_HD bool g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf, const uint32_t (&kin)[8], int32_t* lane_tab) {
-    uint32_t k[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k[i] = kin[i];
-    scalar_mod_r(k);
-    uint32_t k0[4], k1[4], kb0[5], kb1[5];
-    scalar_glv_split(k0, k1, k);
-    glv_bias(kb0, k0);
-    glv_bias(kb1, k1);
+    uint32_t kb0[5], kb1[5];
+    glv_scalar_digits(kb0, kb1, kin);
 
     fp beta;
     fp_set_const(beta, FP_BETA_A);
-    {   // table T[j] = jP, j = 1..16: forward co-Z pass
-        fp x1, y1, xj, yj, xn, yn, h, hn, bx;
-        g1j_dblu(xj, yj, x1, y1, px, py);                       // 2P and P on Z_2 = 2y
+    g1_coz_forward(lane_tab, px, py, beta, [](int, const fp&) {});
+    {   // backward pass: entry j times mu_j^2, mu_j^3 with mu_j = h_j h_(j+1) ... h_15 = Z_T / Z_j; the chain ends in Z_T for free
+        fp mu, zt, y2;
 #pragma unroll 1
-        for (int j = 2; j < G1_TAB; ++j) {
-            g1j_zaddu(xn, yn, x1, y1, h, xj, yj);               // (j+1)P and P on Z_(j+1) = Z_j h_j
-            fp_norm1(hn, h);
-            tab_store_rec(lane_tab + (j - 1) * G1_ENT_DWORDS, xj, yj, hn, 32.0);
-            xj = xn; yj = yn;
-        }
-        fp_mul(bx, xj, beta);
-        tab_store_rec(lane_tab + (G1_TAB - 1) * G1_ENT_DWORDS, xj, yj, bx, 4.0);
-        fp_mul(bx, x1, beta);
-        tab_store_rec(lane_tab, x1, y1, bx, 4.0);
-    }
-    {   // backward pass: entry j times mu_j^2, mu_j^3 with mu_j = h_j h_(j+1) ... h_15 = Z_T / Z_j
-        fp mu, m2, m3, x, y, h, bx, zt, y2;
-#pragma unroll 1
-        for (int j = G1_TAB - 1; j >= 2; --j) {
-            int32_t* ent = lane_tab + (j - 1) * G1_ENT_DWORDS;
-            tab_load_rec(x, y, h, ent, 32.0);
-            if (j == G1_TAB - 1) mu = h; else fp_mul(mu, mu, h);   // wave-uniform
-            fp_sqr(m2, mu);
-            fp_mul(m3, m2, mu);
-            fp_mul(x, x, m2);
-            fp_mul(y, y, m3);
-            fp_mul(bx, x, beta);
-            tab_store_rec(ent, x, y, bx, 4.0);
-        }
+        for (int j = G1_TAB - 1; j >= 2; --j) g1_coz_backward<false>(lane_tab + (j - 1) * G1_ENT_DWORDS, mu, j == G1_TAB - 1, beta);
         fp_raw_dbl(y2, py);
         fp_mul(zt, mu, y2);                                     // Z_T = Z_2 mu_2
         tab_store_zt(lane_tab, zt);
@@ -647,41 +660,20 @@ C12381_HD bool g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf
         tab_load_ybx(y, x, g1_digit_entry(lane_tab, d1));
         g1j_add_digit(a, acc_inf, x, y, d1, true);
     }
-    // the record of an addition is requested one operation ahead (round 4): the first digit's before the window's doublings, the second
-    // digit's before the first addition
 #pragma unroll 1
     for (int w = G1_WINDOWS - 2; w >= 0; --w) {
         const int d0 = glv_digit(kb0, w), d1 = glv_digit(kb1, w);
         fp x0, y0, x1, y1;
-        tab_load_xy(x0, y0, g1_digit_entry(lane_tab, d0));
-#if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_sched_barrier(0);               // the loads stay in front of the doublings
-#endif
-        g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); g1j_dbl(a);
-        if (G1_WIN == 5) g1j_dbl(a);
-        tab_load_ybx(y1, x1, g1_digit_entry(lane_tab, d1));
-#if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_sched_barrier(0);
-#endif
+        tab_fetch_xy(x0, y0, lane_tab, d0);
+        g1j_dbl_window(a);
+        tab_fetch_ybx(y1, x1, lane_tab, d1);
         g1j_add_digit(a, acc_inf, x0, y0, d0, false);
         g1j_add_digit(a, acc_inf, x1, y1, d1, true);
     }
 
-    // back to E and to homogeneous coordinates: (X Z : Y : Z^3) with Z = Z_acc Z_T
-    fp zt, z, z2;
+    fp zt;
     tab_load_zt(zt, lane_tab);
-    fp_mul(z, a.z, zt);
-    const bool inf = acc_inf || p_is_inf;
-    const bool exc = !inf && fp_is_zero(z);
-    fp_sqr(z2, z);
-    fp_mul(acc.x, a.x, z);
-    acc.y = a.y;
-    fp_mul(acc.z, z2, z);
-    {
-        g1p o;
-        g1_set_inf(o);
-        fp_select(acc.x, inf, o.x, acc.x); fp_select(acc.y, inf, o.y, acc.y); fp_select(acc.z, inf, o.z, acc.z);
-    }
+    const bool exc = g1_coz_finish(acc, a, zt, acc_inf || p_is_inf);
     if (exc) g1_scalar_mul_complete(acc, px, py, p_is_inf, kin, lane_tab);
     return exc;
 }
@@ -707,20 +699,6 @@ C12381_HD void tab_load_kb(uint32_t (&kb0)[5], uint32_t (&kb1)[5], const int32_t
 #pragma unroll
     for (int j = 0; j < 5; ++j) { const d2 t = *reinterpret_cast<const d2*>(lane_tab + (NL / 2 + j) * G1_ENT_DWORDS + 42); kb0[j] = (uint32_t)t.v[0]; kb1[j] = (uint32_t)t.v[1]; }
 }
-// tab_store_rec that leaves the record's two pad dwords as they are
-C12381_HD void tab_store_rec_keep_pads(int32_t* ent, const fp& a, const fp& b, const fp& c, double vb_cap) {
-    (void)vb_cap;
-    C12381_BOUNDS(for (const fp* e : {&a, &b, &c}) { if (e->vb > vb_cap) bounds_fail("tab_store_rec value bound", e->vb, vb_cap);
-                                                      if (e->lb > G1_REC_LB) bounds_fail("tab_store_rec limb bound", e->lb, G1_REC_LB); })
-    int32_t w[G1_ENT_DWORDS];
-#pragma unroll
-    for (int i = 0; i < NL; ++i) { w[i] = a.l[i]; w[NL + i] = b.l[i]; w[2 * NL + i] = c.l[i]; }
-    q4* dst = reinterpret_cast<q4*>(ent);
-#pragma unroll
-    for (int i = 0; i < G1_ENT_DWORDS / 4 - 1; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; dst[i] = t; }
-    d2 t; t.v[0] = w[40]; t.v[1] = w[41];
-    *reinterpret_cast<d2*>(ent + 40) = t;
-}
 
 // `in(j, px, py, inf, k)` hands out term j: the affine point, whether it counts as infinity, the scalar words.  It is called again for
 // the terms of an exceptional lane, so the inputs do not stay in registers across the loop.  Returns true for a lane that took the
@@ -735,28 +713,12 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
         int32_t* tab = lane_tab + t * G1_TAB_DWORDS;
         fp px, py;
         bool p_is_inf;
-        uint32_t k[8], k0[4], k1[4], kb0[5], kb1[5];
+        uint32_t k[8], kb0[5], kb1[5];
         in(t, px, py, p_is_inf, k);
-        scalar_mod_r(k);
-        scalar_glv_split(k0, k1, k);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { k0[i] = p_is_inf ? 0u : k0[i]; k1[i] = p_is_inf ? 0u : k1[i]; }
-        glv_bias(kb0, k0);
-        glv_bias(kb1, k1);
-        fp x1, y1, xj, yj, xn, yn, h, hn, bx, zrun, zt, y2, one;
-        g1j_dblu(xj, yj, x1, y1, px, py);                       // 2P and P on Z_2 = 2y
-#pragma unroll 1
-        for (int j = 2; j < G1_TAB; ++j) {
-            g1j_zaddu(xn, yn, x1, y1, h, xj, yj);               // (j+1)P and P on Z_(j+1) = Z_j h_j
-            fp_norm1(hn, h);
-            tab_store_rec(tab + (j - 1) * G1_ENT_DWORDS, xj, yj, hn, 32.0);
-            if (j == 2) zrun = hn; else fp_mul(zrun, zrun, hn);    // wave-uniform
-            xj = xn; yj = yn;
-        }
-        fp_mul(bx, xj, beta);
-        tab_store_rec(tab + (G1_TAB - 1) * G1_ENT_DWORDS, xj, yj, bx, 4.0);
-        fp_mul(bx, x1, beta);
-        tab_store_rec(tab, x1, y1, bx, 4.0);
+        glv_scalar_digits(kb0, kb1, k, p_is_inf);
+        // Z_T,t is needed before any backward pass, so it is multiplied up here: 14 products
+        fp zrun, zt, y2, one;
+        g1_coz_forward(tab, px, py, beta, [&](int j, const fp& hn) { if (j == 2) zrun = hn; else fp_mul(zrun, zrun, hn); });   // wave-uniform
         fp_raw_dbl(y2, py);
         fp_mul(zt, zrun, y2);                                   // Z_T = Z_2 h_2 ... h_15
         fp_one(one);
@@ -767,8 +729,9 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
 #pragma unroll 1
     for (int t = 0; t < K; ++t) {                               // backward passes onto the common Z
         int32_t* tab = lane_tab + t * G1_TAB_DWORDS;
-        fp mu, m2, m3, x, y, h, bx;
+        fp mu;
         if (K > 1) {
+            fp m2, m3, x, y, h, bx;
             bool first = true;
 #pragma unroll 1
             for (int l = 0; l < K; ++l) {                       // f_t = prod_(l != t) Z_T,l (wave-uniform control flow)
@@ -786,21 +749,12 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
                 fp_mul(x, x, m2);
                 fp_mul(y, y, m3);
                 fp_mul(bx, bx, m2);
-                tab_store_rec_keep_pads(ent, x, y, bx, 4.0);
+                tab_store_rec<true>(ent, x, y, bx, 4.0);
             }
         }
+        // entry j times mu_j^2, mu_j^3 with mu_j = f_t h_j ... h_15; a single table (K = 1) has f_t = 1 and starts its chain as g1_scalar_mul does
 #pragma unroll 1
-        for (int j = G1_TAB - 1; j >= 2; --j) {                 // entry j times mu_j^2, mu_j^3 with mu_j = f_t h_j ... h_15
-            int32_t* ent = tab + (j - 1) * G1_ENT_DWORDS;
-            tab_load_rec(x, y, h, ent, 32.0);
-            if (K == 1 && j == G1_TAB - 1) mu = h; else fp_mul(mu, mu, h);
-            fp_sqr(m2, mu);
-            fp_mul(m3, m2, mu);
-            fp_mul(x, x, m2);
-            fp_mul(y, y, m3);
-            fp_mul(bx, x, beta);
-            tab_store_rec_keep_pads(ent, x, y, bx, 4.0);
-        }
+        for (int j = G1_TAB - 1; j >= 2; --j) g1_coz_backward<true>(tab + (j - 1) * G1_ENT_DWORDS, mu, K == 1 && j == G1_TAB - 1, beta);
     }
 
     uint32_t kb[2 * K][5];
@@ -809,9 +763,8 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
     // One loop over the windows and, inside it, one over the terms whose body is the two additions of g1_scalar_mul's window: the code
     // of a window is as long as the single loop's whatever K is.  The digit words rotate by one term per pass (2 x 5 moves per term
     // against two additions), so the term at work is always rows 0 and 1 and no row is indexed by the term counter.
-    // As in g1_scalar_mul, the record of an addition is requested one operation ahead: a window's first before its doublings, every
-    // other one before the addition in front of its own.  The accumulator starts at infinity (acc_inf; its coordinates are then
-    // placeholders that every formula accepts) and the top window has no doublings.
+    // The accumulator starts at infinity (acc_inf; its coordinates are then placeholders that every formula accepts) and the top
+    // window has no doublings.
     g1j a;
     fp_one(a.x); a.y = a.x; a.z = a.x;
     bool acc_inf = true;
@@ -819,22 +772,13 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
     for (int w = G1_WINDOWS - 1; w >= 0; --w) {
         fp x0, y0, x1, y1;
         int d0 = glv_digit(kb[0], w);
-        tab_load_xy(x0, y0, g1_digit_entry(lane_tab, d0));
-#if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_sched_barrier(0);               // the loads stay in front of the doublings
-#endif
-        if (w < G1_WINDOWS - 1) {                        // wave-uniform
-            g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); g1j_dbl(a);
-            if (G1_WIN == 5) g1j_dbl(a);
-        }
+        tab_fetch_xy(x0, y0, lane_tab, d0);
+        if (w < G1_WINDOWS - 1) g1j_dbl_window(a);       // wave-uniform
         const int32_t* tab = lane_tab;
 #pragma unroll 1
         for (int t = 0; t < K; ++t) {
             const int d1 = glv_digit(kb[1], w);
-            tab_load_ybx(y1, x1, g1_digit_entry(tab, d1));
-#if defined(__HIP_DEVICE_COMPILE__)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            tab_fetch_ybx(y1, x1, tab, d1);
             g1j_add_digit(a, acc_inf, x0, y0, d0, false);
             if (K > 1) {
 #pragma unroll
@@ -847,36 +791,21 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
                 tab += G1_TAB_DWORDS;
                 if (t + 1 < K) {                         // wave-uniform
                     d0 = glv_digit(kb[0], w);
-                    tab_load_xy(x0, y0, g1_digit_entry(tab, d0));
-#if defined(__HIP_DEVICE_COMPILE__)
-                    __builtin_amdgcn_sched_barrier(0);
-#endif
+                    tab_fetch_xy(x0, y0, tab, d0);
                 }
             }
             g1j_add_digit(a, acc_inf, x1, y1, d1, true);
         }
     }
 
-    // back to E and to homogeneous coordinates: (X Z : Y : Z^3) with Z = Z_acc prod_j Z_T,j
-    fp zc, z, z2;
+    fp zc, z;
     tab_load_zt(zc, lane_tab);
 #pragma unroll 1
-    for (int t = 1; t < K; ++t) {
+    for (int t = 1; t < K; ++t) {                               // the common Z = prod_j Z_T,j
         tab_load_zt(z, lane_tab + t * G1_TAB_DWORDS);
         fp_mul(zc, zc, z);
     }
-    fp_mul(z, a.z, zc);
-    const bool inf = acc_inf;                            // every digit of every term was 0
-    const bool exc = !inf && fp_is_zero(z);
-    fp_sqr(z2, z);
-    fp_mul(acc.x, a.x, z);
-    acc.y = a.y;
-    fp_mul(acc.z, z2, z);
-    {
-        g1p o;
-        g1_set_inf(o);
-        fp_select(acc.x, inf, o.x, acc.x); fp_select(acc.y, inf, o.y, acc.y); fp_select(acc.z, inf, o.z, acc.z);
-    }
+    const bool exc = g1_coz_finish(acc, a, zc, acc_inf);        // acc_inf: every digit of every term was 0
     if (exc) {
 #pragma unroll 1
         for (int t = 0; t < K; ++t) {
@@ -889,8 +818,7 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
             g1_norm1(n, term);
             if (t == 0) { acc = n; continue; }
             g1_add(acc, n);
-            g1_norm1(n, acc);
-            acc = n;
+            g1_norm1(acc);
         }
     }
     return exc;

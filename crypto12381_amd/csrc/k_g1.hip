@@ -80,8 +80,7 @@ __global__ void __launch_bounds__(BLOCK, G1_OCC) g1_mul_kernel(size_t n, const u
     }
     if (!ok) {
         *bad_flag = 1;
-        // poison: Z = 0, X = 1 marks "invalid" for the finish kernel
-        fp_one(acc.x); fp_zero(acc.y); fp_zero(acc.z);
+        g1_set_invalid(acc);
     }
     g1p o;
     g1_norm1(o, acc);
@@ -92,18 +91,14 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_add_kernel(size_t n, const uint8_
                                                        int* bad_flag) {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    g1p p, q, inf_pt;
+    g1p p, q;
     bool ia, oa, ib, ob;
-    g1_parse96(p.x, p.y, ia, oa, a + 96 * i); fp_one(p.z);
-    g1_parse96(q.x, q.y, ib, ob, b + 96 * i); fp_one(q.z);
-    g1_set_inf(inf_pt);
-    fp_select(p.x, ia, inf_pt.x, p.x); fp_select(p.y, ia, inf_pt.y, p.y); fp_select(p.z, ia, inf_pt.z, p.z);
-    fp_select(q.x, ib, inf_pt.x, q.x); fp_select(q.y, ib, inf_pt.y, q.y); fp_select(q.z, ib, inf_pt.z, q.z);
+    g1_parse96_proj(p, ia, oa, a + 96 * i);
+    g1_parse96_proj(q, ib, ob, b + 96 * i);
     g1_add(p, q);
-    if (!(oa && ob)) { *bad_flag = 1; fp_one(p.x); fp_zero(p.y); fp_zero(p.z); }
-    g1p o;
-    g1_norm1(o, p);
-    soa_store_g1(proj, proj_stride, i, o);
+    if (!(oa && ob)) { *bad_flag = 1; g1_set_invalid(p); }
+    g1_norm1(p);
+    soa_store_g1(proj, proj_stride, i, p);
 }
 
 // Simultaneous inversion (Montgomery's trick) + affine + encode.  Lane t owns elements
@@ -135,7 +130,7 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_finish_kernel(size_t n, const int
         soa_load_g1(p, proj, stride, e);
         fp one, prev, zinv;
         fp_one(one);
-        const bool inf = fp_is_zero(p.z);
+        const bool inf = fp_is_zero(p.z), invalid = g1_is_invalid(p);    // the point at infinity, or the mark of a rejected input
         fp_select(p.z, inf, one, p.z);
         if (e >= T + t) soa_load_fp(prev, pref, stride, e - T); else prev = one;
         fp_mul(zinv, inv, prev);
@@ -145,8 +140,6 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_finish_kernel(size_t n, const int
         uint32_t rx[12], ry[12];
         fp_to_raw48(rx, ax);
         uint8_t* o = out + (size_t)fmt * e;
-        // X = 1 (Montgomery), Z = 0 marks an invalid input; X = 0, Z = 0 is the point at infinity
-        const bool invalid = inf && !fp_is_zero(p.x);
         if (fmt == 96) {
             fp_to_raw48(ry, ay);
             if (inf) {
@@ -184,9 +177,7 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_reduce_kernel(size_t n, const int
         g1p q;
         soa_load_g1(q, in, in_stride, i);
         g1_add(acc, q);
-        g1p nn;
-        g1_norm1(nn, acc);
-        acc = nn;
+        g1_norm1(acc);
     }
     soa_store_g1(outp, out_stride, j, acc);
 }
@@ -196,14 +187,10 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_reduce_kernel(size_t n, const int
 __global__ void __launch_bounds__(BLOCK, 2) g1_lift_kernel(size_t n, const uint8_t* pts, int32_t* proj, size_t stride, int* bad_flag) {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    g1p p, inf_pt, o;
+    g1p p, o;
     bool inf, ok;
-    g1_parse96(p.x, p.y, inf, ok, pts + 96 * i);
-    fp_one(p.z);
-    g1_set_inf(inf_pt);
-    const bool drop = inf || !ok;
-    fp_select(p.x, drop, inf_pt.x, p.x); fp_select(p.y, drop, inf_pt.y, p.y); fp_select(p.z, drop, inf_pt.z, p.z);
-    if (!ok) *bad_flag = 1;
+    g1_parse96_proj(p, inf, ok, pts + 96 * i);
+    if (!ok) { *bad_flag = 1; g1_set_inf(p); }
     g1_norm1(o, p);
     soa_store_g1(proj, stride, i, o);
 }
@@ -216,10 +203,9 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_mul_plain_kernel(size_t n, const 
     if (i >= n) return;
     g1p base, acc, inf_pt;
     bool inf, ok;
-    g1_parse96(base.x, base.y, inf, ok, pts + 96 * i);
-    fp_one(base.z);
+    g1_parse96_proj(base, inf, ok, pts + 96 * i);
     g1_set_inf(inf_pt);
-    if (inf || !ok) base = inf_pt;
+    if (!ok) base = inf_pt;
     uint32_t raw[8], k[8];
     load_raw32(raw, scalars + 32 * i);
     scalar_from_raw32(k, raw);
@@ -231,11 +217,11 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_mul_plain_kernel(size_t n, const 
         g1p nn, q;
         g1_norm1(nn, acc);
         const bool bit = ((k[b >> 5] >> (b & 31)) & 1u) != 0;
-        fp_select(q.x, bit, base.x, inf_pt.x); fp_select(q.y, bit, base.y, inf_pt.y); fp_select(q.z, bit, base.z, inf_pt.z);
+        g1_select(q, bit, base, inf_pt);
         g1_add(nn, q);
         g1_norm1(acc, nn);
     }
-    if (!ok) { *bad_flag = 1; fp_one(acc.x); fp_zero(acc.y); fp_zero(acc.z); }
+    if (!ok) { *bad_flag = 1; g1_set_invalid(acc); }
     soa_store_g1(proj, proj_stride, i, acc);
 }
 
@@ -243,11 +229,9 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_mul_plain_kernel(size_t n, const 
 __global__ void __launch_bounds__(BLOCK, 2) g1_add_const_kernel(size_t n, int32_t* proj, size_t stride, const uint8_t* pt96, int* bad_flag) {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    g1p q, inf_pt, acc;
+    g1p q, acc;
     bool inf, ok;
-    g1_parse96(q.x, q.y, inf, ok, pt96); fp_one(q.z);
-    g1_set_inf(inf_pt);
-    fp_select(q.x, inf, inf_pt.x, q.x); fp_select(q.y, inf, inf_pt.y, q.y); fp_select(q.z, inf, inf_pt.z, q.z);
+    g1_parse96_proj(q, inf, ok, pt96);
     if (!ok) *bad_flag = 1;
     soa_load_g1(acc, proj, stride, i);
     g1_add(acc, q);
@@ -352,13 +336,13 @@ __global__ void __launch_bounds__(BLOCK, MSM_OCC) msm_bucket_kernel(size_t nbk, 
     const size_t slot = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (slot >= nbk) return;
     const size_t b = order[slot];
-    g1p acc, nn;
+    g1p acc;
     const size_t l = lo[b];
     size_t h = hi[b];
     if (b == nbk - 1 && h - l <= early_max) h = l;                 // summed by msm_small_early_kernel (see msm_sizes_kernel)
     msm_bucket_one(acc, l, h - l > cap ? l + cap : h, vals, pts2);
-    g1_norm1(nn, acc);
-    tab_store_g1(bk + b * G1_ENT_DWORDS, nn);
+    g1_norm1(acc);
+    tab_store_g1(bk + b * G1_ENT_DWORDS, acc);
 }
 // partial sum of overflow segment q (entries [lo + cap + s seg, lo + cap + (s + 1) seg) of its run); the grid covers the
 // capacity of the segment list, wavefronts beyond the registered count leave at once.  The 64 segments of a wavefront are
@@ -373,7 +357,7 @@ __global__ void __launch_bounds__(BLOCK, 2) msm_overflow_kernel(const uint32_t* 
     if (q - lane >= total) return;                                 // the whole wavefront is beyond the list
     const bool valid = q < total;
     uint32_t bucket = 0xffffffffu;
-    g1p acc, nn, t, cand;
+    g1p acc, t, cand;
     g1_set_inf(acc);
     if (valid) {
         const uint2 e = seg[q];
@@ -381,19 +365,16 @@ __global__ void __launch_bounds__(BLOCK, 2) msm_overflow_kernel(const uint32_t* 
         const size_t sl = cap / 2, start = (size_t)lo[e.x] + cap + (size_t)e.y * sl, h = hi[e.x];
         msm_bucket_one(acc, start, h - start > sl ? start + sl : h, vals, pts2);
     }
-    g1_norm1(nn, acc); acc = nn;
+    g1_norm1(acc);
 #pragma unroll 1
     for (int off = 1; off < 64; off <<= 1) {
         const uint32_t ob = (uint32_t)__shfl_down((int)bucket, off, 64);
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            t.x.l[j] = __shfl_down(acc.x.l[j], off, 64); t.y.l[j] = __shfl_down(acc.y.l[j], off, 64); t.z.l[j] = __shfl_down(acc.z.l[j], off, 64);
-        }
+        g1_shfl_down(t, acc, off);
         cand = acc;
         g1_add(cand, t);
-        g1_norm1(nn, cand);
+        g1_norm1(cand);
         const bool take = lane + (uint32_t)off < 64u && ob == bucket;
-        fp_select(acc.x, take, nn.x, acc.x); fp_select(acc.y, take, nn.y, acc.y); fp_select(acc.z, take, nn.z, acc.z);
+        g1_select(acc, take, cand, acc);
     }
     const uint32_t left = (uint32_t)__shfl_up((int)bucket, 1, 64);
     if (valid && (lane == 0 || left != bucket)) tab_store_g1(part + q * G1_ENT_DWORDS, acc);
@@ -410,7 +391,7 @@ __global__ void __launch_bounds__(BLOCK, 2) msm_overflow_combine_kernel(const ui
         const uint4 e = big[q];
         const uint32_t base = e.y, end = e.y + e.z, first = (base / 64u + 1u) * 64u;
         const uint32_t heads = 1u + (end > first ? (end - 1u - first) / 64u + 1u : 0u);
-        g1p acc, t, nn;
+        g1p acc, t;
         g1_set_inf(acc);
 #pragma unroll 1
         for (uint32_t j0 = 0; j0 < heads; j0 += 64) {
@@ -419,23 +400,15 @@ __global__ void __launch_bounds__(BLOCK, 2) msm_overflow_combine_kernel(const ui
                 const uint32_t pos = j == 0 ? base : first + 64u * (j - 1u);
                 tab_load_g1(t, part + (size_t)pos * G1_ENT_DWORDS);
                 g1_add(acc, t);
-                g1_norm1(nn, acc); acc = nn;
+                g1_norm1(acc);
             }
         }
         if (lane == 0) {
             tab_load_g1(t, bk + (size_t)e.x * G1_ENT_DWORDS);
             g1_add(acc, t);
-            g1_norm1(nn, acc); acc = nn;
+            g1_norm1(acc);
         }
-#pragma unroll 1
-        for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-            for (int i = 0; i < NL; ++i) {
-                t.x.l[i] = __shfl_down(acc.x.l[i], off, 64); t.y.l[i] = __shfl_down(acc.y.l[i], off, 64); t.z.l[i] = __shfl_down(acc.z.l[i], off, 64);
-            }
-            g1_add(acc, t);
-            g1_norm1(nn, acc); acc = nn;
-        }
+        g1_wave_sum(acc);
         if (lane == 0) tab_store_g1(bk + (size_t)e.x * G1_ENT_DWORDS, acc);
     }
 }
@@ -486,18 +459,10 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_wave_reduce_kernel(size_t groups,
     if (wave >= out_groups * (size_t)W) return;                               // wave-uniform
     const size_t g = wave / (size_t)W, w = wave % (size_t)W;
     const size_t src = g * 64 + lane;
-    g1p acc, t, nn;
+    g1p acc;
     g1_set_inf(acc);
     if (src < groups) soa_load_g1(acc, in, in_stride, src * (size_t)W + w);
-#pragma unroll 1
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            t.x.l[i] = __shfl_down(acc.x.l[i], off, 64); t.y.l[i] = __shfl_down(acc.y.l[i], off, 64); t.z.l[i] = __shfl_down(acc.z.l[i], off, 64);
-        }
-        g1_add(acc, t);
-        g1_norm1(nn, acc); acc = nn;
-    }
+    g1_wave_sum(acc);
     if (lane == 0) soa_store_g1(outp, out_stride, g * (size_t)W + w, acc);
 }
 
@@ -609,7 +574,7 @@ __global__ void __launch_bounds__(64, 1) msm_small_early_kernel(const uint32_t* 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t l = lo[small_bucket], h = hi[small_bucket];
     if (h - l > early_max) { if (lane == 0) *done = 0u; return; }      // wave-uniform
-    g1p acc, t, nn;
+    g1p acc, nn;
     g1_set_inf(acc);
     if (h > l) {
 #pragma unroll 1
@@ -618,16 +583,8 @@ __global__ void __launch_bounds__(64, 1) msm_small_early_kernel(const uint32_t* 
             msm_load_pt(x, y, pts2 + (size_t)vals[j] * MSM_PT_STRIDE);
             g1_add_affine(acc, x, y);
         }
-        g1_norm1(nn, acc); acc = nn;
-#pragma unroll 1
-        for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-            for (int i = 0; i < NL; ++i) {
-                t.x.l[i] = __shfl_down(acc.x.l[i], off, 64); t.y.l[i] = __shfl_down(acc.y.l[i], off, 64); t.z.l[i] = __shfl_down(acc.z.l[i], off, 64);
-            }
-            g1_add(acc, t);
-            g1_norm1(nn, acc); acc = nn;
-        }
+        g1_norm1(acc);
+        g1_wave_sum(acc);
 #pragma unroll
         for (int i = 0; i < NL; ++i) {                                 // the sum sits in lane 0: replicate it over the first quad
             acc.x.l[i] = __shfl(acc.x.l[i], 0, 64); acc.y.l[i] = __shfl(acc.y.l[i], 0, 64); acc.z.l[i] = __shfl(acc.z.l[i], 0, 64);

@@ -9,7 +9,7 @@ using namespace c12381;
 namespace {
 
 // term j of lane i of the argument-major arrays (`col` records between two terms of a lane).  A point that is not on the curve takes
-// part as the point at infinity; the kernel poisons its lane afterwards.
+// part as the point at infinity; the kernel marks its lane invalid afterwards.
 struct g1_sum_in {
     const uint8_t* pts;
     const uint8_t* scalars;
@@ -57,7 +57,7 @@ __device__ __forceinline__ void g1_mul_sum_body(size_t n, const uint8_t* pts, co
     }
     if (!ok_all) {
         *bad_flag = 1;
-        fp_one(acc.x); fp_zero(acc.y); fp_zero(acc.z);          // Z = 0, X = 1 marks "invalid" for the finish kernel
+        g1_set_invalid(acc);
     }
     g1p o;
     g1_norm1(o, acc);

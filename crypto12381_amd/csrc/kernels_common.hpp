@@ -46,6 +46,14 @@ __device__ __forceinline__ void g1_parse96(fp& x, fp& y, bool& inf, bool& ok, co
     fp_from_raw48(x, raw); fp_from_raw48(y, raw + 12);
     ok = inf || g1_on_curve(x, y);
 }
+// the same as a projective point: (x : y : 1), or the point at infinity for the all-zero record
+__device__ __forceinline__ void g1_parse96_proj(g1p& p, bool& inf, bool& ok, const uint8_t* src) {
+    g1p inf_pt;
+    g1_parse96(p.x, p.y, inf, ok, src);
+    fp_one(p.z);
+    g1_set_inf(inf_pt);
+    g1_select(p, inf, inf_pt, p);
+}
 // The 49-byte form as the header layer reads it (g1_point.hpp:87-111 in front of ECP_fromOctet ecp_BLS12381.cpp:495-545): a leading
 // 0x00 is the point at infinity, 0x02 / 0x03 carry x and the parity of y (ECP_setx: one square root, on-curve by construction, no
 // subgroup check), every other tag is rejected (ok = false: the lane is treated like a point that is not on the curve).
@@ -66,6 +74,23 @@ __device__ __noinline__ void g1_parse49(fp& x, fp& y, bool& inf, bool& ok, const
 __device__ __forceinline__ void g1_parse_any(fp& x, fp& y, bool& inf, bool& ok, const uint8_t* pts, size_t pt_stride, size_t i) {
     if (pt_stride == 49) g1_parse49(x, y, inf, ok, pts + 49 * i);
     else g1_parse96(x, y, inf, ok, pts + pt_stride * i);
+}
+// t = the point of the lane `off` above
+__device__ __forceinline__ void g1_shfl_down(g1p& t, const g1p& p, int off) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        t.x.l[i] = __shfl_down(p.x.l[i], off, 64); t.y.l[i] = __shfl_down(p.y.l[i], off, 64); t.z.l[i] = __shfl_down(p.z.l[i], off, 64);
+    }
+}
+// sum of the (normalised) points of a wavefront in six shuffle-and-add steps; the sum arrives in lane 0
+__device__ __forceinline__ void g1_wave_sum(g1p& acc) {
+    g1p t;
+#pragma unroll 1
+    for (int off = 32; off >= 1; off >>= 1) {
+        g1_shfl_down(t, acc, off);
+        g1_add(acc, t);
+        g1_norm1(acc);
+    }
 }
 __device__ __forceinline__ void fp2_load_raw96(fp2& r, const uint8_t* p) {       // b || a
     uint32_t raw[24];

@@ -1,6 +1,7 @@
 // Calibration of the FETCH_SIZE counter for THIS kernel's access pattern: every lane reads whole 176-byte records of its own
-// 1408-byte table slab as eleven 16-byte loads (tab_load_g1, g1.hpp), record index data dependent — exactly what g1_mul_kernel
-// does 66 times per scalar multiplication.  The bytes requested are known (lanes x lookups x 176), so
+// 1408-byte table slab as eleven 16-byte loads (tab_load_g1, g1.hpp), record index data dependent — what g1_mul_kernel did 66 times
+// per scalar multiplication when this was measured (8 entries, 4-bit windows; the table has 16 entries and the loop 52 lookups of 112 or
+// 128 bytes since).  The bytes requested are known (lanes x lookups x 176), so
 //     rocprofv3 --pmc FETCH_SIZE -- ./fetch_calib
 // tells how the counter's kilobytes relate to them (MI355X_MICROARCH.md: "16-B/lane loads count half"; profiles/traffic.json
 // applied that rule to a pattern it had not been calibrated on).

@@ -69,9 +69,7 @@ C12381_HD void msm_store_pt(int32_t* dst, const fp& x, const fp& y) {
     int32_t w[MSM_PT_DWORDS];
 #pragma unroll
     for (int i = 0; i < NL; ++i) { w[i] = x.l[i]; w[NL + i] = y.l[i]; }
-    q4* d = reinterpret_cast<q4*>(dst);
-#pragma unroll
-    for (int i = 0; i < MSM_PT_DWORDS / 4; ++i) { q4 t; t.v[0] = w[4 * i]; t.v[1] = w[4 * i + 1]; t.v[2] = w[4 * i + 2]; t.v[3] = w[4 * i + 3]; d[i] = t; }
+    rec_store_q4<0, MSM_PT_DWORDS / 4>(reinterpret_cast<q4*>(dst), w);
 }
 C12381_HD void msm_load_pt(fp& x, fp& y, const int32_t* src) {
     int32_t w[MSM_PT_DWORDS];
@@ -82,8 +80,7 @@ C12381_HD void msm_load_pt(fp& x, fp& y, const int32_t* src) {
 #else
     const q4* s = reinterpret_cast<const q4*>(src);
 #endif
-#pragma unroll
-    for (int i = 0; i < MSM_PT_DWORDS / 4; ++i) { q4 t = s[i]; w[4 * i] = t.v[0]; w[4 * i + 1] = t.v[1]; w[4 * i + 2] = t.v[2]; w[4 * i + 3] = t.v[3]; }
+    rec_load_q4<0, MSM_PT_DWORDS / 4>(w, s);
 #pragma unroll
     for (int i = 0; i < NL; ++i) { x.l[i] = w[i]; y.l[i] = w[NL + i]; }
     C12381_BOUNDS(x.lb = y.lb = 268435456.0 + 8.0; x.vb = y.vb = 2.0; check_actual(x, "msm_load_pt"); check_actual(y, "msm_load_pt");)
@@ -192,12 +189,12 @@ C12381_HD void msm_wreduce_one(g1p& out, const int32_t* bk, uint32_t d0, uint32_
         if (d < nb) {                              // uniform across the wavefront except in the last chunk
             tab_load_g1(b, bk + (size_t)d * G1_ENT_DWORDS);
             g1_add(run, b);
-            g1p nn; g1_norm1(nn, run); run = nn;
+            g1_norm1(run);
             g1_add(acc, run);
-            g1_norm1(nn, acc); acc = nn;
+            g1_norm1(acc);
         }
     }
-    if (d0 < nb) { tab_load_g1(b, bk + (size_t)d0 * G1_ENT_DWORDS); g1_add(run, b); g1p nn; g1_norm1(nn, run); run = nn; }
+    if (d0 < nb) { tab_load_g1(b, bk + (size_t)d0 * G1_ENT_DWORDS); g1_add(run, b); g1_norm1(run); }
     // [d0] S by double-and-add (d0 < 2^16), selects instead of branches.  d0 is a multiple of the chunk length: its low bits are
     // doublings only (round 4: log2(MSM_CHUNK) additions of the point at infinity less)
     constexpr int LOW = MSM_CHUNK >= 16 ? 4 : (MSM_CHUNK >= 8 ? 3 : (MSM_CHUNK >= 4 ? 2 : (MSM_CHUNK >= 2 ? 1 : 0)));
@@ -208,7 +205,7 @@ C12381_HD void msm_wreduce_one(g1p& out, const int32_t* bk, uint32_t d0, uint32_
         g1_dbl(t);
         g1p s;
         const bool on = (d0 >> bit) & 1u;
-        fp_select(s.x, on, run.x, inf.x); fp_select(s.y, on, run.y, inf.y); fp_select(s.z, on, run.z, inf.z);
+        g1_select(s, on, run, inf);
         g1p tn; g1_norm1(tn, t);
         g1_add(tn, s);
         t = tn;
@@ -229,7 +226,7 @@ C12381_HD void msm_horner(g1p& acc, const int32_t* rw, size_t stride, int W, int
         g1_add(nn, q);
         acc = nn;
     }
-    g1p nn; g1_norm1(nn, acc); acc = nn;
+    g1_norm1(acc);
 }
 
 // the [r]phi(S) owed for S = the sum of the points whose scalar is below x^2 (bucket W << c); infinity when S is in G1

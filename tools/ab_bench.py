@@ -4,7 +4,7 @@ wall time per call over a few repetitions, and a SHA-256 of every output so that
 The variants run in child processes (one library per process), interleaved round by round (A B A B ...) so that clock drift of the box
 hits all of them alike.
 
-    python tools/ab_bench.py [--legs g1,g2,pair,miller,fexp,msm,bbs] [--reps 3] [--rounds 2] default crypto12381_amd/lib/exp/libX.so ...
+    python tools/ab_bench.py [--legs g1,g1sum,g2,pair,miller,fexp,msm,bbs] [--reps 3] [--rounds 2] default crypto12381_amd/lib/exp/libX.so ...
 
 `default` = the product library.  Prints one table; exit status 1 if any digest differs from the first variant's or any child failed
 (crash, time-out, no result line): the run stops at the first such child."""
@@ -19,7 +19,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ALL_LEGS = ["g1", "g2", "pair", "miller", "fexp", "msm", "bbs"]
+ALL_LEGS = ["g1", "g1sum", "g2", "pair", "miller", "fexp", "msm", "bbs"]
 
 
 def child(lib, legs, reps):
@@ -60,6 +60,13 @@ def child(lib, legs, reps):
         dp, dk, o = d(p1k * (n // 1024)), d(sc(2, n)), torch.empty(96 * n, dtype=torch.uint8, device=dev)
         res["g1"] = (*timeit(lambda: c.g1_mul_dev(n, dp.data_ptr(), dk.data_ptr(), o.data_ptr(), 96)), digest(o))
         del dp, dk, o
+    if "g1sum" in legs:                  # per-lane sums of k products (rows g1sum2, g1sum4): term j takes the points rotated by 37 j records
+        n = 1 << 20
+        for k in (2, 4):
+            dp = d(b"".join((p1k[96 * 37 * j:] + p1k[:96 * 37 * j]) * (n // 1024) for j in range(k)))
+            dk, o = d(b"".join(sc(20 + j, n) for j in range(k))), torch.empty(96 * n, dtype=torch.uint8, device=dev)
+            res["g1sum%d" % k] = (*timeit(lambda: c.g1_mul_sum_dev(n, k, dp.data_ptr(), dk.data_ptr(), o.data_ptr(), 96)), digest(o))
+            del dp, dk, o
     if "g2" in legs:
         n = 1 << 18
         dq, dk, o = d(q1k * (n // 1024)), d(sc(5, n)), torch.empty(192 * n, dtype=torch.uint8, device=dev)
@@ -147,7 +154,7 @@ def main():
             break
     first = a.libs[0]
     print("\n%-8s" % "leg" + "".join("%28s" % os.path.basename(l)[:26] for l in a.libs))
-    for leg in legs + (["miller"] if "fexp" in legs and "miller" not in legs else []):
+    for leg in (runs[first][0] if runs[first] else []):       # the rows the first child reported: a leg may give several, fexp brings miller along
         row = "%-8s" % leg
         for lib in a.libs:
             rs = [r[leg] for r in runs[lib] if leg in r]
