@@ -142,14 +142,20 @@ C12381_HD int fp2_sign(const fp2& x) {
 }
 // FP2_qr :446 + FP2_sqrt :460-521 (complex method) in one pass.  Returns false when the norm a^2+b^2 is a
 // non-residue (or 0); on success w is the root of sign 0, exactly as the reference returns it.
+// Contract: the reference's bytes for every u, not "a square root of u".  FP_sqrt hands back the root of sign 0, so w1 below is the
+// even one of +-sqrt(a^2 + b^2).  For b != 0 the choice is absorbed by the sign fix at the end; for a real u (b = 0, a != 0) it is
+// w1 = +-a and decides between w2 = a and w2 = 0: an even a gives the true root (sqrt(a), 0) or (0, sqrt(-a)), an odd a gives (0, 0),
+// the reference's own artefact, which g2_set_x passes on as the "point" (x, 0) with status 1.
 C12381_HDN bool fp2_sqrt(fp2& w, const fp2& u) {
-    fp n, w1, w1inv, w2, hb, half, ra, rainv, rb;
+    fp n, w1, w1inv, nw1, w2, hb, half, ra, rainv, rb;
     fp ua2, ub2;
     fp_raw_dbl(ua2, u.a);
     fp_raw_dbl(ub2, u.b);
     fp_reduce_cols(n, [&](int k, int64_t& acc) { fp_col_sqr_acc(acc, u.a, ua2, u.a, k); fp_col_sqr_acc(acc, u.b, ub2, u.b, k); });
     C12381_BOUNDS(set_lazy_bounds(n, u.a.lb * u.a.lb + u.b.lb * u.b.lb, u.a.vb * u.a.vb + u.b.vb * u.b.vb, "fp2_sqrt");)
     const bool norm_qr = fp_sqrt_progen(w1, w1inv, n);          // w1 = sqrt(a^2 + b^2)
+    fp_neg(nw1, w1);
+    fp_select(w1, fp_sign(w1) != 0, nw1, w1);                   // ... the one of sign 0 (FP_sqrt :873-876)
     fp_set_const(half, FP_HALF);
     fp_add(w2, u.a, w1);
     fp_norm1(w2, w2);

@@ -168,12 +168,15 @@ static void fp2_mul_ip(fp2* w) { fp2 t = *w; fp_sub(&w->a, &t.a, &t.b); fp_add(&
 static int fp2_sign(const fp2* w) { return fp_is_zero(&w->a) ? fp_sign(&w->b) : fp_sign(&w->a); }
 /* FP2_qr :446 */
 static int fp2_qr(const fp2* x) { fp n, t; fp_sqr(&n, &x->a); fp_sqr(&t, &x->b); fp_add(&n, &n, &t); return fp_qr(&n); }
-/* FP2_sqrt :460-521 (complex method; returns the root of sign 0 like the reference) */
+/* FP2_sqrt :460-521 (complex method; returns the root of sign 0 like the reference).  Contract: the reference's bytes for every u.
+ * FP_sqrt returns the root of sign 0, so w1 is the even one of +-sqrt(a^2 + b^2); for a real u (b = 0) that is +-a and decides between
+ * w2 = a (the true root) and w2 = 0 (the root "(0, 0)" of an odd a, which the reference returns and decoding accepts). */
 static void fp2_sqrt(fp2* w, const fp2* u) {
     fp w1, w2, w3, hb; fp2 t = *u;
     if (fp2_is_zero(&t)) { *w = t; return; }
     fp_sqr(&w1, &t.b); fp_sqr(&w2, &t.a); fp_add(&w1, &w1, &w2);
     fp_sqrt(&w1, &w1);                      /* sqrt(a^2 + b^2) */
+    if (fp_sign(&w1)) fp_neg(&w1, &w1);     /* FP_sqrt :873-876 returns the root of sign 0; for a real u this decides w2 = a or 0 */
     fp_add(&w2, &t.a, &w1); fp_div2(&w2, &w2);
     fp_div2(&hb, &t.b);
     int qr = fp_qr(&w2);

@@ -690,10 +690,13 @@ extern "C" int sim_pair2_fixed_batch(size_t n, const uint8_t* a96, const uint8_t
     int32_t* t1 = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(t1v.data()) + 15) & ~(uintptr_t)15);
     int32_t* t2 = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(t2v.data()) + 15) & ~(uintptr_t)15);
     fp2 qx, qy;
+    uint32_t rq[48];
+    load_raw(rq, w192, 48);                                   // an all-zero record is infinity, as g2_lines_table_kernel reads it
     fp2_from_bytes96(qx, w192); fp2_from_bytes96(qy, w192 + 96);
-    miller_lines_precompute(t1, qx, qy);
+    miller_lines_precompute(t1, qx, qy, raw_all_zero(rq, 48));
+    load_raw(rq, g192, 48);
     fp2_from_bytes96(qx, g192); fp2_from_bytes96(qy, g192 + 96);
-    miller_lines_precompute(t2, qx, qy);
+    miller_lines_precompute(t2, qx, qy, raw_all_zero(rq, 48));
     // a2 is only parsed for its infinity flag by pair_load: give every lane the fixed point
     std::vector<uint8_t> wrep(192 * n);
     for (size_t i = 0; i < n; ++i) std::memcpy(&wrep[192 * i], w192, 192);

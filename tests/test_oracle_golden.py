@@ -293,3 +293,78 @@ def test_port_matches_reference_on_torsion_points(oracle_port, oracle_ref):
     n0 = len(pts)
     assert [dec(out[96 * i:96 * i + 96]) for i in range(n0, n0 + 4)] == [(0, 2), (0, 2), (0, P - 2), (0, P - 2)] or \
         [dec(out[96 * i:96 * i + 96]) for i in range(n0, n0 + 4)] == [(0, P - 2), (0, P - 2), (0, 2), (0, 2)]   # x = p is x = 0; the tags differ
+
+
+def test_port_matches_reference_on_twist_edge_points(oracle_port, oracle_ref):
+    """The C restatement against the compiled reference on structured inputs of the twist (g2_twist.py): two independent points of order
+    13 and every multiple of one of them (the Miller loop passes through infinity: an addition with T = -Q, doublings of infinity, an
+    addition to infinity), points of order 23 and 2713 (no exceptional step), G2gen + T13, and x coordinates whose right-hand side is
+    real — where FP_sqrt's sign-0 root of the norm decides between the true root and (0, 0) — or purely imaginary.  Decoding under both
+    sign tags, multiplication by the edge scalars (an order-13 base puts infinity into the window table), additions, Miller values,
+    pairings, pair2 and pair_eq.  Inputs are computed here; every mismatch is collected, so a failure names all the cases that differ."""
+    import g2_twist as tw
+    assert tw.degenerate_steps(13) == [(61, tw.ADD_NEG), (60, tw.DBL_INF), (59, tw.DBL_INF), (58, tw.DBL_INF), (58, tw.ADD_INF)]
+    assert all(tw.degenerate_steps(q) == [] for q in (23, 2713, 11953, 262069)) and len(tw.miller_multiples()) == 69
+    bad = []
+    pts = tw.twist_points()
+    names = list(pts)
+    assert all(tw.on_curve(p) for p in pts.values()) and tw.ec_mul(13, pts["t13a"]) is None and tw.ec_mul(13, pts["t13b"]) is None
+    # decoding: the points' own encodings, then the real and imaginary right-hand sides (expected bytes from Python integers)
+    own = b"".join(tw.compress(pts[k]) for k in names)
+    d = oracle_ref.g2_decompress(own)
+    assert d == (b"".join(tw.enc192(pts[k]) for k in names), b"\x01" * len(names))
+    if oracle_port.g2_decompress(own) != d:
+        bad.append("decompress: the points' own encodings")
+    cases = tw.real_rhs_cases()
+    assert len(cases) == 12 and len({c[0] for c in cases}) == 12           # the four real classes exist, under both tags
+    for label, c97, want in cases:
+        r = oracle_ref.g2_decompress(c97)
+        assert r == (want, b"\x01"), label                                  # the reference's rule as g2_twist.py states it
+        if oracle_port.g2_decompress(c97) != r:
+            bad.append("decompress: " + label)
+    # the two real classes that decode to a curve point join the points below
+    for label, _, want in cases:
+        if label.startswith("real") and label.endswith("tag 2") and want[96:] != bytes(96):
+            pts[label] = tw.dec192(want)
+            assert tw.on_curve(pts[label])
+    mul_names = ["inf", "t13a", "t13b", "5*t13a", "t23", "t2713", "g+t13", "g"] + [k for k in pts if k.startswith("real")]
+    ks = tw.g2_edge_scalars() + [prng(9601, i) % (1 << 256) for i in range(4)]
+    sb = b"".join(k.to_bytes(32, "big") for k in ks)
+    for k in mul_names:
+        pb = tw.enc192(pts[k]) * len(ks)
+        for fmt in (97, 192):
+            if oracle_port.g2_mul(pb, sb, fmt, 4) != oracle_ref.g2_mul(pb, sb, fmt, 4):
+                bad.append("g2_mul %s fmt %d" % (k, fmt))
+    # additions: every ordered pair of a subset (P + P, P + (-P) = 12 T + T, with infinity), against affine arithmetic as well
+    add_names = ["inf", "t13a", "12*t13a", "2*t13a", "t13b", "t23", "g+t13", "g"]
+    a = b"".join(tw.enc192(pts[p]) for p in add_names for _ in add_names)
+    b = b"".join(tw.enc192(pts[q]) for _ in add_names for q in add_names)
+    for fmt in (97, 192):
+        if oracle_port.g2_add(a, b, fmt) != oracle_ref.g2_add(a, b, fmt):
+            bad.append("g2_add fmt %d" % fmt)
+    assert oracle_ref.g2_add(a, b, 192) == b"".join(tw.enc192(tw.ec_add(pts[p], pts[q])) for p in add_names for q in add_names)
+    # Miller values and pairings: every point with an ordinary G1 argument, and one lane with the G1 argument at infinity
+    g1 = tw.g1_ordinary(len(pts) + 1, 9602)
+    p1 = b"".join(g1[:len(pts)]) + bytes(96)
+    q2 = b"".join(tw.enc192(p) for p in pts.values()) + tw.enc192(pts["t13a"])
+    for name in ("miller", "pair"):
+        x, y = getattr(oracle_port, name)(p1, q2), getattr(oracle_ref, name)(p1, q2)
+        bad += ["%s %s" % (name, k) for i, k in enumerate(list(pts) + ["t13a, G1 infinity"]) if x[576 * i:576 * i + 576] != y[576 * i:576 * i + 576]]
+    one = oracle_ref.pair(bytes(96), bytes(192))
+    assert oracle_ref.pair(p1[-96:], q2[-192:]) == one and oracle_ref.pair(p1[:96], q2[:192]) == one
+    # pair2 / pair_eq: a degenerate point in the first slot, in the second, in both; equal and unequal sides
+    n = len(pts)
+    rot = lambda buf, w, j: buf[w * j:] + buf[:w * j]
+    a1, a2 = p1[:96 * n], q2[:192 * n]
+    b1, b2 = rot(a1, 96, 3), rot(a2, 192, 5)
+    if oracle_port.pair2(a1, a2, b1, b2) != oracle_ref.pair2(a1, a2, b1, b2):
+        bad.append("pair2")
+    e1 = a1 + a1 + a1[:96 * 4]
+    e2 = a2 + a2 + a2[:192 * 4]
+    f1 = a1 + b1 + a1[96:96 * 4] + a1[:96]
+    f2 = a2 + b2 + a2[:192 * 4]
+    eq = oracle_ref.pair_eq(e1, e2, f1, f2)
+    assert set(eq[:n]) == {1} and 0 in eq[n:]
+    if oracle_port.pair_eq(e1, e2, f1, f2) != eq:
+        bad.append("pair_eq")
+    assert bad == [], "; ".join(bad)
