@@ -129,6 +129,10 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp]
         for name in ("c12381_bbs04_open_batch", "c12381_bbs04_open_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, vp]
+        for name in ("c12381_bbs04_sign_batch", "c12381_bbs04_sign_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        for name in ("c12381_bbs04_issue_batch", "c12381_bbs04_issue_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, vp]
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -519,6 +523,33 @@ class Context:
 
     def bbs04_open_dev(self, n, gmsk_ptr, sig_ptr, out_ptr, status_ptr):
         self._ck(self.lib.c12381_bbs04_open_batch_dev(self.h, n, _p(gmsk_ptr), _p(sig_ptr), _p(out_ptr), _p(status_ptr)))
+
+    def bbs04_sign(self, gpk390: bytes, gsk97: bytes, msgs: bytes, rnd224: bytes, msg_len: int, strict: bool = True):
+        """bbs04 sign from the wire formats: gpk (390 B), member keys serialize(A, x) (97 B each), messages of msg_len bytes each and the
+        caller's randomness (alpha, beta, r_alpha, r_beta, r_x, r_delta1, r_delta2: 7 x 32 B per signature) -> (n x 435-byte signatures,
+        n status bytes: 0, or 0xff — and 435 bytes of 0xff — where the reference would terminate).  A gpk that does not decode is
+        C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise.  Not constant-time."""
+        n = len(gsk97) // 97
+        sig = ctypes.create_string_buffer(max(435 * n, 1))
+        st = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_bbs04_sign_batch(self.h, n, msg_len, _p(gpk390), _p(gsk97), _p(msgs) if msg_len else None, _p(rnd224), _p(sig),
+                                                  _p(st)), allow_point=not strict)
+        return sig.raw[:435 * n], st.raw[:n]
+
+    def bbs04_sign_dev(self, n, msg_len, gpk_ptr, gsk_ptr, msg_ptr, rnd_ptr, sig_ptr, status_ptr):
+        self._ck(self.lib.c12381_bbs04_sign_batch_dev(self.h, n, msg_len, _p(gpk_ptr), _p(gsk_ptr), _p(msg_ptr), _p(rnd_ptr), _p(sig_ptr),
+                                                      _p(status_ptr)))
+
+    def bbs04_issue(self, gpk390: bytes, gamma32: bytes, x32: bytes, strict: bool = True) -> bytes:
+        """bbs04 member keys as key_gen issues them: n x serialize(g1^inverse(gamma + x_i), x_i) (97 B each) for n 32-byte scalars x_i.
+        A gpk that does not decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise."""
+        n = len(x32) // 32
+        out = ctypes.create_string_buffer(max(97 * n, 1))
+        self._ck(self.lib.c12381_bbs04_issue_batch(self.h, n, _p(gpk390), _p(gamma32), _p(x32), _p(out)), allow_point=not strict)
+        return out.raw[:97 * n]
+
+    def bbs04_issue_dev(self, n, gpk_ptr, gamma_ptr, x_ptr, gsk_ptr):
+        self._ck(self.lib.c12381_bbs04_issue_batch_dev(self.h, n, _p(gpk_ptr), _p(gamma_ptr), _p(x_ptr), _p(gsk_ptr)))
 
     # ---- device-pointer entry points (ints = device addresses, e.g. torch tensor.data_ptr())
     def bbs_plus_sign(self, g1, h0, h, gamma32, x, r, m) -> bytes:

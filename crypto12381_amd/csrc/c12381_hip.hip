@@ -440,7 +440,7 @@ static bool msm_use_buckets(size_t n) {
 
 extern "C" {
 
-int c12381_version(void) { return (0 << 16) | 2; }
+int c12381_version(void) { return (0 << 16) | 3; }
 
 int c12381_create(int device, c12381_ctx** out) {
     if (!out) return C12381_E_ARG;
@@ -2047,6 +2047,137 @@ int c12381_bbs04_open_batch(c12381_ctx* c, size_t n, const uint8_t* gmsk_96, con
     staging s;
     if ((rc = stage(c, s, {{gmsk_96, 96}, {sig_435, 435 * n}}, {{out49, 49 * n}, {status, n}}))) return rc;
     if ((rc = c12381_bbs04_open_batch_dev(c, n, s.in[0], s.in[1], s.out[0], s.out[1]))) return rc;
+    return unstage(c, s);
+}
+
+// sign (:32-59), per signature: decode A, reduce the seven random scalars and write the scalar columns (bbs04_sign_prep_kernel,
+// bbs04_sign.hpp).  Phase 1: u^alpha, v^beta, h^(alpha + beta) through the fixed-base tables (generic kernel when a base is not a subgroup
+// point), T3 = A + h^(alpha + beta), T1..T3 as 49-byte records (wire, transcript) and 96-byte records (bases of phase 2).  Phase 2: T1^rx,
+// T2^rx, T3^rx in one variable-base launch of 3 m lanes, six fixed-base columns, the additions (bbs04_sign_combine_kernel), R3 by the
+// k = 2 fixed-G2 product, verify's transcript kernel, then c and the responses (bbs04_sign_finish_kernel).  Table slots as in verify
+// (u -> 0, v -> 1, h -> 2, g1 -> 3), so signing and verifying under one gpk share the tables.  WS_BBS04 holds, behind BBS04_PUB_BYTES and
+// per signature of a chunk, bbs04_sign_layout's 2848 + msg_len bytes; the scalar-multiplication workspace holds 9 projective points.
+struct bbs04_sign_slab { uint8_t *a49, *a96, *st_a, *sc, *t49, *t96, *r49, *p96, *gt, *tr; size_t bytes; };
+static bbs04_sign_slab bbs04_sign_layout(uint8_t* base, size_t m, size_t msg_len) {
+    bbs04_sign_slab s;
+    size_t o = BBS04_PUB_BYTES;
+    auto take = [&](uint8_t*& p, size_t bytes) { p = base ? base + o : nullptr; o = round_up(o + bytes, 256); };
+    take(s.a49, 49 * m); take(s.a96, 96 * m); take(s.st_a, m); take(s.sc, 12 * 32 * m); take(s.t49, 3 * 49 * m); take(s.t96, 3 * 96 * m);
+    take(s.r49, 4 * 49 * m); take(s.p96, 2 * 96 * m); take(s.gt, 576 * m); take(s.tr, (msg_len + 919) * m);
+    s.bytes = o;
+    return s;
+}
+// m products of one public base into column `col` of the projective workspace: the table of `slot` where the base is a subgroup point, the
+// generic kernel otherwise (each of the two launches returns at once when the other one serves the column)
+static int bbs04_fixed_column(c12381_ctx* c, size_t m, const uint8_t* base, int slot, const uint8_t* sc, size_t stride, size_t col, bool fb) {
+    const int32_t* skip = nullptr;
+    if (fb) {
+        skip = (const int32_t*)c->ws[c12381_ctx::WS_FB_G1_0 + slot];
+        hipLaunchKernelGGL(g1_fixed_eval_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, skip, sc, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride,
+                           col * m);
+        HIPCK(c, hipGetLastError());
+    }
+    return g1_mul_to_proj(c, m, base, sc, stride, 0, col * m, skip);
+}
+static int bbs04_sign_args(size_t msg_len, const void* gpk, const void* gsk, const void* msgs, const void* rnd, const void* sig, const void* status) {
+    return (!gpk || !gsk || !rnd || !sig || !status || (msg_len && !msgs)) ? C12381_E_ARG : 0;
+}
+int c12381_bbs04_sign_batch_dev(c12381_ctx* c, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* gsk_97, const uint8_t* msgs,
+                                const uint8_t* rnd_224, uint8_t* sig_435, uint8_t* status) {
+    int rc = bind(c); if (rc || (rc = bbs04_sign_args(msg_len, gpk_390, gsk_97, msgs, rnd_224, sig_435, status))) return rc;
+    if (n == 0) return 0;
+    const size_t ch = n < BBS04_CHUNK ? n : BBS04_CHUNK, L = msg_len + 919;
+    if ((rc = ensure(c, c12381_ctx::WS_BBS04, bbs04_sign_layout(nullptr, ch, msg_len).bytes))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS04];
+    if ((rc = bbs04_pub(c, gpk_390, d))) return rc;
+    const uint8_t *h = d + 512 + 96, *u = d + 512 + 192, *v = d + 512 + 288;
+    const bool fb = fixed_base_enabled();
+    for (size_t off = 0; off < n; off += ch) {
+        const size_t m = n - off < ch ? n - off : ch;
+        const bbs04_sign_slab s = bbs04_sign_layout(d, m, msg_len);
+        const uint8_t *gsk = gsk_97 + 97 * off, *rnd = rnd_224 + 224 * off;
+        hipLaunchKernelGGL(bbs04_sign_prep_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, gsk, rnd, s.a49, s.sc);
+        hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, s.a49, s.a96, s.st_a, 0);
+        HIPCK(c, hipGetLastError());
+        if (off == 0) HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        const size_t stride = round_up(9 * m, 64);
+        if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+        if (fb)
+            for (int t = 0; t < 3; ++t)
+                if ((rc = fixed_table(c, c12381_ctx::WS_FB_G1_0 + t, t == 0 ? u : (t == 1 ? v : h), false))) return rc;
+        // phase 1: scalar columns 0-2 -> T1, T2, T3
+        const uint8_t* base1[3] = {u, v, h};
+        for (size_t k = 0; k < 3; ++k)
+            if ((rc = bbs04_fixed_column(c, m, base1[k], (int)k, s.sc + 32 * k * m, stride, k, fb))) return rc;
+        int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
+        hipLaunchKernelGGL(bbs04_sign_t3_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, proj, stride, (const uint8_t*)s.a96);
+        HIPCK(c, hipGetLastError());
+        if ((rc = g1_finish(c, 3 * m, proj, stride, s.t49, 49))) return rc;
+        if ((rc = g1_finish(c, 3 * m, proj, stride, s.t96, 96))) return rc;
+        // phase 2: T1, T2, T3 against scalar columns 3-5 (r_x) in one launch of 3 m lanes, then columns 6-11 (u, v, u, v, h, h)
+        if ((rc = g1_mul_to_proj(c, 3 * m, s.t96, s.sc + 32 * 3 * m, stride))) return rc;
+        const uint8_t* base2[6] = {u, v, u, v, h, h};
+        const int slot2[6] = {0, 1, 0, 1, 2, 2};
+        for (size_t k = 0; k < 6; ++k)
+            if ((rc = bbs04_fixed_column(c, m, base2[k], slot2[k], s.sc + 32 * (6 + k) * m, stride, 3 + k, fb))) return rc;
+        proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
+        hipLaunchKernelGGL(bbs04_sign_combine_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, proj, stride);
+        HIPCK(c, hipGetLastError());
+        if ((rc = g1_finish(c, 4 * m, proj, stride, s.r49, 49))) return rc;
+        if ((rc = g1_finish(c, 2 * m, proj + 4 * m, stride, s.p96, 96))) return rc;
+        if ((rc = c12381_pair_product_fixed_g2_batch_dev(c, m, 2, s.p96, d + 1024, s.gt, 0u))) return rc;
+        hipLaunchKernelGGL(bbs04_transcript_kernel, dim3(grid_for(m * L)), dim3(BLOCK), 0, c->stream, m, msg_len, msg_len ? msgs + msg_len * off : msgs,
+                           s.t49, s.t96, s.r49, s.gt, s.tr);
+        hipLaunchKernelGGL(bbs04_sign_finish_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, L, s.tr, gsk, rnd, s.t49, s.st_a, d + 1536,
+                           sig_435 + 435 * off, status + off, c->d_flag);
+        HIPCK(c, hipGetLastError());
+    }
+    return 0;
+}
+int c12381_bbs04_sign_batch(c12381_ctx* c, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* gsk_97, const uint8_t* msgs,
+                            const uint8_t* rnd_224, uint8_t* sig_435, uint8_t* status) {
+    int rc = bind(c); if (rc || (rc = bbs04_sign_args(msg_len, gpk_390, gsk_97, msgs, rnd_224, sig_435, status))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{gpk_390, 390}, {gsk_97, 97 * n}, {msg_len ? msgs : nullptr, msg_len * n}, {rnd_224, 224 * n}}, {{sig_435, 435 * n}, {status, n}})))
+        return rc;
+    if ((rc = c12381_bbs04_sign_batch_dev(c, n, msg_len, s.in[0], s.in[1], s.in[2], s.in[3], s.out[0], s.out[1]))) return rc;
+    return unstage(c, s);
+}
+// key_gen's issuance (:17-23): gsk_i = serialize(g1^inverse(gamma + x_i), x_i) — the simultaneous inversion of c12381_zp_op_batch, g1's
+// fixed-base table (slot 3, as in verify; the generic kernel when g1 is not a subgroup point), 49-byte records, bbs04_issue_pack_kernel.
+// WS_BBS04: BBS04_PUB_BYTES, then 32 + 49 bytes per key of a chunk.
+static int bbs04_issue_args(const void* gpk, const void* gamma, const void* x, const void* gsk) { return (!gpk || !gamma || !x || !gsk) ? C12381_E_ARG : 0; }
+int c12381_bbs04_issue_batch_dev(c12381_ctx* c, size_t n, const uint8_t* gpk_390, const uint8_t* gamma_32, const uint8_t* x_32, uint8_t* gsk_97) {
+    int rc = bind(c); if (rc || (rc = bbs04_issue_args(gpk_390, gamma_32, x_32, gsk_97))) return rc;
+    if (n == 0) return 0;
+    const size_t ch = n < BBS04_CHUNK ? n : BBS04_CHUNK;
+    const size_t o_inv = BBS04_PUB_BYTES, o_a49 = round_up(o_inv + 32 * ch, 256);
+    if ((rc = ensure(c, c12381_ctx::WS_BBS04, o_a49 + 49 * ch))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS04];
+    if ((rc = bbs04_pub(c, gpk_390, d))) return rc;
+    const bool fb = fixed_base_enabled();
+    for (size_t off = 0; off < n; off += ch) {
+        const size_t m = n - off < ch ? n - off : ch;
+        if ((rc = zp_batch_inverse(c, m, x_32 + 32 * off, gamma_32, d + o_inv))) return rc;
+        if (off == 0) HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        const size_t stride = round_up(m, 64);
+        if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+        if (fb && (rc = fixed_table(c, c12381_ctx::WS_FB_G1_3, d + 512, false))) return rc;
+        if ((rc = bbs04_fixed_column(c, m, d + 512, 3, d + o_inv, stride, 0, fb))) return rc;
+        if ((rc = g1_finish(c, m, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, d + o_a49, 49))) return rc;
+        hipLaunchKernelGGL(bbs04_issue_pack_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, d + o_a49, x_32 + 32 * off, d + 1536, gsk_97 + 97 * off,
+                           c->d_flag);
+        HIPCK(c, hipGetLastError());
+    }
+    return 0;
+}
+int c12381_bbs04_issue_batch(c12381_ctx* c, size_t n, const uint8_t* gpk_390, const uint8_t* gamma_32, const uint8_t* x_32, uint8_t* gsk_97) {
+    int rc = bind(c); if (rc || (rc = bbs04_issue_args(gpk_390, gamma_32, x_32, gsk_97))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{gpk_390, 390}, {gamma_32, 32}, {x_32, 32 * n}}, {{gsk_97, 97 * n}}))) return rc;
+    if ((rc = c12381_bbs04_issue_batch_dev(c, n, s.in[0], s.in[1], s.in[2], s.out[0]))) return rc;
     return unstage(c, s);
 }
 }  // extern "C"

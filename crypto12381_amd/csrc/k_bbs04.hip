@@ -6,31 +6,20 @@
 //   bbs04_transcript_kernel  msg || T1 || T2 || T3 || R1 || R2 || R3 || R4 || R5, one thread per byte
 //   bbs04_check_kernel       SHA3-512 of the transcript mod r == c, and the status bytes
 //   bbs04_open_*             open: T3 - (T1^xi1 + T2^xi2)
+//   bbs04_sign_*             sign: member key and randomness -> scalar columns (bbs04_sign.hpp), T3 = A + h^(alpha + beta), the additions
+//                            behind R1..R5 / P1, P2, and c, the five responses and the 435-byte record from the transcript
+//   bbs04_issue_pack_kernel  key_gen's member keys: serialize(A_i, x_i)
 // c12381_hip.hip (c12381_sha3_512_batch*, c12381_bbs04_*) launches them; the scalar multiplications, the affine conversions and the
 // pairing product are the library's existing kernels.
 #include "kernels_common.hpp"
 #include "fr.hpp"
 #include "sha3.hpp"
+#include "bbs04_sign.hpp"
 
 using namespace c12381;
 
 namespace {
 
-// 32 big-endian bytes -> little-endian numeric words
-__device__ __forceinline__ void words_from_be32(uint32_t (&k)[8], const uint8_t* b) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint8_t* q = b + 4 * (7 - i);
-        k[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | (uint32_t)q[3];
-    }
-}
-__device__ __forceinline__ void store_be32(uint8_t* o, const fr& a) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t v = a.w[7 - i];
-        o[4 * i] = (uint8_t)(v >> 24); o[4 * i + 1] = (uint8_t)(v >> 16); o[4 * i + 2] = (uint8_t)(v >> 8); o[4 * i + 3] = (uint8_t)v;
-    }
-}
 // signature j: T1, T2, T3 into three 49-byte columns, the six Zp fields (c, s_alpha, s_beta, s_x, s_delta1, s_delta2) as numeric values;
 // returns whether every field is below r (parse<G1^3 | Zp^6>, zp_number.hpp:226-236)
 __device__ __forceinline__ bool bbs04_parse_sig(size_t n, size_t j, const uint8_t* sig435, uint8_t* t49, fr (&z)[6]) {
@@ -230,6 +219,129 @@ __global__ void __launch_bounds__(BLOCK, 2) bbs04_open_status_kernel(size_t n, c
     const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (j >= n) return;
     status[j] = (st_sig[j] && st_t[j] && st_t[n + j] && st_t[2 * n + j]) ? 0 : 0xff;
+}
+
+// ---- sign (bbs.cpp:32-59)
+// gsk_j = serialize(A, x) -> a49[j] = A's wire bytes; rnd_j -> the twelve scalar columns sc[k * n + j] (bbs04_sign.hpp numbers the fixed ones):
+//   0 alpha (u)  1 beta (v)  2 alpha + beta (h)  |  3, 4, 5 r_x (T1, T2, T3)  |  6 r_alpha (u)  7 r_beta (v)  8 -r_delta1 (u)  9 -r_delta2 (v)
+//   10 -(r_delta1 + r_delta2) (h)  11 -(r_alpha + r_beta) (h)
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_prep_kernel(size_t n, const uint8_t* gsk97, const uint8_t* rnd224, uint8_t* a49, uint8_t* sc) {
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+#pragma unroll 1
+    for (int b = 0; b < 49; ++b) a49[49 * j + b] = gsk97[97 * j + b];
+    fr s[BBS04_SIGN_SCALARS], col[BBS04_SIGN_COLS];
+    bbs04_sign_reduce(s, rnd224 + 224 * j);
+    bbs04_sign_columns(col, s);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        store_be32(sc + 32 * (k * n + j), col[k]);
+        store_be32(sc + 32 * ((3 + k) * n + j), s[BBS04_RX]);
+    }
+#pragma unroll
+    for (int k = 3; k < BBS04_SIGN_COLS; ++k) store_be32(sc + 32 * ((3 + k) * n + j), col[k]);
+}
+// proj column 2 (h^(alpha + beta)) += A: T3
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_t3_kernel(size_t n, int32_t* proj, size_t stride, const uint8_t* a96) {
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    g1p a, b;
+    g1_load_affine(a, a96 + 96 * j);
+    soa_load_g1(b, proj, stride, 2 * n + j);
+    g1_add(a, b);
+    g1_store_norm(proj, stride, 2 * n + j, a);
+}
+// In place over the nine projective columns of phase 2 (0 T1^rx  1 T2^rx  2 T3^rx  3 u^ra  4 v^rb  5 u^-rd1  6 v^-rd2  7 h^-(rd1 + rd2)
+// 8 h^-(ra + rb)) -> 0 R1  1 R2  2 R4 = T1^rx u^-rd1  3 R5 = T2^rx v^-rd2  4 P1 = T3^rx h^-(rd1 + rd2)  5 P2 = h^-(ra + rb), the order verify's
+// transcript and pairing product take.  Every column is read before it is written (R4 waits in column 5).
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_combine_kernel(size_t n, int32_t* proj, size_t stride) {
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    g1p a, b;
+    soa_load_g1(a, proj, stride, j);
+    soa_load_g1(b, proj, stride, 5 * n + j);
+    g1_add(a, b);
+    g1_store_norm(proj, stride, 5 * n + j, a);              // R4, parked
+    soa_load_g1(a, proj, stride, 3 * n + j);
+    g1_store_norm(proj, stride, j, a);                      // R1
+    soa_load_g1(a, proj, stride, n + j);
+    soa_load_g1(b, proj, stride, 6 * n + j);
+    g1_add(a, b);
+    g1_store_norm(proj, stride, 3 * n + j, a);              // R5
+    soa_load_g1(a, proj, stride, 4 * n + j);
+    g1_store_norm(proj, stride, n + j, a);                  // R2
+    soa_load_g1(a, proj, stride, 2 * n + j);
+    soa_load_g1(b, proj, stride, 7 * n + j);
+    g1_add(a, b);
+    g1_store_norm(proj, stride, 4 * n + j, a);              // P1
+    soa_load_g1(a, proj, stride, 5 * n + j);
+    g1_store_norm(proj, stride, 2 * n + j, a);              // R4
+    soa_load_g1(a, proj, stride, 8 * n + j);
+    g1_store_norm(proj, stride, 5 * n + j, a);              // P2
+}
+// sig_j = T1 | T2 | T3 (t49 columns) | c | s_alpha | s_beta | s_x | s_delta1 | s_delta2 with c = SHA3-512(transcript_j) mod r; status[j] = 0.
+// Where the reference would terminate — A does not decode (st_a), x >= r — status[j] = 0xff and the record is 435 bytes of 0xff; public
+// material that does not decode (st_pub: 4 G1 + 2 G2 statuses) does that to every lane and raises bad_flag[0] (C12381_E_POINT).
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_finish_kernel(size_t n, size_t L, const uint8_t* tr, const uint8_t* gsk97, const uint8_t* rnd224,
+                                                                   const uint8_t* t49, const uint8_t* st_a, const uint8_t* st_pub, uint8_t* sig435,
+                                                                   uint8_t* status, int* bad_flag) {
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    bool pub = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) pub = pub && st_pub[i] != 0;
+    if (!pub && j == 0) *bad_flag = 1;
+    uint8_t x32[32];
+    const bool x_ok = wire_zp(x32, gsk97 + 97 * j + 49);
+    uint8_t* o = sig435 + 435 * j;
+    if (!pub || !x_ok || !st_a[j]) {
+#pragma unroll 1
+        for (int b = 0; b < 435; ++b) o[b] = 0xff;
+        status[j] = 0xff;
+        return;
+    }
+    uint64_t h[8];
+    sha3_512(h, tr + L * j, L);
+    uint32_t w[16], xw[8];
+    sha3_digest_words_be(w, h);
+    fr c, x, s[BBS04_SIGN_SCALARS], f[6];
+    fr_from_digest_words(c, w);
+    words_from_be32(xw, x32);
+    fr_set_words(x, xw);
+    bbs04_sign_reduce(s, rnd224 + 224 * j);
+    bbs04_sign_responses(f, c, x, s);
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k)
+#pragma unroll 1
+        for (int b = 0; b < 49; ++b) o[49 * k + b] = t49[49 * (k * n + j) + b];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) store_be48(o + 147 + 48 * k, f[k]);
+    status[j] = 0;
+}
+
+// key_gen's member keys (bbs.cpp:17-23): gsk_j = a49[j] | x_j mod r as 48 bytes; public material that does not decode: every byte 0xff and
+// bad_flag[0] (C12381_E_POINT)
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_issue_pack_kernel(size_t n, const uint8_t* a49, const uint8_t* x32, const uint8_t* st_pub, uint8_t* gsk97,
+                                                                  int* bad_flag) {
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    bool pub = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) pub = pub && st_pub[i] != 0;
+    if (!pub && j == 0) *bad_flag = 1;
+    uint8_t* o = gsk97 + 97 * j;
+    if (!pub) {
+#pragma unroll 1
+        for (int b = 0; b < 97; ++b) o[b] = 0xff;
+        return;
+    }
+#pragma unroll 1
+    for (int b = 0; b < 49; ++b) o[b] = a49[49 * j + b];
+    uint32_t w[8];
+    fr x;
+    words_from_be32(w, x32 + 32 * j);
+    fr_reduce_words(x, w);
+    store_be48(o + 49, x);
 }
 
 }  // namespace c12381

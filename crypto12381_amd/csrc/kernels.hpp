@@ -129,6 +129,11 @@ __global__ void __launch_bounds__(BLOCK, 2) bbs04_check_kernel(size_t n, size_t 
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_open_prep_kernel(size_t n, const uint8_t* gmsk96, const uint8_t* sig435, uint8_t* t49, uint8_t* sc, uint8_t* st, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_open_combine_kernel(size_t n, int32_t* proj, size_t stride, const uint8_t* t3_96);
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_open_status_kernel(size_t n, const uint8_t* st_sig, const uint8_t* st_t, uint8_t* status);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_prep_kernel(size_t n, const uint8_t* gsk97, const uint8_t* rnd224, uint8_t* a49, uint8_t* sc);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_t3_kernel(size_t n, int32_t* proj, size_t stride, const uint8_t* a96);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_combine_kernel(size_t n, int32_t* proj, size_t stride);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_finish_kernel(size_t n, size_t L, const uint8_t* tr, const uint8_t* gsk97, const uint8_t* rnd224, const uint8_t* t49, const uint8_t* st_a, const uint8_t* st_pub, uint8_t* sig435, uint8_t* status, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) bbs04_issue_pack_kernel(size_t n, const uint8_t* a49, const uint8_t* x32, const uint8_t* st_pub, uint8_t* gsk97, int* bad_flag);
 __global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(const uint8_t* base, int nbytes, int32_t* header);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_table_kernel(const uint8_t* base96, int32_t* buf);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_eval_kernel(size_t n, const int32_t* buf, const uint8_t* scalars, int32_t* proj, size_t proj_stride, size_t proj_off);

@@ -417,6 +417,41 @@ int c12381_bbs04_verify_batch_dev(c12381_ctx* ctx, size_t n, size_t msg_len, con
  * reports it at the next c12381_sync). */
 int c12381_bbs04_open_batch(c12381_ctx* ctx, size_t n, const uint8_t* gmsk_96, const uint8_t* sig_435, uint8_t* out49, uint8_t* status);
 int c12381_bbs04_open_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* gmsk_96, const uint8_t* sig_435, uint8_t* out49, uint8_t* status);
+/* c12381_bbs04_sign_batch: sig[j] = sign(gpk, gsk_j, msg_j) (bbs.cpp:32-59) with the caller's randomness.  Further layouts:
+ *   gsk   n records serialize(A_i, x_i), 49 + 48 = 97 bytes (GroupMemberPrivateKey, bbs.hpp), decoded as above: a leading 0x00 is
+ *         infinity, x taken mod p, no subgroup check, parse<Zp> range check on the 48-byte field
+ *   rnd   per signature the seven scalars the reference draws inside sign(), in the order of its structured binding: alpha, beta, r_alpha,
+ *         r_beta, r_x, r_delta1, r_delta2, 32 big-endian bytes each, 224 bytes per signature; any value below 2^256, reduced mod r first
+ *   sig   serialize(T1, T2, T3, c, s_alpha, s_beta, s_x, s_delta1, s_delta2), 435 bytes per signature
+ * Per signature, `^` being multiply (PAIR_G1mul, exact for every curve point: gpk and A may lie outside G1 / G2, w may be infinity):
+ *   T1 = u^alpha   T2 = v^beta   T3 = A h^(alpha + beta)   R1 = u^ra   R2 = v^rb   R4 = T1^rx u^-rd1   R5 = T2^rx v^-rd2
+ *   R3 = e(T3^rx h^-(rd1 + rd2), g2) * e(h^-(ra + rb), w)                  (c12381_pair_product_fixed_g2_batch with k = 2)
+ *   c = SHA3-512(msg | T1 | T2 | T3 | R1 | R2 | R3 | R4 | R5) mod r         (the transcript verify hashes, msg_len + 919 bytes)
+ *   s_alpha = ra + c alpha   s_beta = rb + c beta   cx = c x   s_x = rx + cx   s_delta1 = rd1 + alpha cx   s_delta2 = rd2 + beta cx
+ * Status: status[j] = 0 and 435 signature bytes; 0xff where the reference would terminate (A does not decode, or x >= r): that signature
+ * is then 435 bytes of 0xff, the other lanes are unaffected and the call returns C12381_OK.  A gpk that does not decode sets every status
+ * and signature byte to 0xff and returns C12381_E_POINT (the _dev form reports it at the next c12381_sync); the context stays usable.
+ * n = 0 touches nothing.
+ * NOT constant-time: the scalar multiplications, the pairing and the table look-ups take data-dependent paths and addresses.  The secrets
+ * the call is given (gsk, alpha ... r_delta2) and values derived from them stay in the context's device workspaces (and, for the host
+ * form, its staging buffer) until a later call overwrites them or c12381_trim frees them; nothing is wiped.
+ * Workspace: per signature of a chunk of up to 2^18, 1929 + (msg_len + 919) bytes (A 49 + 96 + 1, twelve scalar columns 384, T records
+ * 147 + 288, R records 196, P points 192, R3 576, transcript) plus 9 projective G1 points (1296 bytes) in the scalar-multiplication
+ * workspace, whose window tables take 2816 bytes per lane of three variable-base columns; 2^18 signatures with 32-byte messages: about
+ * 1.1 GB besides 2.2 GB of tables. */
+int c12381_bbs04_sign_batch(c12381_ctx* ctx, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* gsk_97, const uint8_t* msgs,
+                            const uint8_t* rnd_224, uint8_t* sig_435, uint8_t* status);
+int c12381_bbs04_sign_batch_dev(c12381_ctx* ctx, size_t n, size_t msg_len, const uint8_t* gpk_390, const uint8_t* gsk_97, const uint8_t* msgs,
+                                const uint8_t* rnd_224, uint8_t* sig_435, uint8_t* status);
+/* c12381_bbs04_issue_batch: the member keys of key_gen (bbs.cpp:17-23): gsk[i] = serialize(g1^inverse(gamma + x_i), x_i), 97 bytes each.
+ * gamma (one scalar) and x_i are 32 big-endian bytes, any value below 2^256, reduced mod r first.  inverse(0) = 0, so A is then g1^0:
+ * infinity (49 zero bytes) for a g1 in G1; for a g1 outside G1 it is whatever PAIR_G1mul makes of the scalar 0, which need not be infinity
+ * (a g1 with a point of order 3 added gives the order-3 point at x = 0, bytes 03 | 00..00).  g1 is gpk's, by its fixed-base table, or the
+ * generic kernel when it lies outside G1.  A gpk that does not decode makes every output byte 0xff and returns C12381_E_POINT.  Not
+ * constant-time; gamma and its inverses stay in the workspaces as above (32 + 49 bytes per key of a chunk of up to 2^18, one projective
+ * point). */
+int c12381_bbs04_issue_batch(c12381_ctx* ctx, size_t n, const uint8_t* gpk_390, const uint8_t* gamma_32, const uint8_t* x_32, uint8_t* gsk_97);
+int c12381_bbs04_issue_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* gpk_390, const uint8_t* gamma_32, const uint8_t* x_32, uint8_t* gsk_97);
 
 #ifdef __cplusplus
 }
