@@ -99,6 +99,8 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, vp, vp, ci]
         for name in ("c12381_g1_mul_fixed_batch", "c12381_g1_mul_fixed_batch_dev", "c12381_g2_mul_fixed_batch", "c12381_g2_mul_fixed_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, ci]
+        for name in ("c12381_g1_mul_fixed_sum_batch", "c12381_g1_mul_fixed_sum_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp, ci]
         for name in ("c12381_pair_fixed_g2_batch", "c12381_pair_fixed_g2_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp]
         for name in ("c12381_pair_product_fixed_g2_batch", "c12381_pair_product_fixed_g2_batch_dev"):
@@ -391,6 +393,19 @@ class Context:
 
     def g2_mul_fixed_dev(self, n, base_ptr, sc_ptr, out_ptr, fmt=97):
         self._ck(self.lib.c12381_g2_mul_fixed_batch_dev(self.h, n, _p(base_ptr), _p(sc_ptr), _p(out_ptr), fmt))
+
+    def g1_mul_fixed_sum(self, bases: bytes, scalars: bytes, addend: bytes | None = None, fmt: int = 49, strict: bool = True) -> bytes:
+        """out[j] = addend + sum over i < nb of scalars[i n + j] * bases[i]: per-lane products over nb = len(bases) // 96 public bases shared by
+        the batch (1 <= nb <= 32), served from nb fixed-base tables when every base is a subgroup point.  scalars: base-major, nb arrays of n
+        records; addend: one 96-byte point or None; returns n points of `fmt` bytes.  Every lane equals multiply on each term followed by add"""
+        nb = len(bases) // 96
+        n = len(scalars) // (32 * nb) if nb > 0 else 0
+        out = ctypes.create_string_buffer(max(fmt * n, 1))
+        self._ck(self.lib.c12381_g1_mul_fixed_sum_batch(self.h, n, nb, _p(bases), _p(addend), _p(scalars), _p(out), fmt), allow_point=not strict)
+        return out.raw[:fmt * n]
+
+    def g1_mul_fixed_sum_dev(self, n, nb, bases_ptr, sc_ptr, out_ptr, addend_ptr=None, fmt=49):
+        self._ck(self.lib.c12381_g1_mul_fixed_sum_batch_dev(self.h, n, nb, _p(bases_ptr), _p(addend_ptr), _p(sc_ptr), _p(out_ptr), fmt))
 
     def g1_map_to_point(self, u48: bytes) -> bytes:
         n = len(u48) // 48

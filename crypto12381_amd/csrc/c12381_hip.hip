@@ -74,7 +74,7 @@ struct c12381_ctx {
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
            WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_G, WS_FQ_GATE, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
-           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_COUNT };
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;
@@ -440,7 +440,7 @@ static bool msm_use_buckets(size_t n) {
 
 extern "C" {
 
-int c12381_version(void) { return (0 << 16) | 3; }
+int c12381_version(void) { return (0 << 16) | 4; }
 
 int c12381_create(int device, c12381_ctx** out) {
     if (!out) return C12381_E_ARG;
@@ -1582,6 +1582,65 @@ int c12381_g1_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base96, co
     if (n == 0) return 0;
     staging s;
     if ((rc = stage(c, s, {{base96, 96}, {sc, 32 * n}}, {{out, (size_t)fmt * n}})) || (rc = c12381_g1_mul_fixed_batch_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
+}
+// ---------------------------------------------------------------- per-lane sums over a set of bases shared by the batch
+// out[j] = addend + sum_(i < nb) sc[i n + j] B_i.  WS_FB_G1_SUM: [gate: FBS_GATE_DWORDS][table 0] ... [table G1_FIXED_SUM_MAX - 1], each table
+// a header (fixed_cache_check_kernel protocol, per position: changing one base rebuilds one table) and the 4080 multiples of fixed_base.hpp.
+// One cache-check launch, one table launch and one gate launch whatever nb; then BOTH routes are queued and the gate lets one run:
+//   every base a subgroup point   g1_fixed_sum_kernel: all nb tables into one accumulator per lane
+//   otherwise                     the columns through the generic kernel one by one, each folded into proj[0, n) (two projective arrays
+//                                 whatever nb), as bbs_message_points sums its columns
+// The skipped route's kernels return at their first load.  Nothing waits for the host.
+static_assert(C12381_G1_FIXED_SUM_MAX == G1_FIXED_SUM_MAX, "public and device bound of nb");
+constexpr size_t FBS_GATE_DWORDS = 128;
+constexpr size_t FBS_TAB_DWORDS = (FB_HEADER_DWORDS + (size_t)FB_G1_WINDOWS * FB_ENTRIES * FB_G1_DWORDS + 63) / 64 * 64;
+static int g1_fixed_sum_args(size_t nb, const void* bases, const void* sc, const void* out, int fmt) {
+    return (nb < 1 || nb > C12381_G1_FIXED_SUM_MAX || !bases || !sc || !out || !g1_fmt(fmt)) ? C12381_E_ARG : 0;
+}
+int c12381_g1_mul_fixed_sum_batch_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc, uint8_t* out,
+                                      int fmt) {
+    int rc = bind(c); if (rc || (rc = g1_fixed_sum_args(nb, bases96, sc, out, fmt))) return rc;
+    if (n == 0) return 0;
+    const size_t bytes = (FBS_GATE_DWORDS + (size_t)G1_FIXED_SUM_MAX * FBS_TAB_DWORDS) * 4;
+    if (c->ws_bytes[c12381_ctx::WS_FB_G1_SUM] < bytes) {
+        if ((rc = ensure(c, c12381_ctx::WS_FB_G1_SUM, bytes))) return rc;
+        HIPCK(c, hipMemsetAsync(c->ws[c12381_ctx::WS_FB_G1_SUM], 0, bytes, c->stream));      // no magic yet: first use of every table is a miss
+    }
+    int32_t* gate = (int32_t*)c->ws[c12381_ctx::WS_FB_G1_SUM];
+    int32_t* tabs = gate + FBS_GATE_DWORDS;
+    const size_t half = round_up(n, 64), stride = 2 * half;       // proj[0, n): the sums; proj[half, half + n): the generic route's current column
+    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+    int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
+    const bool fb = fixed_base_enabled();
+    if (fb) {
+        hipLaunchKernelGGL(fixed_cache_checkk_kernel, dim3((unsigned)nb), dim3(64), 0, c->stream, bases96, 96, tabs, (int)FBS_TAB_DWORDS);
+        hipLaunchKernelGGL(g1_fixed_tablek_kernel, dim3(grid_for((size_t)FB_G1_WINDOWS * FB_ENTRIES), (unsigned)nb), dim3(BLOCK), 0, c->stream, bases96, tabs,
+                           (int)FBS_TAB_DWORDS);
+    }
+    hipLaunchKernelGGL(g1_fixed_sum_gate_kernel, dim3(1), dim3(64), 0, c->stream, (int)nb, bases96, addend96, gate, (const int32_t*)tabs, (int)FBS_TAB_DWORDS,
+                       fb ? 1 : 0, c->d_flag);
+    HIPCK(c, hipGetLastError());
+    if (fb) {
+        hipLaunchKernelGGL(g1_fixed_sum_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (int)nb, (const int32_t*)gate, (const int32_t*)tabs,
+                           (int)FBS_TAB_DWORDS, sc, addend96, proj, stride);
+        HIPCK(c, hipGetLastError());
+    }
+    for (size_t col = 0; col < nb; ++col) {
+        if ((rc = g1_mul_to_proj(c, n, bases96 + 96 * col, sc + 32 * n * col, stride, 0, col ? half : 0, gate))) return rc;
+        if (col == 0 && nb > 1) continue;                          // the first column is written in place
+        hipLaunchKernelGGL(g1_fixed_sum_fold_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (const int32_t*)gate, proj, stride, half, col ? 1 : 0,
+                           col + 1 == nb ? 1 : 0, addend96);
+        HIPCK(c, hipGetLastError());
+    }
+    return g1_finish(c, n, proj, stride, out, fmt);
+}
+int c12381_g1_mul_fixed_sum_batch(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc, uint8_t* out, int fmt) {
+    int rc = bind(c); if (rc || (rc = g1_fixed_sum_args(nb, bases96, sc, out, fmt))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{bases96, 96 * nb}, {addend96, 96}, {sc, 32 * n * nb}}, {{out, (size_t)fmt * n}}))) return rc;
+    if ((rc = c12381_g1_mul_fixed_sum_batch_dev(c, n, nb, s.in[0], s.in[1], s.in[2], s.out[0], fmt))) return rc;
     return unstage(c, s);
 }
 int c12381_g2_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base192, const uint8_t* sc, uint8_t* out, int fmt) {

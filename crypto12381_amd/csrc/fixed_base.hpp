@@ -82,8 +82,11 @@ C12381_HD void fb_load_g2(fp2& x, fp2& y, const int32_t* src) {
     msm_load_pt(y.a, y.b, src + MSM_PT_DWORDS);
 }
 
-// acc = [k]B from the table (k: 8 little-endian words, any value; reduced mod r here)
-C12381_HD void g1_fixed_eval(g1p& acc, const int32_t* tab, const uint32_t (&kin)[8]) {
+// acc += [k]B from the table (k: 8 little-endian words, any value; reduced mod r here).  acc may be ANY point, related to B or not:
+// g1_add_affine is complete for a finite affine addend (E(Fp) has odd order) and no table entry is the point at infinity (B has order r,
+// the entries are [d 2^(8j)]B with 0 < d < 256), so sums over bases with H2 = +-H1, 2 H1, phi(H1), and sums that pass through or end at
+// infinity, need no exceptional path.
+C12381_HD void g1_fixed_eval_add(g1p& acc, const int32_t* tab, const uint32_t (&kin)[8]) {
     uint32_t k[8], k0[4], k1[4];
 #pragma unroll
     for (int i = 0; i < 8; ++i) k[i] = kin[i];
@@ -91,7 +94,6 @@ C12381_HD void g1_fixed_eval(g1p& acc, const int32_t* tab, const uint32_t (&kin)
     scalar_glv_split(k0, k1, k);
     fp beta;
     fp_set_const(beta, FP_BETA_A);
-    g1_set_inf(acc);
 #pragma unroll 1
     for (int j = 0; j < FB_G1_WINDOWS; ++j) {
         const uint32_t d0 = (k0[j >> 2] >> (8 * (j & 3))) & 255u, d1 = (k1[j >> 2] >> (8 * (j & 3))) & 255u;
@@ -107,6 +109,23 @@ C12381_HD void g1_fixed_eval(g1p& acc, const int32_t* tab, const uint32_t (&kin)
             fp_neg(ny, y); fp_norm1(ny, ny);
             g1_add_affine(acc, bx, ny);
         }
+    }
+}
+// acc = [k]B from the table
+C12381_HD void g1_fixed_eval(g1p& acc, const int32_t* tab, const uint32_t (&kin)[8]) {
+    g1_set_inf(acc);
+    g1_fixed_eval_add(acc, tab, kin);
+}
+// acc = sum_(i < nb) [k_i]B_i from nb tables `tab_stride` dwords apart, scalar(i, k) handing out the lane's k_i: one accumulator across
+// all bases, base by base (the table offset is the same for every lane of a wavefront), up to 32 nb mixed additions and no doubling
+template <class SC>
+C12381_HD void g1_fixed_eval_sum(g1p& acc, const int32_t* tabs, size_t tab_stride, int nb, const SC& scalar) {
+    g1_set_inf(acc);
+#pragma unroll 1
+    for (int i = 0; i < nb; ++i) {
+        uint32_t k[8];
+        scalar(i, k);
+        g1_fixed_eval_add(acc, tabs + (size_t)i * tab_stride, k);
     }
 }
 template <int I>

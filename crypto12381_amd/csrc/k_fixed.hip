@@ -1,5 +1,6 @@
 // Fixed-base columns (fixed_base.hpp): table construction with a device-side "same base as last time?" check, and
-// the table-driven evaluation kernels.  Table buffer = FB_HEADER_DWORDS header (cached base bytes, state) + entries.
+// the table-driven evaluation kernels (one base per column, and per-lane sums over a set of bases).
+// Table buffer = FB_HEADER_DWORDS header (cached base bytes, state) + entries.
 //   header[0..47]  the base's canonical bytes as dwords (96 B for G1, 192 B for G2)
 //   header[HDR_VALID]    ok: 1 = table valid (base on the curve, not infinity, in the order-r subgroup)
 //   header[HDR_REBUILD]  build: 1 = the table kernel must (re)build, 0 = cached table matches the base
@@ -11,7 +12,7 @@ using namespace c12381;
 namespace c12381 {
 
 // one wavefront: compare the base with the cached copy; on a miss store the new copy and request a rebuild
-__global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(const uint8_t* base, int nbytes, int32_t* header) {
+static __device__ __forceinline__ void fixed_cache_check(const uint8_t* base, int nbytes, int32_t* header) {
     const int lane = threadIdx.x;
     const int nd = nbytes / 4;
     const uint32_t* b = reinterpret_cast<const uint32_t*>(base);
@@ -21,11 +22,18 @@ __global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(const uint8_t*
     if (lane < nd) header[lane] = (int32_t)mine;
     if (lane == 0) { header[HDR_REBUILD] = same ? 0 : 1; header[HDR_MAGIC] = 0x46423031; if (!same) header[HDR_VALID] = 0; }
 }
+__global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(const uint8_t* base, int nbytes, int32_t* header) {
+    fixed_cache_check(base, nbytes, header);
+}
+// the same for the tables of a set of bases, one workgroup per base (tables tab_stride dwords apart)
+__global__ void __launch_bounds__(64, 1) fixed_cache_checkk_kernel(const uint8_t* bases, int nbytes, int32_t* tabs, int tab_stride) {
+    fixed_cache_check(bases + (size_t)nbytes * blockIdx.x, nbytes, tabs + (size_t)blockIdx.x * tab_stride);
+}
 
-__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_table_kernel(const uint8_t* base96, int32_t* buf) {
+// entry L of the table of base96 (every entry by its own lane: no entry waits for another)
+static __device__ __forceinline__ void g1_fixed_table_entry(const uint8_t* base96, int32_t* buf, size_t L) {
     int32_t* header = buf;
     if (header[HDR_REBUILD] == 0) return;                                   // cached table is current
-    const size_t L = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (L >= (size_t)FB_G1_WINDOWS * FB_ENTRIES) return;
     g1p base;
     bool inf, ok;
@@ -45,6 +53,13 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_table_kernel(const uint8_t*
     g1_to_affine(ax, ay, an, zi);
     msm_store_pt(buf + FB_HEADER_DWORDS + L * FB_G1_DWORDS, ax, ay);
 }
+__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_table_kernel(const uint8_t* base96, int32_t* buf) {
+    g1_fixed_table_entry(base96, buf, (size_t)blockIdx.x * BLOCK + threadIdx.x);
+}
+// the tables of a set of bases in one launch: blockIdx.y = base; a base whose cached table is current costs its workgroups one load
+__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_tablek_kernel(const uint8_t* bases96, int32_t* tabs, int tab_stride) {
+    g1_fixed_table_entry(bases96 + (size_t)96 * blockIdx.y, tabs + (size_t)blockIdx.y * tab_stride, (size_t)blockIdx.x * BLOCK + threadIdx.x);
+}
 
 // proj[off + i] = [k_i]B from the table; does nothing when the table is not valid (the generic kernel runs then)
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_eval_kernel(size_t n, const int32_t* buf, const uint8_t* scalars, int32_t* proj, size_t proj_stride,
@@ -59,6 +74,80 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_eval_kernel(size_t n, const
     g1_fixed_eval(acc, buf + FB_HEADER_DWORDS, k);
     g1_norm1(o, acc);
     soa_store_g1(proj, proj_stride, proj_off + i, o);
+}
+
+// ---- per-lane sums over a set of shared bases (c12381_g1_mul_fixed_sum_batch): out[j] = addend + sum_i [k_(i n + j)]B_i
+// The gate in front of the nb tables picks the route on the device: gate[HDR_VALID] = every base has a valid table (g1_fixed_sum_kernel
+// runs), (gate + GATE_OTHER)[HDR_VALID] = the opposite (the generic columns and g1_fixed_sum_fold_kernel run), gate[HDR_RULE] = a base or
+// the addend is not on the curve (every output is marked invalid; *bad_flag is raised here, once).  One wavefront: lane t looks at base t,
+// lane nb at the addend.
+__global__ void __launch_bounds__(64, 1) g1_fixed_sum_gate_kernel(int nb, const uint8_t* bases96, const uint8_t* addend96, int32_t* gate,
+                                                                 const int32_t* tabs, int tab_stride, int use_tables, int* bad_flag) {
+    const int t = threadIdx.x;
+    bool ok = true, valid = true;
+    if (t < nb || (t == nb && addend96)) {
+        fp x, y;
+        bool inf;
+        g1_parse96(x, y, inf, ok, t < nb ? bases96 + 96 * t : addend96);
+    }
+    if (t < nb) valid = use_tables && tabs[(size_t)t * tab_stride + HDR_VALID] != 0;
+    const bool all_valid = __all(valid), bad = __any(!ok);
+    if (t == 0) {
+        gate[HDR_VALID] = all_valid ? 1 : 0;
+        gate[GATE_OTHER + HDR_VALID] = all_valid ? 0 : 1;
+        gate[HDR_RULE] = bad ? 1 : 0;
+        if (bad) *bad_flag = 1;
+    }
+}
+// acc -> the lane's result: plus the addend (complete addition, as g1_add_const_kernel), or the invalid mark when the gate says so
+static __device__ __forceinline__ void g1_fixed_sum_close(g1p& o, const g1p& acc, const uint8_t* addend96, const int32_t* gate) {
+    g1_norm1(o, acc);
+    if (addend96) {                                       // kernel-uniform
+        g1p q;
+        bool inf, ok;
+        g1_parse96_proj(q, inf, ok, addend96);
+        g1_add(o, q);
+        g1_norm1(o);
+    }
+    if (gate[HDR_RULE] != 0) g1_set_invalid(o);
+}
+// lane j's 32-byte scalar for base i of a base-major array of nb x n records
+struct fixed_sum_scalars {
+    const uint8_t* sc; size_t n, j;
+    __device__ __forceinline__ void operator()(int i, uint32_t (&k)[8]) const {
+        uint32_t raw[8];
+        load_raw32(raw, sc + 32 * ((size_t)i * n + j));
+        scalar_from_raw32(k, raw);
+    }
+};
+// proj[j] = addend + sum_(i < nb) [k_(i n + j)]B_i from the nb tables behind the gate: one lane per output, one accumulator per lane in
+// registers across all bases, no per-column store and no reduce pass
+__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_sum_kernel(size_t n, int nb, const int32_t* gate, const int32_t* tabs, int tab_stride,
+                                                             const uint8_t* scalars, const uint8_t* addend96, int32_t* proj, size_t proj_stride) {
+    if (gate[HDR_VALID] == 0) return;
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    g1p acc, o;
+    g1_fixed_eval_sum(acc, tabs + FB_HEADER_DWORDS, (size_t)tab_stride, nb, fixed_sum_scalars{scalars, n, j});
+    g1_fixed_sum_close(o, acc, addend96, gate);
+    soa_store_g1(proj, proj_stride, j, o);
+}
+// The generic route, column by column: proj[j] += proj[col_off + j] (has_col), and behind the last column the addend / invalid mark (last)
+__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_sum_fold_kernel(size_t n, const int32_t* gate, int32_t* proj, size_t proj_stride, size_t col_off,
+                                                                  int has_col, int last, const uint8_t* addend96) {
+    if (gate[GATE_OTHER + HDR_VALID] == 0) return;
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    g1p acc, o;
+    soa_load_g1(acc, proj, proj_stride, j);
+    if (has_col) {
+        g1p q;
+        soa_load_g1(q, proj, proj_stride, col_off + j);
+        g1_add(acc, q);
+    }
+    if (last) g1_fixed_sum_close(o, acc, addend96, gate);
+    else g1_norm1(o, acc);
+    soa_store_g1(proj, proj_stride, j, o);
 }
 
 __global__ void __launch_bounds__(BLOCK, 2) g2_fixed_table_kernel(const uint8_t* base192, int32_t* buf) {

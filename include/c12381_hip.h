@@ -294,6 +294,32 @@ int c12381_g1_mul_fixed_batch(c12381_ctx* ctx, size_t n, const uint8_t* base96, 
 int c12381_g1_mul_fixed_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* base96, const uint8_t* scalars32, uint8_t* out, int out_fmt);
 int c12381_g2_mul_fixed_batch(c12381_ctx* ctx, size_t n, const uint8_t* base192, const uint8_t* scalars32, uint8_t* out, int out_fmt);
 int c12381_g2_mul_fixed_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* base192, const uint8_t* scalars32, uint8_t* out, int out_fmt);
+/* out[j] = addend + sum_(i < nb) scalars[i n + j] * bases[i]: per-lane products over PUBLIC bases shared by the whole batch — the shape of
+ * the reference's credential schemes: B = g1 * h0^r * Π h_i^m_i (examples/bbs-plus/src/bbs+.cpp:51, :72), C_I = g * Π Y_i^a_i and
+ * U = C_I^α * A_^β * Π Y_j^δ_j (examples/AC-bbs/src/pres.cpp:16-29, verify.cpp:24), C_hid = Π h[Prv]^z * Π h[Hid_Pub]^z_hid_pub
+ * (examples/MHAC-bbs/src/verify_pres.cpp:39-42), Π Y[n - Ip[i]]^q[i] (examples/AC-rps/src/verify.cpp:36).
+ * bases96: nb points of 96 B, one set for the batch, 1 <= nb <= C12381_G1_FIXED_SUM_MAX; addend96: one point of 96 B, or NULL for none;
+ * scalars32: base-major, nb x n records of 32 B, any value below 2^256; out_fmt = 49 or 96.
+ * Value: every lane equals multiply(point1&, const big&) on each term (PAIR_G1mul: scalar mod r, GLV form, with the [r]phi(P) term of
+ * k mod r < x^2) followed by add(point1&, point1&), the addend last, for EVERY curve point and every scalar — the contract of
+ * c12381_g1_mul_sum_batch and c12381_g1_mul_fixed_batch; nb = 1 with a NULL addend returns the bytes of c12381_g1_mul_fixed_batch.
+ * Routes: when every base is a point of G1 other than infinity the batch runs from nb device-built tables of multiples (457 KB per base,
+ * 14.6 MB at nb = 32): one accumulator per lane across all bases, up to 32 nb mixed additions, no doubling, one projective result and
+ * one affine conversion per lane.  The additions are complete, so RELATED bases (H2 = +-H1, 2 H1, phi(H1)) and sums that cancel to
+ * infinity take no other path.  Otherwise the call runs column by column through the generic kernel of c12381_g1_mul_batch and sums
+ * the columns: correct for every input, at generic speed.  The device picks the route; the host never waits.
+ * Tables live in the context in a workspace of their own (not the slots of c12381_g1_mul_fixed_batch, BBS+ and bbs04), one per base
+ * position, each kept until the base at its position changes; a call whose bases are all cached costs one check launch whatever nb.
+ * c12381_trim frees them.
+ * Status: a base or the addend that is not on the curve makes every output byte 0xff and the call return C12381_E_POINT (the _dev form:
+ * the next c12381_sync, once); the context stays usable.  nb = 0, nb > C12381_G1_FIXED_SUM_MAX, a bad out_fmt or a null ctx / bases /
+ * scalars / out: C12381_E_ARG, checked before the empty-batch rule; n = 0 returns C12381_OK and touches nothing.
+ * Not constant-time: table indices and the additions executed depend on the scalars (as in the signing entries below). */
+#define C12381_G1_FIXED_SUM_MAX 32
+int c12381_g1_mul_fixed_sum_batch(c12381_ctx* ctx, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* scalars32,
+                                  uint8_t* out, int out_fmt);
+int c12381_g1_mul_fixed_sum_batch_dev(c12381_ctx* ctx, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* scalars32,
+                                      uint8_t* out, int out_fmt);
 
 /* caller pattern of BASELINE config 5 ------------------------------------------ */
 /* ok[j] = [ e(A_j, w + x_j*g2) == e(g1 + r_j*h0 + sum_i m[i*n + j]*h_i, g2) ]: the BBS+ verification equation of the
