@@ -73,7 +73,7 @@ struct c12381_ctx {
     // WS_STAGE holds the caller's buffers of a host form (stage / unstage).  No _dev path uses it and no _dev path calls a host form
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
-           WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_G, WS_FQ_GATE, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
+           WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
            WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
@@ -247,14 +247,123 @@ int tree_sum(c12381_ctx* c, reduce_fn reduce, size_t words, size_t n, const int3
 inline bool g1_fmt(int fmt) { return fmt == 49 || fmt == 96; }
 inline bool g2_fmt(int fmt) { return fmt == 97 || fmt == 192; }
 
-// ev_chunk[0]: the event the bucket product forks its side-stream work from (the scalar-multiplication batches use the same vector per chunk)
-static int ensure_fork_event(c12381_ctx* c) {
+// fork_side: what is queued on the side stream from here on starts after everything queued on the context's stream so far (ev_chunk[0]).
+// join_side: the context's stream waits for what the side stream has been given (ev_side).  Every call that forks joins before it returns.
+int fork_side(c12381_ctx* c) {
     if (c->ev_chunk.empty()) {
         hipEvent_t e;
         HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->ev_chunk.push_back(e);
     }
+    HIPCK(c, hipEventRecord(c->ev_chunk[0], c->stream));
+    HIPCK(c, hipStreamWaitEvent(c->side, c->ev_chunk[0], 0));
     return 0;
+}
+int join_side(c12381_ctx* c) {
+    HIPCK(c, hipEventRecord(c->ev_side, c->side));
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+    return 0;
+}
+// ---------------------------------------------------------------- device-built tables, kept across calls
+// A table array: `count` tables `stride` dwords apart behind `gate` dwords (0 or GATE_DWORDS) in workspace `slot`, each a header and its entries
+// built from one point of `point_bytes` bytes (fixed-base multiples, line coefficients: the header words are listed in k_fixed.hip).  A single
+// table is an array of one.  cached_tables makes the first k tables current for the points pts.p[0 .. k): it grows the workspace and zeroes
+// it when it grew, so that every table in it misses on first use, launches fixed_cache_check_kernel — the "same point as last time?"
+// comparison runs on the device — and then the caller's build kernel, whose workgroups return at once where the cached table is current.
+// k = 0 only provides the workspace.  Everything is queued on the stream, nothing waits for the host; a table lives until another point
+// takes its place or c12381_trim frees the workspace.
+struct table_array { int slot, count; size_t stride, gate; int point_bytes; };
+struct cached { int32_t *gate, *tabs; int stride; };
+constexpr size_t GATE_DWORDS = 128;
+static_assert(FB_HEADER_DWORDS == HDR_DWORDS, "every table: header in front of the entries");
+static_assert(FIXED_G2_MAX <= TABLE_ARRAY_MAX && G1_FIXED_SUM_MAX <= TABLE_ARRAY_MAX, "table_points holds the points of the largest array");
+constexpr size_t table_dwords(size_t entries) { return (HDR_DWORDS + entries + 63) / 64 * 64; }
+constexpr size_t FB_G1_ENTRIES = (size_t)FB_G1_WINDOWS * FB_ENTRIES, FB_G2_ENTRIES = (size_t)FB_G2_WINDOWS * FB_ENTRIES;
+constexpr size_t FQ_TAB_DWORDS = table_dwords(FQ_TABLE_DWORDS);
+// G1 multiples: the four slots that g1_mul_fixed (0), the BBS+ columns (h0, h_1, h_2, h_3) and bbs04 (u, v, h, g1) share, and the nb tables
+// of the per-lane sums; G2 multiples; line tables: one Q (pair_fixed_g2), BBS+'s w and g2 (rule 1), the k points of a product.  bbs04's
+// product (rule 0) and BBS+ have a workspace each, so neither evicts the other's tables.
+constexpr table_array fb_g1_slot(int i) { return {c12381_ctx::WS_FB_G1_0 + i, 1, table_dwords(FB_G1_ENTRIES * FB_G1_DWORDS), 0, 96}; }
+constexpr table_array TA_FB_G1_SUM = {c12381_ctx::WS_FB_G1_SUM, G1_FIXED_SUM_MAX, table_dwords(FB_G1_ENTRIES * FB_G1_DWORDS), GATE_DWORDS, 96};
+constexpr table_array TA_FB_G2 = {c12381_ctx::WS_FB_G2, 1, table_dwords(FB_G2_ENTRIES * FB_G2_DWORDS), 0, 192};
+constexpr table_array TA_FQ_P = {c12381_ctx::WS_FQ_P, 1, FQ_TAB_DWORDS, 0, 192};
+constexpr table_array TA_FQ_WG = {c12381_ctx::WS_FQ_W, 2, FQ_TAB_DWORDS, GATE_DWORDS, 192};
+constexpr table_array TA_FQ_K = {c12381_ctx::WS_FQ_K, FIXED_G2_MAX, FQ_TAB_DWORDS, GATE_DWORDS, 192};
+template <class Build>
+int cached_tables(c12381_ctx* c, const table_array& a, int k, const table_points& pts, cached& t, Build build) {
+    if (k < 0 || k > a.count || a.count > TABLE_ARRAY_MAX) return C12381_E_ARG;
+    const size_t bytes = (a.gate + (size_t)a.count * a.stride) * 4;
+    int rc;
+    if (c->ws_bytes[a.slot] < bytes) {
+        if ((rc = ensure(c, a.slot, bytes))) return rc;
+        HIPCK(c, hipMemsetAsync(c->ws[a.slot], 0, bytes, c->stream));      // no magic yet: first use of every table is a miss
+    }
+    t.gate = (int32_t*)c->ws[a.slot];
+    t.tabs = t.gate + a.gate;
+    t.stride = (int)a.stride;
+    if (k == 0) return 0;
+    hipLaunchKernelGGL(fixed_cache_check_kernel, dim3((unsigned)k), dim3(64), 0, c->stream, pts, a.point_bytes, t.tabs, t.stride);
+    build(t);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+// the fixed-base tables of nb G1 points 96 bytes apart / of one G2 point
+int g1_fixed_tables(c12381_ctx* c, const table_array& a, int nb, const uint8_t* bases96, cached& t) {
+    table_points pts = {};
+    for (int i = 0; i < nb; ++i) pts.p[i] = bases96 + 96 * i;
+    return cached_tables(c, a, nb, pts, t, [&](const cached& b) {
+        hipLaunchKernelGGL(g1_fixed_tables_kernel, dim3(grid_for(FB_G1_ENTRIES), (unsigned)nb), dim3(BLOCK), 0, c->stream, bases96, b.tabs, b.stride);
+    });
+}
+int g1_fixed_table(c12381_ctx* c, int slot, const uint8_t* base96) {
+    cached t;
+    return g1_fixed_tables(c, fb_g1_slot(slot), 1, base96, t);
+}
+int g2_fixed_table(c12381_ctx* c, const uint8_t* base192, cached& t) {
+    return cached_tables(c, TA_FB_G2, 1, table_points{{base192}}, t, [&](const cached& b) {
+        hipLaunchKernelGGL(g2_fixed_table_kernel, dim3(grid_for(FB_G2_ENTRIES)), dim3(BLOCK), 0, c->stream, base192, b.tabs);
+    });
+}
+// Line tables of the k points q.p[j] (coefficients of a fixed G2 argument of the Miller loop, pairing3.hpp) and, where the array has one, the
+// gate over the k.  rule: bit 0 need_g2, bit 1 raw records (k_pairk.hip g2_lines_tables_kernel); a table is also rebuilt when its rule changes.
+int lines_tables(c12381_ctx* c, const table_array& a, int k, const g2_cols& q, int rule, cached& t) {
+    table_points pts = {};
+    for (int j = 0; j < k; ++j) pts.p[j] = q.p[j];
+    int rc = cached_tables(c, a, k, pts, t, [&](const cached& b) {
+        hipLaunchKernelGGL(g2_lines_tables_kernel, dim3(1), dim3(BLOCK), 0, c->stream, k, q, b.tabs, b.stride, rule);
+    });
+    if (rc || !a.gate) return rc;
+    hipLaunchKernelGGL(gate_all_kernel, dim3(1), dim3(BLOCK), 0, c->stream, t.gate, (const int32_t*)t.tabs, t.stride, k);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+// the rule of the entry points whose product is followed by the final exponentiation: C12381_FQ_RAW=1 keeps their records raw (A/B switch)
+int fq_rule(int need_g2) {
+    static const int raw = [] { const char* e = tuning_env("C12381_FQ_RAW"); return (e && e[0] == '1') ? 2 : 0; }();
+    return need_g2 | raw;
+}
+// BBS+'s two line tables — w and g2, both have to be elements of G2 — and the gate over them; verification and the aggregate form share them
+int bbs_lines_tables(c12381_ctx* c, const uint8_t* w_192, const uint8_t* g2_192, cached& t) {
+    g2_cols q = {};
+    q.p[0] = w_192; q.p[1] = g2_192;
+    return lines_tables(c, TA_FQ_WG, 2, q, fq_rule(1), t);
+}
+bool fixed_base_enabled() {
+    static const bool on = [] { const char* e = tuning_env("C12381_FIXED_BASE"); return !(e && e[0] == '0'); }();
+    return on;
+}
+// m products of one public base into proj[col_off, col_off + m) of WS_PROJ (stride `stride`): from the table in fixed-base slot `slot`,
+// which the caller has made current (g1_fixed_table), where the base is a subgroup point, by the generic kernel
+// otherwise — each of the two launches returns at once when the other one serves the column.  fb = false: the generic kernel alone.
+int g1_fixed_column(c12381_ctx* c, size_t m, const uint8_t* base, int slot, const uint8_t* sc, size_t stride, size_t col_off, bool fb) {
+    const int32_t* skip = nullptr;
+    if (fb) {
+        skip = (const int32_t*)c->ws[c12381_ctx::WS_FB_G1_0 + slot];
+        hipLaunchKernelGGL(g1_fixed_eval_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, skip, sc, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride,
+                           col_off);
+        HIPCK(c, hipGetLastError());
+    }
+    return g1_mul_to_proj(c, m, base, sc, stride, 0, col_off, skip);
 }
 // window width: msm_window_bits(n), or C12381_MSM_C = 4..16 (tuning runs)
 static int msm_c(size_t n) {
@@ -304,7 +413,6 @@ int g1_msm_pippenger(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t*
         const size_t tmp_half = round_up(tmp_bytes + 256, 256);
         if ((rc = ensure(c, c12381_ctx::WS_MSM_TMP, MSM_SORT_STREAMS * tmp_half))) return rc;
         uint8_t* tmp = (uint8_t*)c->ws[c12381_ctx::WS_MSM_TMP];
-        if ((rc = ensure_fork_event(c))) return rc;
         while ((int)c->sort_streams.size() < MSM_SORT_STREAMS - 2) {       // beyond the context's stream and its side stream
             hipStream_t st; hipEvent_t e;
             HIPCK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -313,18 +421,18 @@ int g1_msm_pippenger(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t*
             c->sort_events.push_back(e);
         }
         auto sort_stream = [&](int k) { return k == 0 ? c->stream : (k == 1 ? c->side : c->sort_streams[(size_t)k - 2]); };
-        HIPCK(c, hipEventRecord(c->ev_chunk[0], c->stream));               // the keys are written
-        for (int k = 1; k < MSM_SORT_STREAMS; ++k) HIPCK(c, hipStreamWaitEvent(sort_stream(k), c->ev_chunk[0], 0));
+        if ((rc = fork_side(c))) return rc;                                // the keys are written
+        for (int k = 2; k < MSM_SORT_STREAMS; ++k) HIPCK(c, hipStreamWaitEvent(sort_stream(k), c->ev_chunk[0], 0));
         for (int w = 0; w <= W; ++w) {                                     // segment W: the small-scalar entries, one key bit
             const size_t off = (size_t)2 * w * n;
             size_t sz = tmp_bytes;
             const int k = w % MSM_SORT_STREAMS;
             HIPCK(c, rocprim::radix_sort_pairs(tmp + (size_t)k * tmp_half, sz, q0 + off, q1 + off, vin, v1 + off, w < W ? 2 * n : n, 0, w < W ? cb : 1, sort_stream(k)));
         }
-        for (int k = 1; k < MSM_SORT_STREAMS; ++k) {
-            hipEvent_t e = k == 1 ? c->ev_side : c->sort_events[(size_t)k - 2];
-            HIPCK(c, hipEventRecord(e, sort_stream(k)));
-            HIPCK(c, hipStreamWaitEvent(c->stream, e, 0));
+        if ((rc = join_side(c))) return rc;
+        for (int k = 2; k < MSM_SORT_STREAMS; ++k) {
+            HIPCK(c, hipEventRecord(c->sort_events[(size_t)k - 2], sort_stream(k)));
+            HIPCK(c, hipStreamWaitEvent(c->stream, c->sort_events[(size_t)k - 2], 0));
         }
         HIPCK(c, hipMemsetAsync(lo, 0, (nbx + 1) * 8, c->stream));
         hipLaunchKernelGGL(msm_ranges16_kernel, dim3(grid_for((2 * n + MSM_RANGES_PER_THREAD - 1) / MSM_RANGES_PER_THREAD), W + 1), dim3(BLOCK), 0, c->stream,
@@ -369,9 +477,7 @@ int g1_msm_pippenger(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t*
     // The small-scalar bucket (index nbk) and the [r]phi(S) it owes, on the side stream while this one goes on to the bucket sums: ranges and
     // sorted values are final here.  ovf_cnt[2] = "term written"; longer buckets are left to the bucket kernel and msm_small_term_kernel.
     int32_t* small_term = (int32_t*)(ovf + 64);
-    if ((rc = ensure_fork_event(c))) return rc;
-    HIPCK(c, hipEventRecord(c->ev_chunk[0], c->stream));
-    HIPCK(c, hipStreamWaitEvent(c->side, c->ev_chunk[0], 0));
+    if ((rc = fork_side(c))) return rc;
     hipLaunchKernelGGL(msm_small_early_kernel, dim3(1), dim3(64), 0, c->side, (const uint32_t*)lo, (const uint32_t*)hi, (uint32_t)nbk, MSM_SMALL_EARLY_MAX,
                        (const uint32_t*)v1, (const int32_t*)pts2, small_term, ovf_cnt + 2);
     HIPCK(c, hipGetLastError());
@@ -399,11 +505,9 @@ int g1_msm_pippenger(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t*
     HIPCK(c, hipGetLastError());
     // a small-scalar bucket too long for the early kernel: its term from the bucket sum, on the side stream beside the window reductions
     // (returns at once when the early kernel has written the term)
-    HIPCK(c, hipEventRecord(c->ev_chunk[0], c->stream));
-    HIPCK(c, hipStreamWaitEvent(c->side, c->ev_chunk[0], 0));
+    if ((rc = fork_side(c))) return rc;
     hipLaunchKernelGGL(msm_small_term_kernel, dim3(1), dim3(64), 0, c->side, (const int32_t*)(bk + nbk * G1_ENT_DWORDS), small_term, (const uint32_t*)(ovf_cnt + 2));
     HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(c->ev_side, c->side));
     const uint32_t chunks = (uint32_t)((nb + MSM_CHUNK - 1) / MSM_CHUNK);
     size_t cur_n = (size_t)W * chunks, cur_stride = round_up(cur_n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_RED0, (size_t)3 * NL * cur_stride * 4))) return rc;
@@ -423,7 +527,7 @@ int g1_msm_pippenger(c12381_ctx* c, size_t n, const uint8_t* pts, const uint8_t*
         slot = slot == c12381_ctx::WS_RED0 ? c12381_ctx::WS_RED1 : c12381_ctx::WS_RED0;
     }
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * 64 * 4))) return rc;
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+    if ((rc = join_side(c))) return rc;                                    // the small-scalar term is written
     hipLaunchKernelGGL(msm_horner_kernel, dim3(1), dim3(64), 0, c->stream, cur, cur_stride, W, cb, (int32_t*)c->ws[c12381_ctx::WS_PROJ], (size_t)64,
                        (const int32_t*)small_term);
     HIPCK(c, hipGetLastError());
@@ -1093,19 +1197,21 @@ int c12381_pair_product_batch(c12381_ctx* c, size_t n, int k, const uint8_t* g1s
     if ((rc = c12381_pair_product_batch_dev(c, n, k, s.in[0], s.in[1], s.out[0], flags))) return rc;
     return unstage(c, s);
 }
-static int lines_table(c12381_ctx* c, int slot, const uint8_t* d_q192, int need_g2);
 // gt[i] = e(P_i, Q) with ONE G2 argument for the batch: the 69 line-coefficient triples of Q are computed once (and kept
 // until Q changes), every element then runs the table-driven Miller loop.  Same field elements as the running-point loop,
 // so the GT bytes equal c12381_pair_batch on n copies of Q for every Q, infinity included.
 int c12381_pair_fixed_g2_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2_192, uint8_t* gt) {
     int rc = bind(c); if (rc || (rc = pair_args(g1, g2_192, gt, 0u))) return rc;
     if (n == 0) return 0;
-    if ((rc = lines_table(c, c12381_ctx::WS_FQ_P, g2_192, 0))) return rc;
+    g2_cols q = {};
+    q.p[0] = g2_192;
+    cached t;
+    if ((rc = lines_tables(c, TA_FQ_P, 1, q, fq_rule(0), t))) return rc;
     uint4* st; unsigned int *fl, *ct; unsigned blocks;
     unsigned int ep;
     if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
     timed tm(c, 3);
-    hipLaunchKernelGGL(pair3_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, n, g1, (const int32_t*)c->ws[c12381_ctx::WS_FQ_P], gt, c->d_flag,
+    hipLaunchKernelGGL(pair3_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, n, g1, (const int32_t*)t.tabs, gt, c->d_flag,
                        st, fl, ct, pair_spin_limit(), ep);
     HIPCK(c, hipGetLastError());
     return 0;
@@ -1119,34 +1225,11 @@ int c12381_pair_fixed_g2_batch(c12381_ctx* c, size_t n, const uint8_t* g1, const
 }
 // ---------------------------------------------------------------- K-way products against fixed G2 points (k_pairk.hip)
 static_assert(C12381_FIXED_G2_MAX == FIXED_G2_MAX, "public and device bound of k");
-// WS_FQ_K: [gate: FQK_GATE_DWORDS][table 0] ... [table FIXED_G2_MAX - 1], each table a header (fixed_cache_check_kernel protocol) and 69 lines
-constexpr size_t FQK_GATE_DWORDS = 128;
-constexpr size_t FQK_TAB_DWORDS = (FB_HEADER_DWORDS + (size_t)FQ_TABLE_DWORDS + 63) / 64 * 64;
-static_assert(FB_HEADER_DWORDS == HDR_DWORDS, "line tables: header in front of the lines");
-// Tables of the k points q.p[c] (rule: bit 0 need_g2, bit 1 raw records, k_pairk.hip g2_lines_tablek_kernel), each kept until its point
-// or rule changes, and the gate over all k.  Queued on the stream; nothing waits for the host.
-static int lines_tables_k(c12381_ctx* c, int k, const g2_cols& q, int rule, const int32_t*& gate, const int32_t*& lines) {
-    const size_t bytes = (FQK_GATE_DWORDS + (size_t)FIXED_G2_MAX * FQK_TAB_DWORDS) * 4;
-    int rc;
-    if (c->ws_bytes[c12381_ctx::WS_FQ_K] < bytes) {
-        if ((rc = ensure(c, c12381_ctx::WS_FQ_K, bytes))) return rc;
-        HIPCK(c, hipMemsetAsync(c->ws[c12381_ctx::WS_FQ_K], 0, bytes, c->stream));      // no magic yet: first use of every table is a miss
-    }
-    int32_t* base = (int32_t*)c->ws[c12381_ctx::WS_FQ_K];
-    int32_t* tabs = base + FQK_GATE_DWORDS;
-    for (int j = 0; j < k; ++j)
-        hipLaunchKernelGGL(fixed_cache_check_kernel, dim3(1), dim3(64), 0, c->stream, q.p[j], 192, tabs + (size_t)j * FQK_TAB_DWORDS);
-    hipLaunchKernelGGL(g2_lines_tablek_kernel, dim3(1), dim3(BLOCK), 0, c->stream, k, q, tabs, (int)FQK_TAB_DWORDS, rule);
-    hipLaunchKernelGGL(gatek_kernel, dim3(1), dim3(BLOCK), 0, c->stream, base, (const int32_t*)tabs, (int)FQK_TAB_DWORDS, k);
-    HIPCK(c, hipGetLastError());
-    gate = base;
-    lines = tabs + HDR_DWORDS;
-    return 0;
-}
 // The prep kernel (G1 columns -> records, skipped when prep_skip says so) and the K-way queue kernel: GT output (eq = false; gate[HDR_VALID]
 // = 0 poisons every lane) or the boolean (eq = true; runs only when gate[HDR_VALID] != 0).
-static int launch_prodk(c12381_ctx* c, size_t n, int k, const g1_cols& cols, uint32_t neg_mask, const int32_t* gate, const int32_t* lines, uint8_t* out,
-                        bool eq, bool miller_only, const int32_t* prep_skip) {
+static int launch_prodk(c12381_ctx* c, size_t n, int k, const g1_cols& cols, uint32_t neg_mask, const cached& t, uint8_t* out, bool eq, bool miller_only,
+                        const int32_t* prep_skip) {
+    const int32_t *gate = t.gate, *lines = t.tabs + HDR_DWORDS;
     const size_t rec_bytes = round_up((size_t)k * n * FQK_PT_DWORDS * 4, 256);
     int rc;
     if ((rc = ensure(c, c12381_ctx::WS_FQK_PTS, rec_bytes + round_up(n * 4, 256)))) return rc;
@@ -1160,10 +1243,10 @@ static int launch_prodk(c12381_ctx* c, size_t n, int k, const g1_cols& cols, uin
     const size_t ndirect = queue_direct_groups_host(groups, (size_t)blocks * (BLOCK / 64));
     if (eq)
         hipLaunchKernelGGL(pair3_prodk_fixed_eq_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines,
-                           (int)FQK_TAB_DWORDS, out, c->d_flag, st, fl, ct, gate, ndirect, pair_spin_limit(), ep);
+                           t.stride, out, c->d_flag, st, fl, ct, gate, ndirect, pair_spin_limit(), ep);
     else
         hipLaunchKernelGGL(pair3_prodk_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines,
-                           (int)FQK_TAB_DWORDS, out, c->d_flag, st, fl, ct, gate, ndirect, miller_only ? 1 : 0, pair_spin_limit(), ep);
+                           t.stride, out, c->d_flag, st, fl, ct, gate, ndirect, miller_only ? 1 : 0, pair_spin_limit(), ep);
     HIPCK(c, hipGetLastError());
     return 0;
 }
@@ -1179,10 +1262,10 @@ int c12381_pair_product_fixed_g2_batch_dev(c12381_ctx* c, size_t n, int k, const
     g1_cols cols = {};
     g2_cols q = {};
     for (int j = 0; j < k; ++j) { cols.p[j] = g1s + (size_t)96 * n * j; q.p[j] = g2s + (size_t)192 * j; }
-    const int32_t *gate, *lines;
-    if ((rc = lines_tables_k(c, k, q, miller_only ? 2 : 0, gate, lines))) return rc;
+    cached t;
+    if ((rc = lines_tables(c, TA_FQ_K, k, q, miller_only ? 2 : 0, t))) return rc;
     timed tm(c, 3);
-    return launch_prodk(c, n, k, cols, 0u, gate, lines, gt, false, miller_only, nullptr);
+    return launch_prodk(c, n, k, cols, 0u, t, gt, false, miller_only, nullptr);
 }
 int c12381_pair_product_fixed_g2_batch(c12381_ctx* c, size_t n, int k, const uint8_t* g1s, const uint8_t* g2s, uint8_t* gt, unsigned flags) {
     int rc = bind(c); if (rc || (rc = pair_product_fixed_args(k, g1s, g2s, gt, flags))) return rc;
@@ -1210,15 +1293,15 @@ int c12381_ps_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8
     if (n == 0) return 0;
     const bool fast = nmsg + 2 <= (size_t)C12381_FIXED_G2_MAX;
     const int k = (int)nmsg + 2;
-    const int32_t *gate_generic = nullptr, *gate_fast = nullptr, *lines = nullptr;
+    const int32_t *gate_generic = nullptr, *gate_fast = nullptr;
+    cached t = {};
     if (fast) {
         g2_cols q = {};
         q.p[0] = g2_192; q.p[1] = X2_192;
         for (size_t i = 0; i < nmsg; ++i) q.p[2 + i] = Y2_192 + 192 * i;
-        const int32_t* gate;
-        if ((rc = lines_tables_k(c, k, q, 1, gate, lines))) return rc;
-        gate_generic = gate;                  // generic kernels: skip when every table is valid
-        gate_fast = gate + GATE_OTHER;        // fast-route kernels with a skip pointer: skip when one is not
+        if ((rc = lines_tables(c, TA_FQ_K, k, q, 1, t))) return rc;
+        gate_generic = t.gate;                // generic kernels: skip when every table is valid
+        gate_fast = t.gate + GATE_OTHER;      // fast-route kernels with a skip pointer: skip when one is not
     }
     // generic route: W = X2 + sum_i m_i Y2_i (WS_BBS_Q), each product in WS_BBS_B
     if ((rc = ensure(c, c12381_ctx::WS_BBS_Q, 192 * n))) return rc;
@@ -1250,7 +1333,7 @@ int c12381_ps_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8
             for (size_t i = 0; i < nmsg; ++i) cols.p[2 + i] = d_m + 96 * n * i;
         }
         timed tm(c, 4);
-        if ((rc = launch_prodk(c, n, k, cols, 1u, gate_generic, lines, ok, true, false, gate_fast))) return rc;
+        if ((rc = launch_prodk(c, n, k, cols, 1u, t, ok, true, false, gate_fast))) return rc;
     }
     timed tm(c, 4);
     return launch_pair_eq(c, n, s1_96, d_w, s2_96, g2_192, (size_t)0, ok, gate_generic);
@@ -1521,60 +1604,15 @@ int c12381_gt_is_unity_batch(c12381_ctx* c, size_t n, const uint8_t* a576, uint8
     return unstage(c, s);
 }
 
-// Fixed-base tables (fixed_base.hpp): make sure slot `slot` holds the table of the point at `d_base`; everything is
-// queued on the stream (the "same base as last time?" comparison runs on the device), nothing waits for the host.
-static int fixed_table(c12381_ctx* c, int slot, const uint8_t* d_base, bool is_g2) {
-    const size_t entries = (size_t)(is_g2 ? FB_G2_WINDOWS : FB_G1_WINDOWS) * FB_ENTRIES;
-    const size_t dwords = FB_HEADER_DWORDS + entries * (size_t)(is_g2 ? FB_G2_DWORDS : FB_G1_DWORDS);
-    int rc;
-    if (c->ws_bytes[slot] < dwords * 4) {
-        if ((rc = ensure(c, slot, dwords * 4))) return rc;
-        HIPCK(c, hipMemsetAsync(c->ws[slot], 0, FB_HEADER_DWORDS * 4, c->stream));      // no magic yet: first use is a miss
-    }
-    int32_t* buf = (int32_t*)c->ws[slot];
-    hipLaunchKernelGGL(fixed_cache_check_kernel, dim3(1), dim3(64), 0, c->stream, d_base, is_g2 ? 192 : 96, buf);
-    HIPCK(c, hipGetLastError());
-    if (is_g2) hipLaunchKernelGGL(g2_fixed_table_kernel, dim3(grid_for(entries)), dim3(BLOCK), 0, c->stream, d_base, buf);
-    else hipLaunchKernelGGL(g1_fixed_table_kernel, dim3(grid_for(entries)), dim3(BLOCK), 0, c->stream, d_base, buf);
-    HIPCK(c, hipGetLastError());
-    return 0;
-}
-// Coefficient table of a fixed G2 argument of the Miller loop (pairing3.hpp): same header / cache protocol as above.
-static int lines_table(c12381_ctx* c, int slot, const uint8_t* d_q192, int need_g2) {
-    const size_t dwords = FB_HEADER_DWORDS + (size_t)FQ_TABLE_DWORDS;
-    int rc;
-    if (c->ws_bytes[slot] < dwords * 4) {
-        if ((rc = ensure(c, slot, dwords * 4))) return rc;
-        HIPCK(c, hipMemsetAsync(c->ws[slot], 0, FB_HEADER_DWORDS * 4, c->stream));
-    }
-    int32_t* buf = (int32_t*)c->ws[slot];
-    hipLaunchKernelGGL(fixed_cache_check_kernel, dim3(1), dim3(64), 0, c->stream, d_q192, 192, buf);
-    HIPCK(c, hipGetLastError());
-    static const int raw = [] { const char* e = tuning_env("C12381_FQ_RAW"); return (e && e[0] == '1') ? 4 : 0; }();
-    hipLaunchKernelGGL(g2_lines_table_kernel, dim3(1), dim3(BLOCK), 0, c->stream, d_q192, buf, need_g2 | raw);
-    HIPCK(c, hipGetLastError());
-    return 0;
-}
-static bool fixed_base_enabled() {
-    static const bool on = [] { const char* e = tuning_env("C12381_FIXED_BASE"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 // ---------------------------------------------------------------- one base for the whole batch (g^x_i)
 int c12381_g1_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base96, const uint8_t* sc, uint8_t* out, int fmt) {
     int rc = bind(c); if (rc || (rc = g1_mul_args(base96, sc, out, fmt, 0u))) return rc;
     if (n == 0) return 0;
     const size_t stride = round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
-    const int32_t* skip = nullptr;
-    if (fixed_base_enabled()) {
-        if ((rc = fixed_table(c, c12381_ctx::WS_FB_G1_0, base96, false))) return rc;
-        skip = (const int32_t*)c->ws[c12381_ctx::WS_FB_G1_0];
-        hipLaunchKernelGGL(g1_fixed_eval_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, skip, sc, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride,
-                           (size_t)0);
-        HIPCK(c, hipGetLastError());
-    }
-    if ((rc = g1_mul_to_proj(c, n, base96, sc, stride, 0, 0, skip))) return rc;
+    const bool fb = fixed_base_enabled();
+    if (fb && (rc = g1_fixed_table(c, 0, base96))) return rc;
+    if ((rc = g1_fixed_column(c, n, base96, 0, sc, stride, 0, fb))) return rc;
     return g1_finish(c, n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, out, fmt);
 }
 int c12381_g1_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base96, const uint8_t* sc, uint8_t* out, int fmt) {
@@ -1585,16 +1623,14 @@ int c12381_g1_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base96, co
     return unstage(c, s);
 }
 // ---------------------------------------------------------------- per-lane sums over a set of bases shared by the batch
-// out[j] = addend + sum_(i < nb) sc[i n + j] B_i.  WS_FB_G1_SUM: [gate: FBS_GATE_DWORDS][table 0] ... [table G1_FIXED_SUM_MAX - 1], each table
-// a header (fixed_cache_check_kernel protocol, per position: changing one base rebuilds one table) and the 4080 multiples of fixed_base.hpp.
+// out[j] = addend + sum_(i < nb) sc[i n + j] B_i.  TA_FB_G1_SUM: a gate and G1_FIXED_SUM_MAX tables of the 4080 multiples of fixed_base.hpp, cached
+// per position (changing one base rebuilds one table).
 // One cache-check launch, one table launch and one gate launch whatever nb; then BOTH routes are queued and the gate lets one run:
 //   every base a subgroup point   g1_fixed_sum_kernel: all nb tables into one accumulator per lane
 //   otherwise                     the columns through the generic kernel one by one, each folded into proj[0, n) (two projective arrays
 //                                 whatever nb), as bbs_message_points sums its columns
 // The skipped route's kernels return at their first load.  Nothing waits for the host.
 static_assert(C12381_G1_FIXED_SUM_MAX == G1_FIXED_SUM_MAX, "public and device bound of nb");
-constexpr size_t FBS_GATE_DWORDS = 128;
-constexpr size_t FBS_TAB_DWORDS = (FB_HEADER_DWORDS + (size_t)FB_G1_WINDOWS * FB_ENTRIES * FB_G1_DWORDS + 63) / 64 * 64;
 static int g1_fixed_sum_args(size_t nb, const void* bases, const void* sc, const void* out, int fmt) {
     return (nb < 1 || nb > C12381_G1_FIXED_SUM_MAX || !bases || !sc || !out || !g1_fmt(fmt)) ? C12381_E_ARG : 0;
 }
@@ -1602,34 +1638,23 @@ int c12381_g1_mul_fixed_sum_batch_dev(c12381_ctx* c, size_t n, size_t nb, const 
                                       int fmt) {
     int rc = bind(c); if (rc || (rc = g1_fixed_sum_args(nb, bases96, sc, out, fmt))) return rc;
     if (n == 0) return 0;
-    const size_t bytes = (FBS_GATE_DWORDS + (size_t)G1_FIXED_SUM_MAX * FBS_TAB_DWORDS) * 4;
-    if (c->ws_bytes[c12381_ctx::WS_FB_G1_SUM] < bytes) {
-        if ((rc = ensure(c, c12381_ctx::WS_FB_G1_SUM, bytes))) return rc;
-        HIPCK(c, hipMemsetAsync(c->ws[c12381_ctx::WS_FB_G1_SUM], 0, bytes, c->stream));      // no magic yet: first use of every table is a miss
-    }
-    int32_t* gate = (int32_t*)c->ws[c12381_ctx::WS_FB_G1_SUM];
-    int32_t* tabs = gate + FBS_GATE_DWORDS;
+    const bool fb = fixed_base_enabled();
+    cached t;
+    if ((rc = g1_fixed_tables(c, TA_FB_G1_SUM, fb ? (int)nb : 0, bases96, t))) return rc;       // without tables: the gate buffer alone
+    const int32_t *gate = t.gate, *tabs = t.tabs;
     const size_t half = round_up(n, 64), stride = 2 * half;       // proj[0, n): the sums; proj[half, half + n): the generic route's current column
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
     int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
-    const bool fb = fixed_base_enabled();
-    if (fb) {
-        hipLaunchKernelGGL(fixed_cache_checkk_kernel, dim3((unsigned)nb), dim3(64), 0, c->stream, bases96, 96, tabs, (int)FBS_TAB_DWORDS);
-        hipLaunchKernelGGL(g1_fixed_tablek_kernel, dim3(grid_for((size_t)FB_G1_WINDOWS * FB_ENTRIES), (unsigned)nb), dim3(BLOCK), 0, c->stream, bases96, tabs,
-                           (int)FBS_TAB_DWORDS);
-    }
-    hipLaunchKernelGGL(g1_fixed_sum_gate_kernel, dim3(1), dim3(64), 0, c->stream, (int)nb, bases96, addend96, gate, (const int32_t*)tabs, (int)FBS_TAB_DWORDS,
-                       fb ? 1 : 0, c->d_flag);
+    hipLaunchKernelGGL(g1_fixed_sum_gate_kernel, dim3(1), dim3(64), 0, c->stream, (int)nb, bases96, addend96, t.gate, tabs, t.stride, fb ? 1 : 0, c->d_flag);
     HIPCK(c, hipGetLastError());
     if (fb) {
-        hipLaunchKernelGGL(g1_fixed_sum_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (int)nb, (const int32_t*)gate, (const int32_t*)tabs,
-                           (int)FBS_TAB_DWORDS, sc, addend96, proj, stride);
+        hipLaunchKernelGGL(g1_fixed_sum_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (int)nb, gate, tabs, t.stride, sc, addend96, proj, stride);
         HIPCK(c, hipGetLastError());
     }
     for (size_t col = 0; col < nb; ++col) {
         if ((rc = g1_mul_to_proj(c, n, bases96 + 96 * col, sc + 32 * n * col, stride, 0, col ? half : 0, gate))) return rc;
         if (col == 0 && nb > 1) continue;                          // the first column is written in place
-        hipLaunchKernelGGL(g1_fixed_sum_fold_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (const int32_t*)gate, proj, stride, half, col ? 1 : 0,
+        hipLaunchKernelGGL(g1_fixed_sum_fold_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, gate, proj, stride, half, col ? 1 : 0,
                            col + 1 == nb ? 1 : 0, addend96);
         HIPCK(c, hipGetLastError());
     }
@@ -1650,8 +1675,9 @@ int c12381_g2_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base19
     const size_t stride = round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)6 * NL * stride * 4))) return rc;
     if (fixed_base_enabled()) {
-        if ((rc = fixed_table(c, c12381_ctx::WS_FB_G2, base192, true))) return rc;
-        skip = (const int32_t*)c->ws[c12381_ctx::WS_FB_G2];
+        cached t;
+        if ((rc = g2_fixed_table(c, base192, t))) return rc;
+        skip = t.tabs;
         hipLaunchKernelGGL(g2_fixed_eval_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, skip, sc, (const uint8_t*)nullptr, out, fmt, c->d_flag,
                            (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride);
         HIPCK(c, hipGetLastError());
@@ -1679,16 +1705,9 @@ static int bbs_message_points(c12381_ctx* c, size_t n, size_t nmsg, const uint8_
     for (size_t col = 0; col < cols; ++col) {
         const uint8_t* base = col == 0 ? h0_96 : h_96 + 96 * (col - 1);
         const uint8_t* sc = col == 0 ? r_32 : m_32 + 32 * n * (col - 1);
-        const int32_t* skip = nullptr;
-        if (fb && col < 4) {                                   // table slots for h0 and the first three h_i
-            const int slot = c12381_ctx::WS_FB_G1_0 + (int)col;
-            if ((rc = fixed_table(c, slot, base, false))) return rc;
-            skip = (const int32_t*)c->ws[slot];
-            hipLaunchKernelGGL(g1_fixed_eval_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, skip, sc, (int32_t*)c->ws[c12381_ctx::WS_PROJ],
-                               stride, col * n);
-            HIPCK(c, hipGetLastError());
-        }
-        if ((rc = g1_mul_to_proj(c, n, base, sc, stride, 0, col * n, skip))) return rc;
+        const bool tab = fb && col < 4;                        // table slots for h0 and the first three h_i, the generic kernel beyond
+        if (tab && (rc = g1_fixed_table(c, (int)col, base))) return rc;
+        if ((rc = g1_fixed_column(c, n, base, (int)col, sc, stride, col * n, tab))) return rc;
     }
     rstride = round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_RED0, (size_t)3 * NL * rstride * 4))) return rc;
@@ -1728,22 +1747,18 @@ int c12381_bbs_plus_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const
     const bool fb = fixed_base_enabled();
     const bool fq = fb && pair_lanes() != 1;
     const int32_t *gate_fast = nullptr, *gate_generic = nullptr;      // skip_if pointers: skip when [HDR_VALID] != 0
+    cached lines = {};
     if (fq) {
-        if ((rc = lines_table(c, c12381_ctx::WS_FQ_W, w_192, 1))) return rc;
-        if ((rc = lines_table(c, c12381_ctx::WS_FQ_G, g2_192, 1))) return rc;
-        if ((rc = ensure(c, c12381_ctx::WS_FQ_GATE, 128 * 4))) return rc;
-        int32_t* gate = (int32_t*)c->ws[c12381_ctx::WS_FQ_GATE];
-        hipLaunchKernelGGL(gate_and_kernel, dim3(1), dim3(BLOCK), 0, c->stream, gate, (const int32_t*)c->ws[c12381_ctx::WS_FQ_W],
-                           (const int32_t*)c->ws[c12381_ctx::WS_FQ_G]);
-        HIPCK(c, hipGetLastError());
-        gate_generic = gate;          // generic kernels: skip when the fixed-G2 path is valid
-        gate_fast = gate + GATE_OTHER;        // kernels that exist only for the fixed-G2 path and take a skip pointer: skip when it is not
+        if ((rc = bbs_lines_tables(c, w_192, g2_192, lines))) return rc;
+        gate_generic = lines.gate;            // generic kernels: skip when the fixed-G2 path is valid
+        gate_fast = lines.gate + GATE_OTHER;  // kernels that exist only for the fixed-G2 path and take a skip pointer: skip when it is not
     }
     // generic path: Q_j = w + x_j g2 (g2's multiples from its fixed-base table when it is a subgroup point)
     const int32_t* skip_g2 = nullptr;
     if (fb && !fq) {
-        if ((rc = fixed_table(c, c12381_ctx::WS_FB_G2, g2_192, true))) return rc;
-        skip_g2 = (const int32_t*)c->ws[c12381_ctx::WS_FB_G2];
+        cached t;
+        if ((rc = g2_fixed_table(c, g2_192, t))) return rc;
+        skip_g2 = t.tabs;
         hipLaunchKernelGGL(g2_fixed_eval_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, skip_g2, x_32, w_192, d_q, 192, c->d_flag, (int32_t*)nullptr, (size_t)0);
         HIPCK(c, hipGetLastError());
     }
@@ -1765,8 +1780,8 @@ int c12381_bbs_plus_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const
         uint4* st; unsigned int *fl, *ct, ep; unsigned blocks;
         if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
         hipLaunchKernelGGL(pair3_prod_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, n, A_96, d_b,
-                           (const int32_t*)c->ws[c12381_ctx::WS_FQ_W] + FB_HEADER_DWORDS, (const int32_t*)c->ws[c12381_ctx::WS_FQ_G] + FB_HEADER_DWORDS, ok,
-                           c->d_flag, st, fl, ct, gate_generic, pair_spin_limit(), ep);
+                           (const int32_t*)lines.tabs + HDR_DWORDS, (const int32_t*)lines.tabs + lines.stride + HDR_DWORDS, ok, c->d_flag, st, fl, ct,
+                           gate_generic, pair_spin_limit(), ep);
         HIPCK(c, hipGetLastError());
     }
     return launch_pair_eq(c, n, A_96, d_q, d_b, g2_192, (size_t)0, ok, gate_generic);
@@ -1806,19 +1821,16 @@ int c12381_bbs_plus_verify_wire_batch_dev(c12381_ctx* c, size_t n, size_t nh, si
     uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS_WIRE];
     // The handful of public points decode on the side stream: two square-root chains of one lane each (0.4 + 0.85 ms of pure latency) beside
     // the parsing and the n square roots of the signatures' A on the context's stream, instead of in front of them.
-    if ((rc = ensure_fork_event(c))) return rc;
-    HIPCK(c, hipEventRecord(c->ev_chunk[0], c->stream));                    // the caller's inputs are ordered on the context's stream
-    HIPCK(c, hipStreamWaitEvent(c->side, c->ev_chunk[0], 0));
+    if ((rc = fork_side(c))) return rc;                                     // the caller's inputs are ordered on the context's stream
     hipLaunchKernelGGL(bbs_wire_pub_kernel, dim3(grid_for(49 * npub1 + 2 * 97)), dim3(BLOCK), 0, c->side, nblk, g1_g2_h0_195, h_49, pk_97, d + o_p49, d + o_p97);
     HIPCK(c, hipGetLastError());
     hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(npub1)), dim3(BLOCK), 0, c->side, npub1, d + o_p49, d + o_p96, d + o_st1, 0);
     hipLaunchKernelGGL(g2_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)2, d + o_p97, d + o_p192, d + o_st2, 0);
     HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(c->ev_side, c->side));
     hipLaunchKernelGGL(bbs_wire_prep_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, msg_len, nblk, sig_145, msgs, d + o_a49, d + o_x, d + o_r, d + o_m, d + o_ss);
     hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, d + o_a49, d + o_A, d + o_sa, 0);
     HIPCK(c, hipGetLastError());
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+    if ((rc = join_side(c))) return rc;
     if ((rc = c12381_bbs_plus_verify_batch_dev(c, n, nblk, d + o_p96, d + o_p192, d + o_p96 + 96, d + o_p96 + 192, d + o_p192 + 192, d + o_A, d + o_x, d + o_r,
                                                d + o_m, ok))) return rc;
     hipLaunchKernelGGL(bbs_wire_finish_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, npub1, d + o_ss, d + o_sa, d + o_st1, d + o_st2, ok, c->d_flag);
@@ -1858,13 +1870,8 @@ int c12381_bbs_plus_verify_aggregate_dev(c12381_ctx* c, size_t n, size_t nmsg, c
     const size_t terms = n + nmsg + 2;
     if (n == 0) { HIPCK(c, hipMemsetAsync(all_ok, 1, 1, c->stream)); return 0; }
     HIPCK(c, hipMemsetAsync(all_ok, 0, 1, c->stream));
-    if ((rc = lines_table(c, c12381_ctx::WS_FQ_W, w_192, 1))) return rc;
-    if ((rc = lines_table(c, c12381_ctx::WS_FQ_G, g2_192, 1))) return rc;
-    if ((rc = ensure(c, c12381_ctx::WS_FQ_GATE, 128 * 4))) return rc;
-    int32_t* gate = (int32_t*)c->ws[c12381_ctx::WS_FQ_GATE];
-    hipLaunchKernelGGL(gate_and_kernel, dim3(1), dim3(BLOCK), 0, c->stream, gate, (const int32_t*)c->ws[c12381_ctx::WS_FQ_W],
-                       (const int32_t*)c->ws[c12381_ctx::WS_FQ_G]);
-    HIPCK(c, hipGetLastError());
+    cached lines;
+    if ((rc = bbs_lines_tables(c, w_192, g2_192, lines))) return rc;
     const size_t o_p = round_up(96 * terms, 256);
     if ((rc = ensure(c, c12381_ctx::WS_BBS_B, o_p + 256))) return rc;
     if ((rc = ensure(c, c12381_ctx::WS_BBS_Q, 32 * terms))) return rc;
@@ -1903,8 +1910,8 @@ int c12381_bbs_plus_verify_aggregate_dev(c12381_ctx* c, size_t n, size_t nmsg, c
     uint4* st; unsigned int *fl, *ct, ep; unsigned blocks;
     if ((rc = pair_queue_setup(c, 1, st, fl, ct, blocks, &ep))) return rc;
     hipLaunchKernelGGL(pair3_prod_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), 0, c->stream, (size_t)1, (const uint8_t*)p1, (const uint8_t*)p2,
-                       (const int32_t*)c->ws[c12381_ctx::WS_FQ_W] + FB_HEADER_DWORDS, (const int32_t*)c->ws[c12381_ctx::WS_FQ_G] + FB_HEADER_DWORDS, all_ok,
-                       c->d_flag, st, fl, ct, (const int32_t*)gate, pair_spin_limit(), ep);
+                       (const int32_t*)lines.tabs + HDR_DWORDS, (const int32_t*)lines.tabs + lines.stride + HDR_DWORDS, all_ok, c->d_flag, st, fl, ct,
+                       (const int32_t*)lines.gate, pair_spin_limit(), ep);
     HIPCK(c, hipGetLastError());
     return 0;
 }
@@ -1986,28 +1993,40 @@ int c12381_sha3_512_batch(c12381_ctx* c, size_t n, size_t len, const uint8_t* ms
 // BBS04_PUB_BYTES of decoded public points and, per signature of a chunk, bbs04_sig_bytes(msg_len) bytes (T records, 13 scalar columns,
 // statuses, R and P points, GT value, transcript); the shared scalar-multiplication workspaces hold 13 projective points per signature.
 constexpr size_t BBS04_CHUNK = (size_t)1 << 18;
-constexpr size_t BBS04_PUB_BYTES = 2048;       // [0] 4 x 49 G1 wire | [256] 2 x 97 G2 wire | [512] g1, h, u, v (96 B) | [1024] g2, w (192 B) | [1536] 6 statuses
+constexpr size_t BBS04_PUB_BYTES = 2048;
+// the public block at the start of WS_BBS04: gpk's points as they arrive, decoded, and the six status bytes of the decoding
+struct bbs04_public {
+    uint8_t *wire_g1, *wire_g2;          // 4 x 49 B (g1, h, u, v), 2 x 97 B (g2, w)
+    uint8_t *g1, *h, *u, *v;             // 96 B each, contiguous from g1
+    uint8_t *g2_w;                       // g2, w: 192 B each
+    uint8_t* st;                         // 4 G1 statuses, 2 G2 statuses
+    explicit bbs04_public(uint8_t* d)
+        : wire_g1(d), wire_g2(d + 256), g1(d + 512), h(g1 + 96), u(g1 + 192), v(g1 + 288), g2_w(d + 1024), st(d + 1536) {}
+};
+// A slab of WS_BBS04 behind the public block: every entry takes its fields in order, each rounded to 256 bytes; `bytes` is the size so far
+// (base = nullptr: sizing only)
+struct bbs04_fields {
+    uint8_t* base; size_t bytes = BBS04_PUB_BYTES;
+    uint8_t* take(size_t n) { uint8_t* p = base ? base + bytes : nullptr; bytes = round_up(bytes + n, 256); return p; }
+};
 struct bbs04_slab { uint8_t *t49, *t96, *sc, *c32, *st, *st_t, *r49, *p96, *gt, *tr; size_t bytes; };
 static bbs04_slab bbs04_layout(uint8_t* base, size_t m, size_t msg_len) {
+    bbs04_fields f{base};
     bbs04_slab s;
-    size_t o = BBS04_PUB_BYTES;
-    auto take = [&](uint8_t*& p, size_t bytes) { p = base ? base + o : nullptr; o = round_up(o + bytes, 256); };
-    take(s.t49, 3 * 49 * m); take(s.t96, 6 * 96 * m); take(s.sc, 13 * 32 * m); take(s.c32, 32 * m); take(s.st, m); take(s.st_t, 3 * m);
-    take(s.r49, 4 * 49 * m); take(s.p96, 2 * 96 * m); take(s.gt, 576 * m); take(s.tr, (msg_len + 919) * m);
-    s.bytes = o;
+    s.t49 = f.take(3 * 49 * m); s.t96 = f.take(6 * 96 * m); s.sc = f.take(13 * 32 * m); s.c32 = f.take(32 * m); s.st = f.take(m); s.st_t = f.take(3 * m);
+    s.r49 = f.take(4 * 49 * m); s.p96 = f.take(2 * 96 * m); s.gt = f.take(576 * m); s.tr = f.take((msg_len + 919) * m);
+    s.bytes = f.bytes;
     return s;
 }
-// the public points on the side stream (two short square-root chains beside the per-signature work on the context's stream)
-static int bbs04_pub(c12381_ctx* c, const uint8_t* gpk, uint8_t* d) {
+// the public points on the side stream (two short square-root chains beside the per-signature work on the context's stream); the caller
+// joins the side stream before its first use of them
+static int bbs04_pub(c12381_ctx* c, const uint8_t* gpk, const bbs04_public& pub) {
     int rc;
-    if ((rc = ensure_fork_event(c))) return rc;
-    HIPCK(c, hipEventRecord(c->ev_chunk[0], c->stream));
-    HIPCK(c, hipStreamWaitEvent(c->side, c->ev_chunk[0], 0));
-    hipLaunchKernelGGL(bbs04_pub_kernel, dim3(grid_for(4 * 49 + 2 * 97)), dim3(BLOCK), 0, c->side, gpk, d, d + 256);
-    hipLaunchKernelGGL(g1_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)4, d, d + 512, d + 1536, 0);
-    hipLaunchKernelGGL(g2_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)2, d + 256, d + 1024, d + 1540, 0);
+    if ((rc = fork_side(c))) return rc;
+    hipLaunchKernelGGL(bbs04_pub_kernel, dim3(grid_for(4 * 49 + 2 * 97)), dim3(BLOCK), 0, c->side, gpk, pub.wire_g1, pub.wire_g2);
+    hipLaunchKernelGGL(g1_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)4, pub.wire_g1, pub.g1, pub.st, 0);
+    hipLaunchKernelGGL(g2_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)2, pub.wire_g2, pub.g2_w, pub.st + 4, 0);
     HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(c->ev_side, c->side));
     return 0;
 }
 static int bbs04_verify_args(size_t msg_len, const void* gpk, const void* sig, const void* msgs, const void* ok) {
@@ -2020,8 +2039,8 @@ int c12381_bbs04_verify_batch_dev(c12381_ctx* c, size_t n, size_t msg_len, const
     const size_t ch = n < BBS04_CHUNK ? n : BBS04_CHUNK, L = msg_len + 919;
     if ((rc = ensure(c, c12381_ctx::WS_BBS04, bbs04_layout(nullptr, ch, msg_len).bytes))) return rc;
     uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS04];
-    if ((rc = bbs04_pub(c, gpk_390, d))) return rc;
-    const uint8_t *g1 = d + 512, *h = d + 512 + 96, *u = d + 512 + 192, *v = d + 512 + 288;
+    const bbs04_public pub(d);
+    if ((rc = bbs04_pub(c, gpk_390, pub))) return rc;
     const bool fb = fixed_base_enabled();
     for (size_t off = 0; off < n; off += ch) {
         const size_t m = n - off < ch ? n - off : ch;
@@ -2031,37 +2050,28 @@ int c12381_bbs04_verify_batch_dev(c12381_ctx* c, size_t n, size_t msg_len, const
         HIPCK(c, hipGetLastError());
         // variable bases T1, T2, T3, T1, T2, T3 against scalar columns 0-5: one launch of 6 m lanes
         HIPCK(c, hipMemcpyAsync(s.t96 + 3 * 96 * m, s.t96, 3 * 96 * m, hipMemcpyDeviceToDevice, c->stream));
-        if (off == 0) HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        if (off == 0 && (rc = join_side(c))) return rc;
         const size_t stride = round_up(13 * m, 64);
         if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
         if ((rc = g1_mul_to_proj(c, 6 * m, s.t96, s.sc, stride))) return rc;
         // fixed bases: columns 6-12 (u, v, u, v, h, g1, h); table slots u -> 0, v -> 1, h -> 2, g1 -> 3
-        const uint8_t* base[7] = {u, v, u, v, h, g1, h};
+        const uint8_t* tab[4] = {pub.u, pub.v, pub.h, pub.g1};
         const int slot[7] = {0, 1, 0, 1, 2, 3, 2};
         if (fb)
             for (int t = 0; t < 4; ++t)
-                if ((rc = fixed_table(c, c12381_ctx::WS_FB_G1_0 + t, t == 0 ? u : (t == 1 ? v : (t == 2 ? h : g1)), false))) return rc;
-        for (int k = 0; k < 7; ++k) {
-            const size_t col = 6 + (size_t)k;
-            const int32_t* skip = nullptr;
-            if (fb) {
-                skip = (const int32_t*)c->ws[c12381_ctx::WS_FB_G1_0 + slot[k]];
-                hipLaunchKernelGGL(g1_fixed_eval_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, skip, s.sc + 32 * col * m,
-                                   (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, col * m);
-                HIPCK(c, hipGetLastError());
-            }
-            if ((rc = g1_mul_to_proj(c, m, base[k], s.sc + 32 * col * m, stride, 0, col * m, skip))) return rc;
-        }
+                if ((rc = g1_fixed_table(c, t, tab[t]))) return rc;
+        for (size_t col = 6; col < 13; ++col)
+            if ((rc = g1_fixed_column(c, m, tab[slot[col - 6]], slot[col - 6], s.sc + 32 * col * m, stride, col * m, fb))) return rc;
         int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
         hipLaunchKernelGGL(bbs04_combine_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, proj, stride);
         HIPCK(c, hipGetLastError());
         if ((rc = g1_finish(c, 4 * m, proj, stride, s.r49, 49))) return rc;
         if ((rc = g1_finish(c, 2 * m, proj + 4 * m, stride, s.p96, 96))) return rc;
-        if ((rc = c12381_pair_product_fixed_g2_batch_dev(c, m, 2, s.p96, d + 1024, s.gt, 0u))) return rc;
+        if ((rc = c12381_pair_product_fixed_g2_batch_dev(c, m, 2, s.p96, pub.g2_w, s.gt, 0u))) return rc;
         const size_t bytes = m * L;
         hipLaunchKernelGGL(bbs04_transcript_kernel, dim3(grid_for(bytes)), dim3(BLOCK), 0, c->stream, m, msg_len, msg_len ? msgs + msg_len * off : msgs,
                            s.t49, s.t96, s.r49, s.gt, s.tr);
-        hipLaunchKernelGGL(bbs04_check_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, L, s.tr, s.c32, s.st, s.st_t, d + 1536, ok + off, c->d_flag);
+        hipLaunchKernelGGL(bbs04_check_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, L, s.tr, s.c32, s.st, s.st_t, pub.st, ok + off, c->d_flag);
         HIPCK(c, hipGetLastError());
     }
     return 0;
@@ -2118,25 +2128,12 @@ int c12381_bbs04_open_batch(c12381_ctx* c, size_t n, const uint8_t* gmsk_96, con
 // per signature of a chunk, bbs04_sign_layout's 2848 + msg_len bytes; the scalar-multiplication workspace holds 9 projective points.
 struct bbs04_sign_slab { uint8_t *a49, *a96, *st_a, *sc, *t49, *t96, *r49, *p96, *gt, *tr; size_t bytes; };
 static bbs04_sign_slab bbs04_sign_layout(uint8_t* base, size_t m, size_t msg_len) {
+    bbs04_fields f{base};
     bbs04_sign_slab s;
-    size_t o = BBS04_PUB_BYTES;
-    auto take = [&](uint8_t*& p, size_t bytes) { p = base ? base + o : nullptr; o = round_up(o + bytes, 256); };
-    take(s.a49, 49 * m); take(s.a96, 96 * m); take(s.st_a, m); take(s.sc, 12 * 32 * m); take(s.t49, 3 * 49 * m); take(s.t96, 3 * 96 * m);
-    take(s.r49, 4 * 49 * m); take(s.p96, 2 * 96 * m); take(s.gt, 576 * m); take(s.tr, (msg_len + 919) * m);
-    s.bytes = o;
+    s.a49 = f.take(49 * m); s.a96 = f.take(96 * m); s.st_a = f.take(m); s.sc = f.take(12 * 32 * m); s.t49 = f.take(3 * 49 * m); s.t96 = f.take(3 * 96 * m);
+    s.r49 = f.take(4 * 49 * m); s.p96 = f.take(2 * 96 * m); s.gt = f.take(576 * m); s.tr = f.take((msg_len + 919) * m);
+    s.bytes = f.bytes;
     return s;
-}
-// m products of one public base into column `col` of the projective workspace: the table of `slot` where the base is a subgroup point, the
-// generic kernel otherwise (each of the two launches returns at once when the other one serves the column)
-static int bbs04_fixed_column(c12381_ctx* c, size_t m, const uint8_t* base, int slot, const uint8_t* sc, size_t stride, size_t col, bool fb) {
-    const int32_t* skip = nullptr;
-    if (fb) {
-        skip = (const int32_t*)c->ws[c12381_ctx::WS_FB_G1_0 + slot];
-        hipLaunchKernelGGL(g1_fixed_eval_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, skip, sc, (int32_t*)c->ws[c12381_ctx::WS_PROJ], stride,
-                           col * m);
-        HIPCK(c, hipGetLastError());
-    }
-    return g1_mul_to_proj(c, m, base, sc, stride, 0, col * m, skip);
 }
 static int bbs04_sign_args(size_t msg_len, const void* gpk, const void* gsk, const void* msgs, const void* rnd, const void* sig, const void* status) {
     return (!gpk || !gsk || !rnd || !sig || !status || (msg_len && !msgs)) ? C12381_E_ARG : 0;
@@ -2148,8 +2145,8 @@ int c12381_bbs04_sign_batch_dev(c12381_ctx* c, size_t n, size_t msg_len, const u
     const size_t ch = n < BBS04_CHUNK ? n : BBS04_CHUNK, L = msg_len + 919;
     if ((rc = ensure(c, c12381_ctx::WS_BBS04, bbs04_sign_layout(nullptr, ch, msg_len).bytes))) return rc;
     uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS04];
-    if ((rc = bbs04_pub(c, gpk_390, d))) return rc;
-    const uint8_t *h = d + 512 + 96, *u = d + 512 + 192, *v = d + 512 + 288;
+    const bbs04_public pub(d);
+    if ((rc = bbs04_pub(c, gpk_390, pub))) return rc;
     const bool fb = fixed_base_enabled();
     for (size_t off = 0; off < n; off += ch) {
         const size_t m = n - off < ch ? n - off : ch;
@@ -2158,16 +2155,16 @@ int c12381_bbs04_sign_batch_dev(c12381_ctx* c, size_t n, size_t msg_len, const u
         hipLaunchKernelGGL(bbs04_sign_prep_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, gsk, rnd, s.a49, s.sc);
         hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, s.a49, s.a96, s.st_a, 0);
         HIPCK(c, hipGetLastError());
-        if (off == 0) HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        if (off == 0 && (rc = join_side(c))) return rc;
         const size_t stride = round_up(9 * m, 64);
         if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+        const uint8_t* tab[3] = {pub.u, pub.v, pub.h};
         if (fb)
             for (int t = 0; t < 3; ++t)
-                if ((rc = fixed_table(c, c12381_ctx::WS_FB_G1_0 + t, t == 0 ? u : (t == 1 ? v : h), false))) return rc;
+                if ((rc = g1_fixed_table(c, t, tab[t]))) return rc;
         // phase 1: scalar columns 0-2 -> T1, T2, T3
-        const uint8_t* base1[3] = {u, v, h};
         for (size_t k = 0; k < 3; ++k)
-            if ((rc = bbs04_fixed_column(c, m, base1[k], (int)k, s.sc + 32 * k * m, stride, k, fb))) return rc;
+            if ((rc = g1_fixed_column(c, m, tab[k], (int)k, s.sc + 32 * k * m, stride, k * m, fb))) return rc;
         int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
         hipLaunchKernelGGL(bbs04_sign_t3_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, proj, stride, (const uint8_t*)s.a96);
         HIPCK(c, hipGetLastError());
@@ -2175,19 +2172,18 @@ int c12381_bbs04_sign_batch_dev(c12381_ctx* c, size_t n, size_t msg_len, const u
         if ((rc = g1_finish(c, 3 * m, proj, stride, s.t96, 96))) return rc;
         // phase 2: T1, T2, T3 against scalar columns 3-5 (r_x) in one launch of 3 m lanes, then columns 6-11 (u, v, u, v, h, h)
         if ((rc = g1_mul_to_proj(c, 3 * m, s.t96, s.sc + 32 * 3 * m, stride))) return rc;
-        const uint8_t* base2[6] = {u, v, u, v, h, h};
         const int slot2[6] = {0, 1, 0, 1, 2, 2};
         for (size_t k = 0; k < 6; ++k)
-            if ((rc = bbs04_fixed_column(c, m, base2[k], slot2[k], s.sc + 32 * (6 + k) * m, stride, 3 + k, fb))) return rc;
+            if ((rc = g1_fixed_column(c, m, tab[slot2[k]], slot2[k], s.sc + 32 * (6 + k) * m, stride, (3 + k) * m, fb))) return rc;
         proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
         hipLaunchKernelGGL(bbs04_sign_combine_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, proj, stride);
         HIPCK(c, hipGetLastError());
         if ((rc = g1_finish(c, 4 * m, proj, stride, s.r49, 49))) return rc;
         if ((rc = g1_finish(c, 2 * m, proj + 4 * m, stride, s.p96, 96))) return rc;
-        if ((rc = c12381_pair_product_fixed_g2_batch_dev(c, m, 2, s.p96, d + 1024, s.gt, 0u))) return rc;
+        if ((rc = c12381_pair_product_fixed_g2_batch_dev(c, m, 2, s.p96, pub.g2_w, s.gt, 0u))) return rc;
         hipLaunchKernelGGL(bbs04_transcript_kernel, dim3(grid_for(m * L)), dim3(BLOCK), 0, c->stream, m, msg_len, msg_len ? msgs + msg_len * off : msgs,
                            s.t49, s.t96, s.r49, s.gt, s.tr);
-        hipLaunchKernelGGL(bbs04_sign_finish_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, L, s.tr, gsk, rnd, s.t49, s.st_a, d + 1536,
+        hipLaunchKernelGGL(bbs04_sign_finish_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, L, s.tr, gsk, rnd, s.t49, s.st_a, pub.st,
                            sig_435 + 435 * off, status + off, c->d_flag);
         HIPCK(c, hipGetLastError());
     }
@@ -2205,27 +2201,36 @@ int c12381_bbs04_sign_batch(c12381_ctx* c, size_t n, size_t msg_len, const uint8
 }
 // key_gen's issuance (:17-23): gsk_i = serialize(g1^inverse(gamma + x_i), x_i) — the simultaneous inversion of c12381_zp_op_batch, g1's
 // fixed-base table (slot 3, as in verify; the generic kernel when g1 is not a subgroup point), 49-byte records, bbs04_issue_pack_kernel.
-// WS_BBS04: BBS04_PUB_BYTES, then 32 + 49 bytes per key of a chunk.
+// WS_BBS04: the public block, then 32 + 49 bytes per key of a chunk.
+struct bbs04_issue_slab { uint8_t *inv, *a49; size_t bytes; };
+static bbs04_issue_slab bbs04_issue_layout(uint8_t* base, size_t m) {
+    bbs04_fields f{base};
+    bbs04_issue_slab s;
+    s.inv = f.take(32 * m); s.a49 = f.take(49 * m);
+    s.bytes = f.bytes;
+    return s;
+}
 static int bbs04_issue_args(const void* gpk, const void* gamma, const void* x, const void* gsk) { return (!gpk || !gamma || !x || !gsk) ? C12381_E_ARG : 0; }
 int c12381_bbs04_issue_batch_dev(c12381_ctx* c, size_t n, const uint8_t* gpk_390, const uint8_t* gamma_32, const uint8_t* x_32, uint8_t* gsk_97) {
     int rc = bind(c); if (rc || (rc = bbs04_issue_args(gpk_390, gamma_32, x_32, gsk_97))) return rc;
     if (n == 0) return 0;
     const size_t ch = n < BBS04_CHUNK ? n : BBS04_CHUNK;
-    const size_t o_inv = BBS04_PUB_BYTES, o_a49 = round_up(o_inv + 32 * ch, 256);
-    if ((rc = ensure(c, c12381_ctx::WS_BBS04, o_a49 + 49 * ch))) return rc;
+    if ((rc = ensure(c, c12381_ctx::WS_BBS04, bbs04_issue_layout(nullptr, ch).bytes))) return rc;
     uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_BBS04];
-    if ((rc = bbs04_pub(c, gpk_390, d))) return rc;
+    const bbs04_issue_slab s = bbs04_issue_layout(d, ch);
+    const bbs04_public pub(d);
+    if ((rc = bbs04_pub(c, gpk_390, pub))) return rc;
     const bool fb = fixed_base_enabled();
     for (size_t off = 0; off < n; off += ch) {
         const size_t m = n - off < ch ? n - off : ch;
-        if ((rc = zp_batch_inverse(c, m, x_32 + 32 * off, gamma_32, d + o_inv))) return rc;
-        if (off == 0) HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        if ((rc = zp_batch_inverse(c, m, x_32 + 32 * off, gamma_32, s.inv))) return rc;
+        if (off == 0 && (rc = join_side(c))) return rc;
         const size_t stride = round_up(m, 64);
         if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
-        if (fb && (rc = fixed_table(c, c12381_ctx::WS_FB_G1_3, d + 512, false))) return rc;
-        if ((rc = bbs04_fixed_column(c, m, d + 512, 3, d + o_inv, stride, 0, fb))) return rc;
-        if ((rc = g1_finish(c, m, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, d + o_a49, 49))) return rc;
-        hipLaunchKernelGGL(bbs04_issue_pack_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, d + o_a49, x_32 + 32 * off, d + 1536, gsk_97 + 97 * off,
+        if (fb && (rc = g1_fixed_table(c, 3, pub.g1))) return rc;
+        if ((rc = g1_fixed_column(c, m, pub.g1, 3, s.inv, stride, 0, fb))) return rc;
+        if ((rc = g1_finish(c, m, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, s.a49, 49))) return rc;
+        hipLaunchKernelGGL(bbs04_issue_pack_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, s.a49, x_32 + 32 * off, pub.st, gsk_97 + 97 * off,
                            c->d_flag);
         HIPCK(c, hipGetLastError());
     }

@@ -1,9 +1,13 @@
 // Fixed-base columns (fixed_base.hpp): table construction with a device-side "same base as last time?" check, and
 // the table-driven evaluation kernels (one base per column, and per-lane sums over a set of bases).
-// Table buffer = FB_HEADER_DWORDS header (cached base bytes, state) + entries.
-//   header[0..47]  the base's canonical bytes as dwords (96 B for G1, 192 B for G2)
-//   header[HDR_VALID]    ok: 1 = table valid (base on the curve, not infinity, in the order-r subgroup)
-//   header[HDR_REBUILD]  build: 1 = the table kernel must (re)build, 0 = cached table matches the base
+// The cache protocol of every device-built table (fixed-base multiples here, line coefficients in k_pairk.hip; the host side is
+// c12381_hip.hip cached_tables).  A table is HDR_DWORDS of header and its entries; the tables of an array lie tab_stride dwords apart:
+//   header[0..47]        the cached point's canonical bytes as dwords (96 B for G1, 192 B for G2)
+//   header[HDR_VALID]    1 = table usable (fixed-base: point on the curve, not infinity, in the order-r subgroup; lines: by HDR_RULE)
+//   header[HDR_REBUILD]  1 = the build kernel must (re)build, 0 = the cached table matches the point
+//   header[HDR_MAGIC]    the header has been written before (a fresh workspace is zeroed: first use is a miss)
+//   header[HDR_RULE]     line tables: the rule the table was built under, + 1
+// fixed_cache_check_kernel compares and sets HDR_REBUILD, the build kernel that follows it on the stream returns at once on a hit.
 #include "kernels_common.hpp"
 #include "fixed_base.hpp"
 
@@ -11,23 +15,17 @@ using namespace c12381;
 
 namespace c12381 {
 
-// one wavefront: compare the base with the cached copy; on a miss store the new copy and request a rebuild
-static __device__ __forceinline__ void fixed_cache_check(const uint8_t* base, int nbytes, int32_t* header) {
+// One wavefront per table of the array (blockIdx.x): compare the point with the cached copy; on a miss store the new copy and request a rebuild
+__global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(table_points pts, int nbytes, int32_t* tabs, int tab_stride) {
+    int32_t* header = tabs + (size_t)blockIdx.x * tab_stride;
     const int lane = threadIdx.x;
     const int nd = nbytes / 4;
-    const uint32_t* b = reinterpret_cast<const uint32_t*>(base);
+    const uint32_t* b = reinterpret_cast<const uint32_t*>(pts.p[blockIdx.x]);
     uint32_t mine = 0, cached = 0;
     if (lane < nd) { mine = b[lane]; cached = (uint32_t)header[lane]; }
     const bool same = __all(mine == cached) && header[HDR_MAGIC] == 0x46423031;      // magic: the header has been written before
     if (lane < nd) header[lane] = (int32_t)mine;
     if (lane == 0) { header[HDR_REBUILD] = same ? 0 : 1; header[HDR_MAGIC] = 0x46423031; if (!same) header[HDR_VALID] = 0; }
-}
-__global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(const uint8_t* base, int nbytes, int32_t* header) {
-    fixed_cache_check(base, nbytes, header);
-}
-// the same for the tables of a set of bases, one workgroup per base (tables tab_stride dwords apart)
-__global__ void __launch_bounds__(64, 1) fixed_cache_checkk_kernel(const uint8_t* bases, int nbytes, int32_t* tabs, int tab_stride) {
-    fixed_cache_check(bases + (size_t)nbytes * blockIdx.x, nbytes, tabs + (size_t)blockIdx.x * tab_stride);
 }
 
 // entry L of the table of base96 (every entry by its own lane: no entry waits for another)
@@ -53,11 +51,8 @@ static __device__ __forceinline__ void g1_fixed_table_entry(const uint8_t* base9
     g1_to_affine(ax, ay, an, zi);
     msm_store_pt(buf + FB_HEADER_DWORDS + L * FB_G1_DWORDS, ax, ay);
 }
-__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_table_kernel(const uint8_t* base96, int32_t* buf) {
-    g1_fixed_table_entry(base96, buf, (size_t)blockIdx.x * BLOCK + threadIdx.x);
-}
-// the tables of a set of bases in one launch: blockIdx.y = base; a base whose cached table is current costs its workgroups one load
-__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_tablek_kernel(const uint8_t* bases96, int32_t* tabs, int tab_stride) {
+// the tables of a set of bases (96 bytes apart) in one launch: blockIdx.y = base; a base whose cached table is current costs its workgroups one load
+__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_tables_kernel(const uint8_t* bases96, int32_t* tabs, int tab_stride) {
     g1_fixed_table_entry(bases96 + (size_t)96 * blockIdx.y, tabs + (size_t)blockIdx.y * tab_stride, (size_t)blockIdx.x * BLOCK + threadIdx.x);
 }
 

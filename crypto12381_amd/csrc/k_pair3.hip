@@ -539,35 +539,7 @@ __global__ void __launch_bounds__(BLOCK, 2) fexp3_queue_kernel(size_t n, const u
 }
 
 // ------------------------------------------------------------------ both G2 arguments fixed for the batch
-// Coefficient table of one G2 point (pairing3.hpp, 69 lines) with the header of the fixed-base tables (k_fixed.hip):
-// header[HDR_VALID] = valid (on the twist, not infinity, in G2), header[HDR_REBUILD] = rebuild requested by fixed_cache_check_kernel.
-// (One working lane, but the launch bounds of every kernel in this file: the out-of-line field routines are compiled
-// once for all their callers, and a kernel that allowed one wave per SIMD would hand them a 512-register budget.)
-// need_g2 != 0: valid only for elements of G2 other than infinity (BBS+ rewrite); need_g2 == 0: any point of the twist
-// and infinity (plain pairing against one Q: the table holds exactly the lines the running-point loop would compute).
-// header[HDR_RULE] remembers which rule the cached flag was computed under.
-// need_g2: bit 0 = the point has to be in G2, bit 2 = keep the records raw (A/B switch C12381_FQ_RAW)
-__global__ void __launch_bounds__(BLOCK, 2) g2_lines_table_kernel(const uint8_t* q192, int32_t* buf, int need_g2_flags) {
-    const int need_g2 = need_g2_flags & 1;
-    const bool raw = (need_g2_flags & 4) != 0;
-    if (buf[HDR_REBUILD] == 0 && buf[HDR_RULE] == need_g2 + 1) return;    // cached table is current
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    g2p Q;
-    bool inf, ok;
-    g2_parse192(Q.x, Q.y, inf, ok, q192);
-    fp2_one(Q.z);
-    const bool valid = need_g2 ? (ok && !inf && g2_in_subgroup(Q)) : ok;
-    buf[HDR_VALID] = valid ? 1 : 0;
-    buf[HDR_RULE] = need_g2 + 1;
-    if (valid) miller_lines_precompute(buf + HDR_DWORDS, Q.x, Q.y, inf, !raw);
-}
-// gate[HDR_VALID] = a valid and b valid (the table-driven kernels run), (gate + GATE_OTHER)[HDR_VALID] = the opposite (the generic kernels run)
-__global__ void __launch_bounds__(BLOCK, 2) gate_and_kernel(int32_t* gate, const int32_t* a, const int32_t* b) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int both = (a[HDR_VALID] != 0 && b[HDR_VALID] != 0) ? 1 : 0;
-    gate[HDR_VALID] = both;
-    gate[GATE_OTHER + HDR_VALID] = both ? 0 : 1;          // read as (gate + GATE_OTHER)[HDR_VALID] by kernels that skip on "generic"
-}
+// The coefficient tables (69 lines behind the header of the fixed-base tables) and the gate over them are built by k_pairk.hip.
 // ok[i] = [ e(a_i, W) * e(c_i, G) == 1 ] with W, G given by their coefficient tables.  Work queue as above (ten tasks
 // per group); the Miller tasks carry only F.  Runs only when run_if[HDR_VALID] != 0.
 // TWO: product of two pairings, boolean output; otherwise one pairing per element against the table tabw, GT output

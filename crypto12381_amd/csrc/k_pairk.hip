@@ -2,8 +2,8 @@
 //   gt[i] = prod_{c < K} e(P_c[i], Q_c)  or  ok[i] = [ that product == 1 ],   K <= FIXED_G2_MAX
 // The verification equations of the reference's examples are such products: PS (examples/ps/src/ps.cpp:32, :98, :145), BBS+
 // (examples/bbs-plus/src/bbs+.cpp:72) and bbs04's R3 (examples/bbs04/src/bbs.cpp:45, :73).  Every Q_c has a 69-line coefficient
-// table with the header and cache protocol of the fixed-base tables (k_fixed.hip fixed_cache_check_kernel), so no G2 arithmetic
-// runs per element.  A separate translation unit: the kernels of k_pair3.hip compile exactly as before.
+// table with the header and cache protocol of the fixed-base tables (k_fixed.hip), so no G2 arithmetic runs per element.
+// A separate translation unit: the kernels of k_pair3.hip compile exactly as before.
 #include "kernels_common.hpp"
 #include "pairing3.hpp"
 #include "fixed_base.hpp"
@@ -13,10 +13,12 @@ using namespace c12381;
 
 namespace c12381 {
 
-// Line tables of the K points q.p[c] into tabs + c * tab_stride (header + lines), one lane per table.  rule: bit 0 = the point has to be
-// an element of G2 other than infinity (need_g2), bit 1 = keep the records raw (the Miller value itself is wanted: a normalised table
-// changes it by factors the final exponentiation removes).  header[HDR_RULE] = rule + 1, so a table built under another rule is rebuilt.
-__global__ void __launch_bounds__(BLOCK, 2) g2_lines_tablek_kernel(int k, g2_cols q, int32_t* tabs, int tab_stride, int rule) {
+// Line tables (pairing3.hpp, 69 lines) of the k points q.p[c] into tabs + c * tab_stride (header + lines), one lane per table; k = 1 is the
+// table of a plain pairing against one Q.  rule: bit 0 = the point has to be an element of G2 other than infinity (need_g2: the rewritten
+// verification equations hold only there; without it any point of the twist and infinity are valid, and the table holds exactly the lines the
+// running-point loop would compute), bit 1 = keep the records raw (the Miller value itself is wanted: a normalised table changes it by
+// factors the final exponentiation removes).  header[HDR_RULE] = rule + 1, so a table built under another rule is rebuilt.
+__global__ void __launch_bounds__(BLOCK, 2) g2_lines_tables_kernel(int k, g2_cols q, int32_t* tabs, int tab_stride, int rule) {
     const int c = (int)threadIdx.x;
     if (blockIdx.x != 0 || c >= k) return;
     int32_t* buf = tabs + (size_t)c * tab_stride;
@@ -31,8 +33,9 @@ __global__ void __launch_bounds__(BLOCK, 2) g2_lines_tablek_kernel(int k, g2_col
     buf[HDR_RULE] = rule + 1;
     if (valid) miller_lines_precompute(buf + HDR_DWORDS, Q.x, Q.y, inf, !raw);
 }
-// gate[HDR_VALID] = every one of the k tables is valid, (gate + GATE_OTHER)[HDR_VALID] = the opposite (as gate_and_kernel for two)
-__global__ void __launch_bounds__(BLOCK, 2) gatek_kernel(int32_t* gate, const int32_t* tabs, int tab_stride, int k) {
+// gate[HDR_VALID] = every one of the k tables is valid (the table-driven kernels run), (gate + GATE_OTHER)[HDR_VALID] = the opposite (the
+// generic kernels run: read as (gate + GATE_OTHER)[HDR_VALID] by kernels that skip on "generic")
+__global__ void __launch_bounds__(BLOCK, 2) gate_all_kernel(int32_t* gate, const int32_t* tabs, int tab_stride, int k) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int all = 1;
     for (int c = 0; c < k; ++c) all = all && tabs[(size_t)c * tab_stride + HDR_VALID] != 0;

@@ -20,9 +20,9 @@ namespace c12381 {
 constexpr int BLOCK = 256;
 constexpr int FINISH_M = 16;                     // most elements per lane in the simultaneous inversion (c12381_hip.hip finish_lanes)
 constexpr int TRI_PER_WAVE = 21;                 // pairings per 64-lane wavefront in the three-lane kernels (lane 63 idles along)
-// Header words in front of a device-built table (fixed-base multiples, line coefficients) and of a gate buffer
+// Header words in front of a device-built table (fixed-base multiples, line coefficients) and of a gate buffer; the protocol: k_fixed.hip
 constexpr int HDR_VALID = 48;                    // 1 = table usable / this path runs; kernels of the other path return at once
-constexpr int HDR_REBUILD = 49;                  // set by fixed_cache_check_kernel when the cached point differs
+constexpr int HDR_REBUILD = 49;                  // set by fixed_cache_check_kernel (the one check kernel of every table array) when the cached point differs
 constexpr int HDR_MAGIC = 50;                    // the header has been written before
 constexpr int HDR_RULE = 51;                     // validity rule the flag was computed under (line tables)
 constexpr int HDR_DWORDS = 64;                   // table data starts here
@@ -88,16 +88,14 @@ __global__ void __launch_bounds__(BLOCK, 2) miller3_queue_kernel(size_t n, const
 __global__ void __launch_bounds__(BLOCK, 2) fexp3_queue_kernel(size_t n, const uint8_t* in576, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch, unsigned long long* wstats);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_queue_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch, unsigned long long* stamps, unsigned long long* wstats);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_eq_queue_kernel(size_t n, const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, size_t b2_stride, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* skip_if, int spin_limit, unsigned int epoch);
-__global__ void __launch_bounds__(BLOCK, 2) g2_lines_table_kernel(const uint8_t* q192, int32_t* buf, int need_g2);
-__global__ void __launch_bounds__(BLOCK, 2) gate_and_kernel(int32_t* gate, const int32_t* a, const int32_t* b);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_prod_fixed_queue_kernel(size_t n, const uint8_t* a96, const uint8_t* c96, const int32_t* tabw, const int32_t* tabg, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* run_if, int spin_limit, unsigned int epoch);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_fixed_queue_kernel(size_t n, const uint8_t* g1_96, const int32_t* buf, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch);
 // k_pairk.hip: K-way products of pairings against fixed G2 points (C12381_FIXED_G2_MAX = FIXED_G2_MAX); the point columns travel by value
 constexpr int FIXED_G2_MAX = 8;
 struct g1_cols { const uint8_t* p[FIXED_G2_MAX]; };
 struct g2_cols { const uint8_t* p[FIXED_G2_MAX]; };
-__global__ void __launch_bounds__(BLOCK, 2) g2_lines_tablek_kernel(int k, g2_cols q, int32_t* tabs, int tab_stride, int rule);
-__global__ void __launch_bounds__(BLOCK, 2) gatek_kernel(int32_t* gate, const int32_t* tabs, int tab_stride, int k);
+__global__ void __launch_bounds__(BLOCK, 2) g2_lines_tables_kernel(int k, g2_cols q, int32_t* tabs, int tab_stride, int rule);   // rule: bit 0 need_g2, bit 1 raw records
+__global__ void __launch_bounds__(BLOCK, 2) gate_all_kernel(int32_t* gate, const int32_t* tabs, int tab_stride, int k);
 __global__ void __launch_bounds__(BLOCK, 2) pairk_prep_kernel(size_t n, int k, g1_cols cols, uint32_t neg_mask, int32_t* pts, uint32_t* mask, const int32_t* skip_if);
 __global__ void __launch_bounds__(BLOCK, 2) g2_bcast_kernel(size_t n, const uint8_t* src, uint8_t* dst, const int32_t* skip_if);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_prodk_fixed_queue_kernel(size_t n, int k, const int32_t* pts, const uint32_t* mask, const int32_t* tabs, int tab_stride, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* gate, size_t ndirect, int miller_only, int spin_limit, unsigned int epoch);
@@ -134,13 +132,14 @@ __global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_t3_kernel(size_t n, int32
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_combine_kernel(size_t n, int32_t* proj, size_t stride);
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_finish_kernel(size_t n, size_t L, const uint8_t* tr, const uint8_t* gsk97, const uint8_t* rnd224, const uint8_t* t49, const uint8_t* st_a, const uint8_t* st_pub, uint8_t* sig435, uint8_t* status, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_issue_pack_kernel(size_t n, const uint8_t* a49, const uint8_t* x32, const uint8_t* st_pub, uint8_t* gsk97, int* bad_flag);
-__global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(const uint8_t* base, int nbytes, int32_t* header);
-__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_table_kernel(const uint8_t* base96, int32_t* buf);
+// k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
+constexpr int TABLE_ARRAY_MAX = 32;
+struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };
+__global__ void __launch_bounds__(64, 1) fixed_cache_check_kernel(table_points pts, int nbytes, int32_t* tabs, int tab_stride);
+__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_tables_kernel(const uint8_t* bases96, int32_t* tabs, int tab_stride);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_eval_kernel(size_t n, const int32_t* buf, const uint8_t* scalars, int32_t* proj, size_t proj_stride, size_t proj_off);
 // per-lane sums over a set of shared G1 bases (C12381_G1_FIXED_SUM_MAX = G1_FIXED_SUM_MAX): nb tables behind one gate
-constexpr int G1_FIXED_SUM_MAX = 32;
-__global__ void __launch_bounds__(64, 1) fixed_cache_checkk_kernel(const uint8_t* bases, int nbytes, int32_t* tabs, int tab_stride);
-__global__ void __launch_bounds__(BLOCK, 2) g1_fixed_tablek_kernel(const uint8_t* bases96, int32_t* tabs, int tab_stride);
+constexpr int G1_FIXED_SUM_MAX = TABLE_ARRAY_MAX;
 __global__ void __launch_bounds__(64, 1) g1_fixed_sum_gate_kernel(int nb, const uint8_t* bases96, const uint8_t* addend96, int32_t* gate, const int32_t* tabs, int tab_stride, int use_tables, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_sum_kernel(size_t n, int nb, const int32_t* gate, const int32_t* tabs, int tab_stride, const uint8_t* scalars, const uint8_t* addend96, int32_t* proj, size_t proj_stride);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_sum_fold_kernel(size_t n, const int32_t* gate, int32_t* proj, size_t proj_stride, size_t col_off, int has_col, int last, const uint8_t* addend96);

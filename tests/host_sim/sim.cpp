@@ -691,7 +691,7 @@ extern "C" int sim_pair2_fixed_batch(size_t n, const uint8_t* a96, const uint8_t
     int32_t* t2 = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(t2v.data()) + 15) & ~(uintptr_t)15);
     fp2 qx, qy;
     uint32_t rq[48];
-    load_raw(rq, w192, 48);                                   // an all-zero record is infinity, as g2_lines_table_kernel reads it
+    load_raw(rq, w192, 48);                                   // an all-zero record is infinity, as g2_lines_tables_kernel reads it
     fp2_from_bytes96(qx, w192); fp2_from_bytes96(qy, w192 + 96);
     miller_lines_precompute(t1, qx, qy, raw_all_zero(rq, 48));
     load_raw(rq, g192, 48);

@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""A/B of two builds of the C ABI on the entry points that go through the host's table cache (c12381_hip.hip cached_tables), in ONE GPU
+session.  One child process per library stays alive with its inputs resident on the device; the parent lets them run one call at a time,
+alternately (A B A B ...), so that clock drift of the box hits both alike.  Per leg: median / min / max wall ms of --reps calls per
+library and a SHA-256 of the output.  A leg is marked OUTSIDE when B's median is not within the min-max spread of A's own repeats
+(the criterion of profiles/g1_fixed_sum_ab.txt).  Exit status 1 when a digest differs or a child fails.
+
+    python tools/host_tables_ab.py [--reps 5] [--out profiles/host_tables_refactor_ab.txt] <A.so | default> <B.so | default>
+
+Legs (sizes of tools/fixed_base_bench.py, g1_fixed_sum_bench.py, fixed_g2_bench.py, bbs04_bench.py --tiled and bench.py):
+  g1_mul_fixed 2^20 | g1_mul_fixed_sum 2^20, nb = 2 and 32 | pair_fixed_g2 2^16 | bbs04 verify, sign 2^18 (1024 distinct, tiled)
+  | BBS+ verify 2^18 (one message block) | BBS+ verify from the wire formats 2^18 (16 h_i, 12-byte messages)"""
+import argparse
+import hashlib
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def child():
+    import numpy as np
+    import torch
+    torch.cuda.init()
+    import tools.libsel  # noqa: F401  (C12381_LIB -> capi.use_library)
+    from crypto12381_amd import Context
+    from tools.bbs04_bench import MSG_LEN, make
+    from tools.prof_driver import G1, G2, sc
+    c = Context(0)
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(20261018)
+    d = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    rand = lambda nbytes: torch.randint(0, 256, (nbytes,), dtype=torch.uint8, device=dev, generator=gen)
+    out = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    legs = {}
+
+    n = 1 << 20
+    base, k20, o20 = d(G1), rand(32 * n), out(96 * n)
+    legs["g1_mul_fixed"] = (lambda: c.g1_mul_fixed_dev(n, base.data_ptr(), k20.data_ptr(), o20.data_ptr(), 96), o20)
+    bases, k32 = d(c.g1_mul_fixed(G1, sc(61, 32), 96)), rand(32 * 32 * n)
+    legs["g1_fixed_sum nb=2"] = (lambda: c.g1_mul_fixed_sum_dev(n, 2, bases.data_ptr(), k32.data_ptr(), o20.data_ptr(), None, 96), o20)
+    legs["g1_fixed_sum nb=32"] = (lambda: c.g1_mul_fixed_sum_dev(n, 32, bases.data_ptr(), k32.data_ptr(), o20.data_ptr(), None, 96), o20)
+
+    np_ = 1 << 16
+    p16, q1, gt = d(c.g1_mul(G1 * 1024, sc(3, 1024), 96) * (np_ // 1024)), d(c.g2_mul(G2, sc(4, 1), 192)), out(576 * np_)
+    legs["pair_fixed_g2"] = (lambda: c.pair_fixed_g2_dev(np_, p16.data_ptr(), q1.data_ptr(), gt.data_ptr()), gt)
+
+    nb = 1 << 18
+    gpk, gsk, msgs, rnd224, sig = make(c, 1024)
+    d_gpk, d_gsk, d_msg, d_rnd, d_sig = (d(b) for b in (gpk, gsk * (nb // 1024), msgs * (nb // 1024), rnd224 * (nb // 1024), sig * (nb // 1024)))
+    ok04, sig_out, st04 = out(nb), out(435 * nb), out(nb)
+    legs["bbs04_verify"] = (lambda: c.bbs04_verify_dev(nb, MSG_LEN, d_gpk.data_ptr(), d_sig.data_ptr(), d_msg.data_ptr(), ok04.data_ptr()), ok04)
+    legs["bbs04_sign"] = (lambda: c.bbs04_sign_dev(nb, MSG_LEN, d_gpk.data_ptr(), d_gsk.data_ptr(), d_msg.data_ptr(), d_rnd.data_ptr(), sig_out.data_ptr(),
+                                                   st04.data_ptr()), sig_out)
+
+    def red(seed, m):
+        a = np.frombuffer(sc(seed, m), dtype=np.uint8).reshape(m, 32).copy()
+        a[:, 0] &= 0x3f
+        return a
+    NH, RAW = 16, 12
+    pub = c.g1_mul_fixed(G1, red(51, 2 + NH).tobytes(), 96)
+    g1p, h0, h1, h_all = pub[:96], pub[96:192], pub[192:288], pub[192:]
+    g2p = c.g2_mul_fixed(G2, red(52, 1).tobytes(), 192)
+    gamma = red(53, 1).tobytes()
+    w = c.g2_mul_fixed(g2p, gamma, 192)
+    xs, rs = red(54, nb), red(55, nb)
+    raw = np.random.Generator(np.random.PCG64(56)).integers(0, 256, size=(nb, RAW), dtype=np.uint8)
+
+    def encode(r):                       # encode_to<Zp> of one unit: 0x01 || message || zero padding
+        mm = np.zeros((nb, 32), dtype=np.uint8)
+        mm[:, 0] = 1
+        mm[:, 1:1 + RAW] = r
+        return mm
+    A = c.bbs_plus_sign(g1p, h0, h1, gamma, xs.tobytes(), rs.tobytes(), encode(raw).tobytes())
+    raw[7::1009, RAW - 1] ^= 1
+    dA, dx, dr, dm = d(A), d(xs.tobytes()), d(rs.tobytes()), d(encode(raw).tobytes())
+    dpub = [d(b) for b in (g1p, g2p, h0, h1, w)]
+    okb, okw = out(nb), out(nb)
+    legs["bbs_plus_verify"] = (lambda: c.bbs_plus_verify_dev(nb, 1, dpub[0].data_ptr(), dpub[1].data_ptr(), dpub[2].data_ptr(), dpub[3].data_ptr(),
+                                                             dpub[4].data_ptr(), dA.data_ptr(), dx.data_ptr(), dr.data_ptr(), dm.data_ptr(), okb.data_ptr()), okb)
+    one = (1).to_bytes(32, "big")
+    A49 = np.frombuffer(c.g1_mul(A, one * nb, 49), dtype=np.uint8).reshape(nb, 49)
+    s145 = np.zeros((nb, 145), dtype=np.uint8)
+    s145[:, 0:49], s145[:, 65:97], s145[:, 113:145] = A49, xs, rs
+    dwire = [d(b) for b in (c.g1_mul(g1p, one, 49) + c.g2_mul(g2p, one, 97) + c.g1_mul(h0, one, 49), c.g1_mul(h_all, one * NH, 49), c.g2_mul(w, one, 97))]
+    dsig, draw = d(s145.tobytes()), d(raw.tobytes())
+    legs["bbs_plus_wire"] = (lambda: c.bbs_plus_verify_wire_dev(nb, NH, RAW, dwire[0].data_ptr(), dwire[1].data_ptr(), dwire[2].data_ptr(), dsig.data_ptr(),
+                                                                draw.data_ptr(), okw.data_ptr()), okw)
+    torch.cuda.synchronize(dev)
+    assert c.sync() == 0
+    print("READY " + "|".join(legs), flush=True)
+    for line in sys.stdin:
+        name = line.strip()
+        if name == "quit":
+            break
+        fn, res = legs[name]
+        t0 = time.perf_counter()
+        fn()
+        rc = c.sync()
+        dt = time.perf_counter() - t0
+        print("T %.4f %d %s" % (dt * 1e3, rc, hashlib.sha256(res.cpu().numpy().tobytes()).hexdigest()[:16]), flush=True)
+    c.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("libs", nargs="*")
+    a = ap.parse_args()
+    if a.child:
+        child()
+        return
+    assert len(a.libs) == 2, "two libraries: A (the baseline) and B"
+    kids = []
+    for lib in a.libs:
+        env = dict(os.environ)
+        env.pop("C12381_LIB", None)
+        if lib != "default":
+            env["C12381_LIB"] = os.path.abspath(lib)
+        kids.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), "--child"], cwd=ROOT, env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE,
+                                     text=True, bufsize=1))
+
+    def answer(k, tag):
+        while True:
+            line = k.stdout.readline()
+            if not line:
+                raise SystemExit("a child ended early (rc %s): nothing further is started" % k.poll())
+            if line.startswith(tag):
+                return line.split()[1:]
+    names = [answer(k, "READY")[0:] for k in kids]
+    legs = " ".join(names[0]).split("|")
+
+    def call(k, leg):
+        k.stdin.write(leg + "\n")
+        k.stdin.flush()
+        ms, rc, dig = answer(k, "T ")
+        if int(rc) != 0:
+            raise SystemExit("%s: status %s" % (leg, rc))
+        return float(ms), dig
+    lines = ["A = %s, B = %s; %d interleaved repeats per leg after one warm-up call each; wall ms per call (c12381_sync included)" % (a.libs[0], a.libs[1], a.reps),
+             "%-20s %30s %30s   %s" % ("leg", "A median (min - max)", "B median (min - max)", "B median within A's spread / digests")]
+    bad = False
+    for leg in legs:
+        digs = [call(k, leg)[1] for k in kids]                  # warm-up: tables built, workspaces grown
+        t = [[], []]
+        for _ in range(a.reps):
+            for i, k in enumerate(kids):
+                ms, dig = call(k, leg)
+                t[i].append(ms)
+                digs.append(dig)
+        med = [statistics.median(x) for x in t]
+        same = len(set(digs)) == 1
+        bad |= not same
+        inside = min(t[0]) <= med[1] <= max(t[0])
+        verdict = "inside" if inside else ("OUTSIDE (B faster)" if med[1] < min(t[0]) else "OUTSIDE (B slower)")
+        lines.append("%-20s %30s %30s   %s / %s" % (leg, "%.2f (%.2f - %.2f)" % (med[0], min(t[0]), max(t[0])), "%.2f (%.2f - %.2f)" % (med[1], min(t[1]), max(t[1])),
+                                                   verdict, "equal" if same else "DIFFER"))
+        print(lines[-1], flush=True)
+    for k in kids:
+        k.stdin.write("quit\n")
+        k.stdin.flush()
+        k.wait(timeout=60)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
