@@ -551,6 +551,20 @@ C12381_HD void fp_mul2(fp& r, const fp& a, const fp& b, const fp& c, const fp& d
                     set_lazy_bounds(t, a.lb * b.lb + c.lb * d.lb, a.vb * b.vb + c.vb * d.vb, "fp_mul2"); })
     r = t;
 }
+// r = (a*b - 2 c^2) / R with ONE reduction: a square that is only ever used linearly (the 8 Y^4 of a Jacobian doubling, as 2 G^2 with
+// G = 2 Y^2) needs no reduction of its own — its 105 column products ride in the reduction of the product it is subtracted from.
+// The square's operands -4c (cross terms) and -2c (diagonal) are raw limb multiples, never normalised (|limb| <= 4 LBc <= 2^30 + slack).
+// Needs 14*(LBa*LBb + 2*LBc^2) + 14*2^56 + 2^40 < 2^63: a, c reduction outputs and LBb <= 3*2^28 give 14 * 6 * 2^56 = 2^62.4
+// (at the caps, and refused with LBb = 2^31: tests/test_host_sim_g1_dbl_fold.py).  Counted by its pieces: 2 x 27 columns, 1 reduction.
+C12381_HD void fp_mul_msqr2(fp& r, const fp& a, const fp& b, const fp& c) {
+    fp t, c2, c4;
+    fp_raw_neg_dbl(c2, c);
+    fp_raw_dbl(c4, c2);
+    fp_reduce_cols(t, [&](int k, int64_t& acc) { fp_col_acc(acc, a, b, k); fp_col_sqr_acc(acc, c, c4, c2, k); });
+    C12381_BOUNDS({ check_actual(a, "fp_mul_msqr2"); check_actual(b, "fp_mul_msqr2"); check_actual(c, "fp_mul_msqr2");
+                    set_lazy_bounds(t, a.lb * b.lb + 2 * c.lb * c.lb, a.vb * b.vb + 2 * c.vb * c.vb, "fp_mul_msqr2"); })
+    r = t;
+}
 
 // ------------------------------------------------------------------ canonical form, tests
 // Leaves Montgomery form and fully reduces: r = a / R mod p as canonical limbs in [0, p).

@@ -91,24 +91,25 @@ C12381_HD void g1_endo_x2(g1p& r, const g1p& p) {
 // is absorbing: a doubling gives Z3 = 2YZ, a mixed addition Z3 = Z1 H.
 struct g1j { fp x, y, z; };
 
-// P = 2P (dbl-2009-l): 2M + 5S, 7 reductions; the linear terms -A - C, -2D and -8C ride in the reductions (fp_*_inj), so every output
-// coordinate is normalised.  Operand limb bound: <= 2^28 + slack (reduction outputs).
+// P = 2P (dbl-2009-l, rearranged): 3M + 3S plus one square's columns, 6 reductions; the linear term -2D rides in the reduction of E^2
+// (fp_sqr_inj), so every output coordinate is normalised.  Operand limb bound: <= 2^28 + slack (reduction outputs).
+// C = Y^4 is not formed: it only ever entered linearly (D/2 = (X + B)^2 - A - C and Y3 = E (D - X3) - 8C), and a value that is never
+// multiplied again needs no reduction of its own.  With G = 2Y^2 = Y (2Y) — 2Y is there for Z3 — D/2 = X G is a plain product and
+// 8C = 2 G^2, whose square columns ride in the reduction of Y3 (fp_mul_msqr2; 8 B^2 itself would not fit the columns beside
+// E (D - X3)).  Same values: X3 = 9X^4 - 8XY^2, Y3 = 3X^2 (4XY^2 - X3) - 8Y^4, Z3 = 2YZ.  g1j_dblu keeps C: there 8C is an output.
 C12381_HD void g1j_dbl(g1j& p) {
-    fp a, b, c, d, e, xb, x3, y3, z3, y2;
-    const int32_t cm1 = fp_opaque_const(-1), cm4 = fp_opaque_const(-4), cm8 = fp_opaque_const(-8);
+    fp a, g, d, e, x3, y3, z3, y2;
+    const int32_t cm4 = fp_opaque_const(-4);
     fp_raw_dbl(y2, p.y);
     fp_mul(z3, y2, p.z);                                 // Z3 = 2YZ
     fp_sqr(a, p.x);                                      // A = X^2
-    fp_sqr(b, p.y);                                      // B = Y^2
-    fp_sqr(c, b);                                        // C = B^2
-    fp_add(xb, p.x, b);
-    fp_sqr_inj(d, xb, [&](int i, int64_t& acc) { fp_inj(acc, a, i, cm1); fp_inj(acc, c, i, cm1); },
-               C12381_BV(a.vb + c.vb), C12381_BV(a.lb + c.lb));                       // D/2 = (X + B)^2 - A - C = 2XB
+    fp_mul(g, p.y, y2);                                  // G = 2Y^2
+    fp_mul(d, p.x, g);                                   // D/2 = 2XY^2
     fp_mul_small(e, a, 3);                               // E = 3A
     fp_sqr_inj(x3, e, [&](int i, int64_t& acc) { fp_inj(acc, d, i, cm4); }, C12381_BV(4 * d.vb), C12381_BV(4 * d.lb));   // X3 = E^2 - 2D
     fp_raw_dbl(d, d);
     fp_sub(d, d, x3);
-    fp_mul_inj(y3, e, d, [&](int i, int64_t& acc) { fp_inj(acc, c, i, cm8); }, C12381_BV(8 * c.vb), C12381_BV(8 * c.lb));  // Y3 = E (D - X3) - 8C
+    fp_mul_msqr2(y3, e, d, g);                           // Y3 = E (D - X3) - 2G^2
     p.x = x3; p.y = y3; p.z = z3;
 }
 
