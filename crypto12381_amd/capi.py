@@ -99,7 +99,8 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, vp, vp, ci]
         for name in ("c12381_g1_mul_fixed_batch", "c12381_g1_mul_fixed_batch_dev", "c12381_g2_mul_fixed_batch", "c12381_g2_mul_fixed_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, ci]
-        for name in ("c12381_g1_mul_fixed_sum_batch", "c12381_g1_mul_fixed_sum_batch_dev"):
+        for name in ("c12381_g1_mul_fixed_sum_batch", "c12381_g1_mul_fixed_sum_batch_dev", "c12381_g2_mul_fixed_sum_batch",
+                     "c12381_g2_mul_fixed_sum_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp, ci]
         for name in ("c12381_pair_fixed_g2_batch", "c12381_pair_fixed_g2_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp]
@@ -406,6 +407,19 @@ class Context:
 
     def g1_mul_fixed_sum_dev(self, n, nb, bases_ptr, sc_ptr, out_ptr, addend_ptr=None, fmt=49):
         self._ck(self.lib.c12381_g1_mul_fixed_sum_batch_dev(self.h, n, nb, _p(bases_ptr), _p(addend_ptr), _p(sc_ptr), _p(out_ptr), fmt))
+
+    def g2_mul_fixed_sum(self, bases: bytes, scalars: bytes, addend: bytes | None = None, fmt: int = 97, strict: bool = True) -> bytes:
+        """The G2 form of g1_mul_fixed_sum: nb = len(bases) // 192 public G2 bases shared by the batch (1 <= nb <= 32), served from nb fixed-base
+        tables when every base is an element of G2.  scalars: base-major, nb arrays of n records; addend: one 192-byte point or None; returns
+        n points of `fmt` bytes (97 or 192).  Every lane equals multiply on each term followed by add, for every point of the twist"""
+        nb = len(bases) // 192
+        n = len(scalars) // (32 * nb) if nb > 0 else 0
+        out = ctypes.create_string_buffer(max(fmt * n, 1))
+        self._ck(self.lib.c12381_g2_mul_fixed_sum_batch(self.h, n, nb, _p(bases), _p(addend), _p(scalars), _p(out), fmt), allow_point=not strict)
+        return out.raw[:fmt * n]
+
+    def g2_mul_fixed_sum_dev(self, n, nb, bases_ptr, sc_ptr, out_ptr, addend_ptr=None, fmt=97):
+        self._ck(self.lib.c12381_g2_mul_fixed_sum_batch_dev(self.h, n, nb, _p(bases_ptr), _p(addend_ptr), _p(sc_ptr), _p(out_ptr), fmt))
 
     def g1_map_to_point(self, u48: bytes) -> bytes:
         n = len(u48) // 48

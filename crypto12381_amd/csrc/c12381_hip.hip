@@ -74,7 +74,7 @@ struct c12381_ctx {
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
            WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
-           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_COUNT };
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;
@@ -276,16 +276,17 @@ struct table_array { int slot, count; size_t stride, gate; int point_bytes; };
 struct cached { int32_t *gate, *tabs; int stride; };
 constexpr size_t GATE_DWORDS = 128;
 static_assert(FB_HEADER_DWORDS == HDR_DWORDS, "every table: header in front of the entries");
-static_assert(FIXED_G2_MAX <= TABLE_ARRAY_MAX && G1_FIXED_SUM_MAX <= TABLE_ARRAY_MAX, "table_points holds the points of the largest array");
+static_assert(FIXED_G2_MAX <= TABLE_ARRAY_MAX && G1_FIXED_SUM_MAX <= TABLE_ARRAY_MAX && G2_FIXED_SUM_MAX <= TABLE_ARRAY_MAX, "table_points holds the points of the largest array");
 constexpr size_t table_dwords(size_t entries) { return (HDR_DWORDS + entries + 63) / 64 * 64; }
 constexpr size_t FB_G1_ENTRIES = (size_t)FB_G1_WINDOWS * FB_ENTRIES, FB_G2_ENTRIES = (size_t)FB_G2_WINDOWS * FB_ENTRIES;
 constexpr size_t FQ_TAB_DWORDS = table_dwords(FQ_TABLE_DWORDS);
 // G1 multiples: the four slots that g1_mul_fixed (0), the BBS+ columns (h0, h_1, h_2, h_3) and bbs04 (u, v, h, g1) share, and the nb tables
-// of the per-lane sums; G2 multiples; line tables: one Q (pair_fixed_g2), BBS+'s w and g2 (rule 1), the k points of a product.  bbs04's
+// of the per-lane sums; G2 multiples: the slot of g2_mul_fixed, BBS+ and bbs04, and the nb tables of the G2 per-lane sums; line tables: one Q (pair_fixed_g2), BBS+'s w and g2 (rule 1), the k points of a product.  bbs04's
 // product (rule 0) and BBS+ have a workspace each, so neither evicts the other's tables.
 constexpr table_array fb_g1_slot(int i) { return {c12381_ctx::WS_FB_G1_0 + i, 1, table_dwords(FB_G1_ENTRIES * FB_G1_DWORDS), 0, 96}; }
 constexpr table_array TA_FB_G1_SUM = {c12381_ctx::WS_FB_G1_SUM, G1_FIXED_SUM_MAX, table_dwords(FB_G1_ENTRIES * FB_G1_DWORDS), GATE_DWORDS, 96};
 constexpr table_array TA_FB_G2 = {c12381_ctx::WS_FB_G2, 1, table_dwords(FB_G2_ENTRIES * FB_G2_DWORDS), 0, 192};
+constexpr table_array TA_FB_G2_SUM = {c12381_ctx::WS_FB_G2_SUM, G2_FIXED_SUM_MAX, table_dwords(FB_G2_ENTRIES * FB_G2_DWORDS), GATE_DWORDS, 192};
 constexpr table_array TA_FQ_P = {c12381_ctx::WS_FQ_P, 1, FQ_TAB_DWORDS, 0, 192};
 constexpr table_array TA_FQ_WG = {c12381_ctx::WS_FQ_W, 2, FQ_TAB_DWORDS, GATE_DWORDS, 192};
 constexpr table_array TA_FQ_K = {c12381_ctx::WS_FQ_K, FIXED_G2_MAX, FQ_TAB_DWORDS, GATE_DWORDS, 192};
@@ -307,7 +308,7 @@ int cached_tables(c12381_ctx* c, const table_array& a, int k, const table_points
     HIPCK(c, hipGetLastError());
     return 0;
 }
-// the fixed-base tables of nb G1 points 96 bytes apart / of one G2 point
+// the fixed-base tables of nb G1 points 96 bytes apart / of nb G2 points 192 bytes apart
 int g1_fixed_tables(c12381_ctx* c, const table_array& a, int nb, const uint8_t* bases96, cached& t) {
     table_points pts = {};
     for (int i = 0; i < nb; ++i) pts.p[i] = bases96 + 96 * i;
@@ -319,11 +320,14 @@ int g1_fixed_table(c12381_ctx* c, int slot, const uint8_t* base96) {
     cached t;
     return g1_fixed_tables(c, fb_g1_slot(slot), 1, base96, t);
 }
-int g2_fixed_table(c12381_ctx* c, const uint8_t* base192, cached& t) {
-    return cached_tables(c, TA_FB_G2, 1, table_points{{base192}}, t, [&](const cached& b) {
-        hipLaunchKernelGGL(g2_fixed_table_kernel, dim3(grid_for(FB_G2_ENTRIES)), dim3(BLOCK), 0, c->stream, base192, b.tabs);
+int g2_fixed_tables(c12381_ctx* c, const table_array& a, int nb, const uint8_t* bases192, cached& t) {
+    table_points pts = {};
+    for (int i = 0; i < nb; ++i) pts.p[i] = bases192 + 192 * i;
+    return cached_tables(c, a, nb, pts, t, [&](const cached& b) {
+        hipLaunchKernelGGL(g2_fixed_tables_kernel, dim3(grid_for(FB_G2_ENTRIES), (unsigned)nb), dim3(BLOCK), 0, c->stream, bases192, b.tabs, b.stride);
     });
 }
+int g2_fixed_table(c12381_ctx* c, const uint8_t* base192, cached& t) { return g2_fixed_tables(c, TA_FB_G2, 1, base192, t); }
 // Line tables of the k points q.p[j] (coefficients of a fixed G2 argument of the Miller loop, pairing3.hpp) and, where the array has one, the
 // gate over the k.  rule: bit 0 need_g2, bit 1 raw records (k_pairk.hip g2_lines_tables_kernel); a table is also rebuilt when its rule changes.
 int lines_tables(c12381_ctx* c, const table_array& a, int k, const g2_cols& q, int rule, cached& t) {
@@ -544,7 +548,7 @@ static bool msm_use_buckets(size_t n) {
 
 extern "C" {
 
-int c12381_version(void) { return (0 << 16) | 4; }
+int c12381_version(void) { return (0 << 16) | 5; }
 
 int c12381_create(int device, c12381_ctx** out) {
     if (!out) return C12381_E_ARG;
@@ -899,11 +903,13 @@ int c12381_g1_msm_multi(c12381_ctx** ctxs, int ngpu, size_t n, const uint8_t* pt
 // ---------------------------------------------------------------- G2
 // finish = true: the kernel leaves projective results in WS_PROJ (the caller has sized it: 6 NL x round_up(n, 64) dwords)
 // and g2_finish converts them with one inversion per FINISH_M elements; false: per-lane conversion straight to `out`.
+// proj_stride / proj_off (finish = true): the results go to proj[proj_off + i] of an SoA with that stride; 0 = round_up(n, 64), the batch
+// entry points' own layout.  g2_finish reads elements [0, n) of the same SoA.
 static int g2_mul_dev_strided(c12381_ctx* c, size_t n, const uint8_t* pts, size_t pt_stride, const uint8_t* sc, uint8_t* out, int fmt,
-                              const int32_t* skip_if = nullptr, bool finish = false, bool in_g2 = false);
-static int g2_finish(c12381_ctx* c, size_t n, uint8_t* d_out, int fmt) {
+                              const int32_t* skip_if = nullptr, bool finish = false, bool in_g2 = false, size_t proj_stride = 0, size_t proj_off = 0);
+static int g2_finish(c12381_ctx* c, size_t n, uint8_t* d_out, int fmt, size_t proj_stride = 0) {
     int rc;
-    const size_t stride = round_up(n, 64);
+    const size_t stride = proj_stride ? proj_stride : round_up(n, 64);
     if ((rc = ensure(c, c12381_ctx::WS_PREF, (size_t)2 * NL * stride * 4))) return rc;
     const size_t T = finish_lanes(n);
     hipLaunchKernelGGL(g2_finish_kernel, dim3(grid_for(T)), dim3(BLOCK), 0, c->stream, n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride,
@@ -927,8 +933,9 @@ int c12381_g2_mul_batch_dev(c12381_ctx* c, size_t n, const uint8_t* pts, const u
     return c12381_g2_mul_batch_flags_dev(c, n, pts, sc, out, fmt, 0u);
 }
 static int g2_mul_dev_strided(c12381_ctx* c, size_t n, const uint8_t* pts, size_t pt_stride, const uint8_t* sc, uint8_t* out, int fmt,
-                              const int32_t* skip_if, bool finish, bool in_g2) {
+                              const int32_t* skip_if, bool finish, bool in_g2, size_t proj_stride, size_t proj_off) {
     int rc;
+    if (!proj_stride) proj_stride = round_up(n, 64);
     const size_t chunk = n < G2_CHUNK ? round_up(n, 64) : G2_CHUNK;
     // C12381_G2_LANES=1 keeps the one-lane-per-point kernel for the batch entry points (A/B measurements); default:
     // two lanes per point (k_g2h.hip), whose per-lane table records are those of G1 (2 x 1408 B per point)
@@ -941,12 +948,12 @@ static int g2_mul_dev_strided(c12381_ctx* c, size_t n, const uint8_t* pts, size_
         timed tm(c, 2);
         if (pairwise) {
             hipLaunchKernelGGL(g2_mul2_kernel, dim3(grid_for(2 * m)), dim3(BLOCK), 0, c->stream, m, pts + pt_stride * off, pt_stride, sc + 32 * off,
-                               (int32_t*)c->ws[c12381_ctx::WS_TAB], c->d_flag, skip_if, proj, round_up(n, 64), off, in_g2 ? 1 : 0);
+                               (int32_t*)c->ws[c12381_ctx::WS_TAB], c->d_flag, skip_if, proj, proj_stride, proj_off + off, in_g2 ? 1 : 0);
             HIPCK(c, hipGetLastError());
             continue;
         }
         hipLaunchKernelGGL(g2_mul_kernel, dim3(grid_for(m)), dim3(BLOCK), 0, c->stream, m, pts + pt_stride * off, pt_stride, sc + 32 * off,
-                           (int32_t*)c->ws[c12381_ctx::WS_TAB], chunk, out + (size_t)fmt * off, fmt, c->d_flag, skip_if, proj, round_up(n, 64), off, in_g2 ? 1 : 0);
+                           (int32_t*)c->ws[c12381_ctx::WS_TAB], chunk, out + (size_t)fmt * off, fmt, c->d_flag, skip_if, proj, proj_stride, proj_off + off, in_g2 ? 1 : 0);
         HIPCK(c, hipGetLastError());
     }
     return 0;
@@ -1282,7 +1289,10 @@ int c12381_pair_product_fixed_g2_batch(c12381_ctx* c, size_t n, int k, const uin
 // Fast route — g2, X2 and every Y2_i elements of G2 other than infinity, nmsg + 2 <= C12381_FIXED_G2_MAX: the argument of the BBS+ path
 // (bilinearity in the G2 argument holds for every curve point s1, and the cofactor part of a GLV multiple m_i s1 pairs to 1 against G2)
 // turns the equation into  e(-s2, g2) * e(s1, X2) * prod_i e(m_i s1, Y2_i) == 1,  ONE K = nmsg + 2 way product over line tables.
-// Generic route — anything else: W_j = X2 + sum_i m_ij Y2_i by the G2 multiplication and addition kernels, then the pair_eq kernels.
+// Generic route — anything else: W_j = X2 + sum_i m_ij Y2_i, then the pair_eq kernels.  With more messages than the product takes
+// (C12381_FIXED_G2_MAX - 2 < nmsg <= C12381_G2_FIXED_SUM_MAX) W is ONE per-lane sum over the shared bases Y2 with the addend X2
+// (c12381_g2_mul_fixed_sum_batch_dev: nmsg tables for keys in G2, its own generic columns otherwise; an off-twist key marks every W 0xff and
+// raises the status word, and pair_eq turns a 0xff W into a 0xff lane).  Otherwise by the G2 multiplication and addition kernels per column.
 // The gate over the K tables picks the route on the device: every kernel of both routes is enqueued and the other route's return at once.
 static int ps_verify_args(size_t nmsg, const void* g2, const void* X2, const void* Y2, const void* s1, const void* s2, const void* m, const void* ok) {
     return (!g2 || !X2 || !s1 || !s2 || !ok || (nmsg && (!Y2 || !m))) ? C12381_E_ARG : 0;
@@ -1309,6 +1319,8 @@ int c12381_ps_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8
     if (nmsg == 0) {
         hipLaunchKernelGGL(g2_bcast_kernel, dim3(grid_for(192 * n)), dim3(BLOCK), 0, c->stream, n, X2_192, d_w, gate_generic);
         HIPCK(c, hipGetLastError());
+    } else if (!fast && nmsg <= (size_t)C12381_G2_FIXED_SUM_MAX) {
+        if ((rc = c12381_g2_mul_fixed_sum_batch_dev(c, n, nmsg, Y2_192, X2_192, m_32, d_w, 192))) return rc;
     } else {
         if ((rc = ensure(c, c12381_ctx::WS_BBS_B, 192 * n))) return rc;
         uint8_t* d_b = (uint8_t*)c->ws[c12381_ctx::WS_BBS_B];
@@ -1690,6 +1702,46 @@ int c12381_g2_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base192, c
     if (n == 0) return 0;
     staging s;
     if ((rc = stage(c, s, {{base192, 192}, {sc, 32 * n}}, {{out, (size_t)fmt * n}})) || (rc = c12381_g2_mul_fixed_batch_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
+    return unstage(c, s);
+}
+// The G2 form of the per-lane sums above, route for route: TA_FB_G2_SUM holds a gate and G2_FIXED_SUM_MAX tables of the 2040 multiples, the generic
+// columns go through the kernel of c12381_g2_mul_batch into proj[half, half + n) and are folded into proj[0, n) by g2_fixed_sum_fold_kernel.
+static_assert(C12381_G2_FIXED_SUM_MAX == G2_FIXED_SUM_MAX, "public and device bound of nb");
+static int g2_fixed_sum_args(size_t nb, const void* bases, const void* sc, const void* out, int fmt) {
+    return (nb < 1 || nb > C12381_G2_FIXED_SUM_MAX || !bases || !sc || !out || !g2_fmt(fmt)) ? C12381_E_ARG : 0;
+}
+int c12381_g2_mul_fixed_sum_batch_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc, uint8_t* out,
+                                      int fmt) {
+    int rc = bind(c); if (rc || (rc = g2_fixed_sum_args(nb, bases192, sc, out, fmt))) return rc;
+    if (n == 0) return 0;
+    const bool fb = fixed_base_enabled();
+    cached t;
+    if ((rc = g2_fixed_tables(c, TA_FB_G2_SUM, fb ? (int)nb : 0, bases192, t))) return rc;      // without tables: the gate buffer alone
+    const int32_t *gate = t.gate, *tabs = t.tabs;
+    const size_t half = round_up(n, 64), stride = 2 * half;       // proj[0, n): the sums; proj[half, half + n): the generic route's current column
+    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)6 * NL * stride * 4))) return rc;
+    int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
+    hipLaunchKernelGGL(g2_fixed_sum_gate_kernel, dim3(1), dim3(64), 0, c->stream, (int)nb, bases192, addend192, t.gate, tabs, t.stride, fb ? 1 : 0, c->d_flag);
+    HIPCK(c, hipGetLastError());
+    if (fb) {
+        hipLaunchKernelGGL(g2_fixed_sum_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (int)nb, gate, tabs, t.stride, sc, addend192, proj, stride);
+        HIPCK(c, hipGetLastError());
+    }
+    for (size_t col = 0; col < nb; ++col) {
+        if ((rc = g2_mul_dev_strided(c, n, bases192 + 192 * col, 0, sc + 32 * n * col, out, fmt, gate, true, false, stride, col ? half : 0))) return rc;
+        if (col == 0 && nb > 1) continue;                          // the first column is written in place
+        hipLaunchKernelGGL(g2_fixed_sum_fold_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, gate, proj, stride, half, col ? 1 : 0,
+                           col + 1 == nb ? 1 : 0, addend192);
+        HIPCK(c, hipGetLastError());
+    }
+    return g2_finish(c, n, out, fmt, stride);
+}
+int c12381_g2_mul_fixed_sum_batch(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc, uint8_t* out, int fmt) {
+    int rc = bind(c); if (rc || (rc = g2_fixed_sum_args(nb, bases192, sc, out, fmt))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{bases192, 192 * nb}, {addend192, 192}, {sc, 32 * n * nb}}, {{out, (size_t)fmt * n}}))) return rc;
+    if ((rc = c12381_g2_mul_fixed_sum_batch_dev(c, n, nb, s.in[0], s.in[1], s.in[2], s.out[0], fmt))) return rc;
     return unstage(c, s);
 }
 

@@ -78,6 +78,27 @@ template <class F> C12381_HD void g2_add_core(g2pt<F>& p, const g2pt<F>& q) {
     fp2_mul2<false>(p.z, z3, t4, t3, t0);          // Z3 = z3 t4 + t3 t0
 }
 template <class F> C12381_HDN void g2_add(g2pt<F>& p, const g2pt<F>& q) { g2_add_core(p, q); }
+// The same addition for an affine Q = (qx, qy), Z2 = 1 (RCB algorithm 8 with a = 0): Z1 Z2 is Z1, and (Y1 + Z1)(Y2 + Z2) - Y1 Y2 - Z1 Z2 =
+// Y1 + Z1 Y2, (X1 + Z1)(X2 + Z2) - X1 X2 - Z1 Z2 = X1 + Z1 X2 — 11 products and 8 reductions for 12 and 9, the same X3, Y3, Z3 mod p as
+// g2_add_core gives for (qx : qy : 1).  Complete for every P and every FINITE Q on a curve of odd order; Q = infinity has no affine form.
+template <class F> C12381_HD void g2_add_affine_core(g2pt<F>& p, const F& qx, const F& qy) {
+    F t0, t1, t2, t3, t4, y3, z3;
+    fp2_mul(t0, p.x, qx);
+    fp2_mul(t1, p.y, qy);
+    fp2_add(t3, p.x, p.y); fp2_norm1(t3, t3); fp2_add(t4, qx, qy); fp2_mul(t3, t3, t4);
+    fp2_add(t4, t0, t1); fp2_sub(t3, t3, t4); fp2_norm1(t3, t3);
+    fp2_mul(t4, p.z, qy); fp2_add(t4, t4, p.y); fp2_norm1(t4, t4);
+    fp2_mul(y3, p.z, qx); fp2_add(y3, y3, p.x);
+    fp2_mul_small(t0, t0, 3);
+    fp2_mul_b3(t2, p.z);
+    fp2_add(z3, t1, t2); fp2_norm1(z3, z3);
+    fp2_sub(t1, t1, t2); fp2_norm1(t1, t1);
+    fp2_mul_b3(y3, y3);
+    fp2_mul2<true>(p.x, t3, t1, y3, t4);           // X3 = t3 t1 - y3 t4
+    fp2_mul2<false>(p.y, y3, t0, z3, t1);          // Y3 = y3 t0 + z3 t1
+    fp2_mul2<false>(p.z, z3, t4, t3, t0);          // Z3 = z3 t4 + t3 t0
+}
+template <class F> C12381_HDN void g2_add_affine(g2pt<F>& p, const F& qx, const F& qy) { g2_add_affine_core(p, qx, qy); }
 // element types whose scalar-multiplication loop keeps the running point in registers: doublings and additions inlined into the
 // window loop (like g1_scalar_mul) instead of out-of-line routines that take the point through private memory.  Pays where the
 // whole addition fits the register file — the two-lane form (fp2h.hpp specialises this to true).

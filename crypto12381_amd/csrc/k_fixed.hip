@@ -1,5 +1,5 @@
 // Fixed-base columns (fixed_base.hpp): table construction with a device-side "same base as last time?" check, and
-// the table-driven evaluation kernels (one base per column, and per-lane sums over a set of bases).
+// the table-driven evaluation kernels (one base per column, and per-lane sums over a set of bases, in G1 and in G2).
 // The cache protocol of every device-built table (fixed-base multiples here, line coefficients in k_pairk.hip; the host side is
 // c12381_hip.hip cached_tables).  A table is HDR_DWORDS of header and its entries; the tables of an array lie tab_stride dwords apart:
 //   header[0..47]        the cached point's canonical bytes as dwords (96 B for G1, 192 B for G2)
@@ -145,10 +145,10 @@ __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_sum_fold_kernel(size_t n, c
     soa_store_g1(proj, proj_stride, j, o);
 }
 
-__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_table_kernel(const uint8_t* base192, int32_t* buf) {
+// entry L of the table of base192, as g1_fixed_table_entry
+static __device__ __forceinline__ void g2_fixed_table_entry(const uint8_t* base192, int32_t* buf, size_t L) {
     int32_t* header = buf;
-    if (header[HDR_REBUILD] == 0) return;
-    const size_t L = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (header[HDR_REBUILD] == 0) return;                                   // cached table is current
     if (L >= (size_t)FB_G2_WINDOWS * FB_ENTRIES) return;
     g2p base;
     bool inf, ok;
@@ -166,6 +166,11 @@ __global__ void __launch_bounds__(BLOCK, 2) g2_fixed_table_kernel(const uint8_t*
     fp2_mul(ax, acc.x, zi); fp2_mul(ay, acc.y, zi);
     fp2_norm1(ax, ax); fp2_norm1(ay, ay);
     fb_store_g2(buf + FB_HEADER_DWORDS + L * FB_G2_DWORDS, ax, ay);
+}
+// the tables of a set of bases (192 bytes apart) in one launch: blockIdx.y = base, as g1_fixed_tables_kernel; the single table of
+// c12381_g2_mul_fixed_batch is an array of one
+__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_tables_kernel(const uint8_t* bases192, int32_t* tabs, int tab_stride) {
+    g2_fixed_table_entry(bases192 + (size_t)192 * blockIdx.y, tabs + (size_t)blockIdx.y * tab_stride, (size_t)blockIdx.x * BLOCK + threadIdx.x);
 }
 
 // out[i] = addend + [k_i]Q (affine, canonical 192 B or 97 B — or projective SoA for g2_finish_kernel when proj is given);
@@ -195,5 +200,72 @@ __global__ void __launch_bounds__(BLOCK, 2) g2_fixed_eval_kernel(size_t n, const
     if (proj) g2_store_proj(proj, proj_stride, i, acc, !wok);                // kernel-uniform: affine conversion by g2_finish_kernel
     else g2_store_affine(out + (size_t)fmt * i, acc, fmt, !wok);
 }
+
+// ---- per-lane sums over a set of shared G2 bases (c12381_g2_mul_fixed_sum_batch): out[j] = addend + sum_i [k_(i n + j)]Q_i
+// The gate words and the two routes are those of the G1 form above (g1_fixed_sum_gate_kernel): gate[HDR_VALID] = every base has a valid
+// table, (gate + GATE_OTHER)[HDR_VALID] = the opposite, gate[HDR_RULE] = a base or the addend is not on the twist.
+__global__ void __launch_bounds__(64, 1) g2_fixed_sum_gate_kernel(int nb, const uint8_t* bases192, const uint8_t* addend192, int32_t* gate,
+                                                                 const int32_t* tabs, int tab_stride, int use_tables, int* bad_flag) {
+    const int t = threadIdx.x;
+    bool ok = true, valid = true;
+    if (t < nb || (t == nb && addend192)) {
+        fp2 x, y;
+        bool inf;
+        g2_parse192(x, y, inf, ok, t < nb ? bases192 + 192 * t : addend192);
+    }
+    if (t < nb) valid = use_tables && tabs[(size_t)t * tab_stride + HDR_VALID] != 0;
+    const bool all_valid = __all(valid), bad = __any(!ok);
+    if (t == 0) {
+        gate[HDR_VALID] = all_valid ? 1 : 0;
+        gate[GATE_OTHER + HDR_VALID] = all_valid ? 0 : 1;
+        gate[HDR_RULE] = bad ? 1 : 0;
+        if (bad) *bad_flag = 1;
+    }
+}
+// acc -> the lane's record for g2_finish_kernel: plus the addend (complete addition, as g2_fixed_eval_kernel adds it), or the invalid mark
+// when the gate says so
+static __device__ __forceinline__ void g2_fixed_sum_close(int32_t* proj, size_t proj_stride, size_t j, const g2p& acc, const uint8_t* addend192,
+                                                          const int32_t* gate) {
+    g2p o;
+    g2_norm1(o, acc);
+    if (addend192) {                                      // kernel-uniform
+        g2p w, inf_pt;
+        bool winf, wok;
+        g2_parse192(w.x, w.y, winf, wok, addend192);
+        fp2_one(w.z);
+        g2_set_inf(inf_pt);
+        fp2_select(w.x, winf, inf_pt.x, w.x); fp2_select(w.y, winf, inf_pt.y, w.y); fp2_select(w.z, winf, inf_pt.z, w.z);
+        g2_add(o, w);
+    }
+    g2_store_proj(proj, proj_stride, j, o, gate[HDR_RULE] != 0);
+}
+// proj[j] = addend + sum_(i < nb) [k_(i n + j)]Q_i from the nb tables behind the gate: one lane per output, one accumulator per lane
+// across all bases, no per-column store and no reduce pass
+__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_sum_kernel(size_t n, int nb, const int32_t* gate, const int32_t* tabs, int tab_stride,
+                                                             const uint8_t* scalars, const uint8_t* addend192, int32_t* proj, size_t proj_stride) {
+    if (gate[HDR_VALID] == 0) return;
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    g2p acc;
+    g2_fixed_eval_sum(acc, tabs + FB_HEADER_DWORDS, (size_t)tab_stride, nb, fixed_sum_scalars{scalars, n, j});
+    g2_fixed_sum_close(proj, proj_stride, j, acc, addend192, gate);
+}
+// The generic route, column by column: proj[j] += proj[col_off + j] (has_col), and behind the last column the addend / invalid mark (last)
+__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_sum_fold_kernel(size_t n, const int32_t* gate, int32_t* proj, size_t proj_stride, size_t col_off,
+                                                                  int has_col, int last, const uint8_t* addend192) {
+    if (gate[GATE_OTHER + HDR_VALID] == 0) return;
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    g2p acc;
+    soa_load_g2(acc, proj, proj_stride, j);
+    if (has_col) {
+        g2p q;
+        soa_load_g2(q, proj, proj_stride, col_off + j);
+        g2_add(acc, q);
+    }
+    if (last) g2_fixed_sum_close(proj, proj_stride, j, acc, addend192, gate);
+    else g2_store_proj(proj, proj_stride, j, acc, false);
+}
+
 
 }  // namespace c12381

@@ -143,7 +143,12 @@ constexpr int G1_FIXED_SUM_MAX = TABLE_ARRAY_MAX;
 __global__ void __launch_bounds__(64, 1) g1_fixed_sum_gate_kernel(int nb, const uint8_t* bases96, const uint8_t* addend96, int32_t* gate, const int32_t* tabs, int tab_stride, int use_tables, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_sum_kernel(size_t n, int nb, const int32_t* gate, const int32_t* tabs, int tab_stride, const uint8_t* scalars, const uint8_t* addend96, int32_t* proj, size_t proj_stride);
 __global__ void __launch_bounds__(BLOCK, 2) g1_fixed_sum_fold_kernel(size_t n, const int32_t* gate, int32_t* proj, size_t proj_stride, size_t col_off, int has_col, int last, const uint8_t* addend96);
-__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_table_kernel(const uint8_t* base192, int32_t* buf);
+__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_tables_kernel(const uint8_t* bases192, int32_t* tabs, int tab_stride);
 __global__ void __launch_bounds__(BLOCK, 2) g2_fixed_eval_kernel(size_t n, const int32_t* buf, const uint8_t* scalars, const uint8_t* addend192, uint8_t* out, int fmt, int* bad_flag, int32_t* proj, size_t proj_stride);
+// per-lane sums over a set of shared G2 bases (C12381_G2_FIXED_SUM_MAX = G2_FIXED_SUM_MAX): nb tables behind one gate, as the G1 form
+constexpr int G2_FIXED_SUM_MAX = TABLE_ARRAY_MAX;
+__global__ void __launch_bounds__(64, 1) g2_fixed_sum_gate_kernel(int nb, const uint8_t* bases192, const uint8_t* addend192, int32_t* gate, const int32_t* tabs, int tab_stride, int use_tables, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_sum_kernel(size_t n, int nb, const int32_t* gate, const int32_t* tabs, int tab_stride, const uint8_t* scalars, const uint8_t* addend192, int32_t* proj, size_t proj_stride);
+__global__ void __launch_bounds__(BLOCK, 2) g2_fixed_sum_fold_kernel(size_t n, const int32_t* gate, int32_t* proj, size_t proj_stride, size_t col_off, int has_col, int last, const uint8_t* addend192);
 
 }  // namespace c12381

@@ -320,6 +320,32 @@ int c12381_g1_mul_fixed_sum_batch(c12381_ctx* ctx, size_t n, size_t nb, const ui
                                   uint8_t* out, int out_fmt);
 int c12381_g1_mul_fixed_sum_batch_dev(c12381_ctx* ctx, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* scalars32,
                                       uint8_t* out, int out_fmt);
+/* The same in G2: out[j] = addend + sum_(i < nb) scalars[i n + j] * bases[i] over PUBLIC G2 bases shared by the whole batch — X2 * Π Y2[i]^m[i]
+ * of PS signatures (examples/ps/src/ps.cpp:98, :145), tilde_X * ... * Π tilde_Y[i]^a[i] (examples/AC-rps/src/verify.cpp:30),
+ * Π tilde_Y[n-1-i]^q[i] (examples/AC-rbbs/src/verify.cpp:22).
+ * bases192: nb points of 192 B, one set for the batch, 1 <= nb <= C12381_G2_FIXED_SUM_MAX; addend192: one point of 192 B, or NULL for none;
+ * scalars32: base-major, nb x n records of 32 B, any value below 2^256; out_fmt = 97 or 192.
+ * Value: every lane equals multiply(point2&, const big&) on each term (PAIR_G2mul: scalar mod r, the four-way GS form with its [r]psi^i(Q)
+ * terms for zero odd digits) followed by add(point2&, point2&), the addend last, for EVERY point of the twist and every scalar — the
+ * contract of c12381_g2_mul_fixed_batch; nb = 1 with a NULL addend returns the bytes of c12381_g2_mul_fixed_batch.
+ * Routes: when every base is an element of G2 other than infinity the batch runs from nb device-built tables of multiples (2040 entries
+ * of 224 B and a header: 457 KB per base, 14.6 MB at nb = 32): one accumulator per lane across all bases, up to 32 nb additions, no
+ * doubling, one projective result and one affine conversion per lane.  The additions are complete on the twist (its order is odd), so
+ * RELATED bases (H2 = +-H1, 2 H1, psi(H1)) and sums that cancel to infinity take no other path.  Otherwise the call runs column by
+ * column through the generic kernel of c12381_g2_mul_batch and sums the columns: correct for every input, at generic speed.  The device
+ * picks the route; the host never waits.
+ * Tables live in the context in a workspace of their own (not the slot of c12381_g2_mul_fixed_batch, BBS+ and bbs04), one per base
+ * position, each kept until the base at its position changes; a call whose bases are all cached costs one check launch whatever nb.
+ * c12381_trim frees them.  c12381_ps_verify_batch forms its W with this entry when C12381_FIXED_G2_MAX - 2 < nmsg <= C12381_G2_FIXED_SUM_MAX.
+ * Status: a base or the addend that is not on the twist makes every output byte 0xff and the call return C12381_E_POINT (the _dev form:
+ * the next c12381_sync, once); the context stays usable.  nb = 0, nb > C12381_G2_FIXED_SUM_MAX, a bad out_fmt or a null ctx / bases /
+ * scalars / out: C12381_E_ARG, checked before the empty-batch rule; n = 0 returns C12381_OK and touches nothing.
+ * Not constant-time: table indices and the additions executed depend on the scalars (as in the G1 entry above). */
+#define C12381_G2_FIXED_SUM_MAX 32
+int c12381_g2_mul_fixed_sum_batch(c12381_ctx* ctx, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* scalars32,
+                                  uint8_t* out, int out_fmt);
+int c12381_g2_mul_fixed_sum_batch_dev(c12381_ctx* ctx, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* scalars32,
+                                      uint8_t* out, int out_fmt);
 
 /* caller pattern of BASELINE config 5 ------------------------------------------ */
 /* ok[j] = [ e(A_j, w + x_j*g2) == e(g1 + r_j*h0 + sum_i m[i*n + j]*h_i, g2) ]: the BBS+ verification equation of the
