@@ -308,26 +308,22 @@ int cached_tables(c12381_ctx* c, const table_array& a, int k, const table_points
     HIPCK(c, hipGetLastError());
     return 0;
 }
-// the fixed-base tables of nb G1 points 96 bytes apart / of nb G2 points 192 bytes apart
-int g1_fixed_tables(c12381_ctx* c, const table_array& a, int nb, const uint8_t* bases96, cached& t) {
+// the fixed-base tables of nb points of G (fixed_base.hpp: fb_g1, fb_g2) POINT_BYTES apart
+struct host_g1 : fb_g1 { static constexpr auto tables_kernel = g1_fixed_tables_kernel; };
+struct host_g2 : fb_g2 { static constexpr auto tables_kernel = g2_fixed_tables_kernel; };
+template <class G>
+int fixed_tables(c12381_ctx* c, const table_array& a, int nb, const uint8_t* bases, cached& t) {
     table_points pts = {};
-    for (int i = 0; i < nb; ++i) pts.p[i] = bases96 + 96 * i;
+    for (int i = 0; i < nb; ++i) pts.p[i] = bases + G::POINT_BYTES * i;
     return cached_tables(c, a, nb, pts, t, [&](const cached& b) {
-        hipLaunchKernelGGL(g1_fixed_tables_kernel, dim3(grid_for(FB_G1_ENTRIES), (unsigned)nb), dim3(BLOCK), 0, c->stream, bases96, b.tabs, b.stride);
+        hipLaunchKernelGGL(G::tables_kernel, dim3(grid_for((size_t)G::WINDOWS * FB_ENTRIES), (unsigned)nb), dim3(BLOCK), 0, c->stream, bases, b.tabs, b.stride);
     });
 }
 int g1_fixed_table(c12381_ctx* c, int slot, const uint8_t* base96) {
     cached t;
-    return g1_fixed_tables(c, fb_g1_slot(slot), 1, base96, t);
+    return fixed_tables<host_g1>(c, fb_g1_slot(slot), 1, base96, t);
 }
-int g2_fixed_tables(c12381_ctx* c, const table_array& a, int nb, const uint8_t* bases192, cached& t) {
-    table_points pts = {};
-    for (int i = 0; i < nb; ++i) pts.p[i] = bases192 + 192 * i;
-    return cached_tables(c, a, nb, pts, t, [&](const cached& b) {
-        hipLaunchKernelGGL(g2_fixed_tables_kernel, dim3(grid_for(FB_G2_ENTRIES), (unsigned)nb), dim3(BLOCK), 0, c->stream, bases192, b.tabs, b.stride);
-    });
-}
-int g2_fixed_table(c12381_ctx* c, const uint8_t* base192, cached& t) { return g2_fixed_tables(c, TA_FB_G2, 1, base192, t); }
+int g2_fixed_table(c12381_ctx* c, const uint8_t* base192, cached& t) { return fixed_tables<host_g2>(c, TA_FB_G2, 1, base192, t); }
 // Line tables of the k points q.p[j] (coefficients of a fixed G2 argument of the Miller loop, pairing3.hpp) and, where the array has one, the
 // gate over the k.  rule: bit 0 need_g2, bit 1 raw records (k_pairk.hip g2_lines_tables_kernel); a table is also rebuilt when its rule changes.
 int lines_tables(c12381_ctx* c, const table_array& a, int k, const g2_cols& q, int rule, cached& t) {
@@ -1634,52 +1630,6 @@ int c12381_g1_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base96, co
     if ((rc = stage(c, s, {{base96, 96}, {sc, 32 * n}}, {{out, (size_t)fmt * n}})) || (rc = c12381_g1_mul_fixed_batch_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
     return unstage(c, s);
 }
-// ---------------------------------------------------------------- per-lane sums over a set of bases shared by the batch
-// out[j] = addend + sum_(i < nb) sc[i n + j] B_i.  TA_FB_G1_SUM: a gate and G1_FIXED_SUM_MAX tables of the 4080 multiples of fixed_base.hpp, cached
-// per position (changing one base rebuilds one table).
-// One cache-check launch, one table launch and one gate launch whatever nb; then BOTH routes are queued and the gate lets one run:
-//   every base a subgroup point   g1_fixed_sum_kernel: all nb tables into one accumulator per lane
-//   otherwise                     the columns through the generic kernel one by one, each folded into proj[0, n) (two projective arrays
-//                                 whatever nb), as bbs_message_points sums its columns
-// The skipped route's kernels return at their first load.  Nothing waits for the host.
-static_assert(C12381_G1_FIXED_SUM_MAX == G1_FIXED_SUM_MAX, "public and device bound of nb");
-static int g1_fixed_sum_args(size_t nb, const void* bases, const void* sc, const void* out, int fmt) {
-    return (nb < 1 || nb > C12381_G1_FIXED_SUM_MAX || !bases || !sc || !out || !g1_fmt(fmt)) ? C12381_E_ARG : 0;
-}
-int c12381_g1_mul_fixed_sum_batch_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc, uint8_t* out,
-                                      int fmt) {
-    int rc = bind(c); if (rc || (rc = g1_fixed_sum_args(nb, bases96, sc, out, fmt))) return rc;
-    if (n == 0) return 0;
-    const bool fb = fixed_base_enabled();
-    cached t;
-    if ((rc = g1_fixed_tables(c, TA_FB_G1_SUM, fb ? (int)nb : 0, bases96, t))) return rc;       // without tables: the gate buffer alone
-    const int32_t *gate = t.gate, *tabs = t.tabs;
-    const size_t half = round_up(n, 64), stride = 2 * half;       // proj[0, n): the sums; proj[half, half + n): the generic route's current column
-    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
-    int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
-    hipLaunchKernelGGL(g1_fixed_sum_gate_kernel, dim3(1), dim3(64), 0, c->stream, (int)nb, bases96, addend96, t.gate, tabs, t.stride, fb ? 1 : 0, c->d_flag);
-    HIPCK(c, hipGetLastError());
-    if (fb) {
-        hipLaunchKernelGGL(g1_fixed_sum_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (int)nb, gate, tabs, t.stride, sc, addend96, proj, stride);
-        HIPCK(c, hipGetLastError());
-    }
-    for (size_t col = 0; col < nb; ++col) {
-        if ((rc = g1_mul_to_proj(c, n, bases96 + 96 * col, sc + 32 * n * col, stride, 0, col ? half : 0, gate))) return rc;
-        if (col == 0 && nb > 1) continue;                          // the first column is written in place
-        hipLaunchKernelGGL(g1_fixed_sum_fold_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, gate, proj, stride, half, col ? 1 : 0,
-                           col + 1 == nb ? 1 : 0, addend96);
-        HIPCK(c, hipGetLastError());
-    }
-    return g1_finish(c, n, proj, stride, out, fmt);
-}
-int c12381_g1_mul_fixed_sum_batch(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc || (rc = g1_fixed_sum_args(nb, bases96, sc, out, fmt))) return rc;
-    if (n == 0) return 0;
-    staging s;
-    if ((rc = stage(c, s, {{bases96, 96 * nb}, {addend96, 96}, {sc, 32 * n * nb}}, {{out, (size_t)fmt * n}}))) return rc;
-    if ((rc = c12381_g1_mul_fixed_sum_batch_dev(c, n, nb, s.in[0], s.in[1], s.in[2], s.out[0], fmt))) return rc;
-    return unstage(c, s);
-}
 int c12381_g2_mul_fixed_batch_dev(c12381_ctx* c, size_t n, const uint8_t* base192, const uint8_t* sc, uint8_t* out, int fmt) {
     int rc = bind(c); if (rc || (rc = g2_mul_args(base192, sc, out, fmt, 0u))) return rc;
     if (n == 0) return 0;
@@ -1704,45 +1654,91 @@ int c12381_g2_mul_fixed_batch(c12381_ctx* c, size_t n, const uint8_t* base192, c
     if ((rc = stage(c, s, {{base192, 192}, {sc, 32 * n}}, {{out, (size_t)fmt * n}})) || (rc = c12381_g2_mul_fixed_batch_dev(c, n, s.in[0], s.in[1], s.out[0], fmt))) return rc;
     return unstage(c, s);
 }
-// The G2 form of the per-lane sums above, route for route: TA_FB_G2_SUM holds a gate and G2_FIXED_SUM_MAX tables of the 2040 multiples, the generic
-// columns go through the kernel of c12381_g2_mul_batch into proj[half, half + n) and are folded into proj[0, n) by g2_fixed_sum_fold_kernel.
-static_assert(C12381_G2_FIXED_SUM_MAX == G2_FIXED_SUM_MAX, "public and device bound of nb");
-static int g2_fixed_sum_args(size_t nb, const void* bases, const void* sc, const void* out, int fmt) {
-    return (nb < 1 || nb > C12381_G2_FIXED_SUM_MAX || !bases || !sc || !out || !g2_fmt(fmt)) ? C12381_E_ARG : 0;
+// ---------------------------------------------------------------- per-lane sums over a set of bases shared by the batch, in G1 and in G2
+// out[j] = addend + sum_(i < nb) sc[i n + j] B_i.  G::SUM (TA_FB_G1_SUM, TA_FB_G2_SUM): a gate and G*_FIXED_SUM_MAX tables of the 4080 / 2040
+// multiples of fixed_base.hpp, cached per position (changing one base rebuilds one table).
+// One cache-check launch, one table launch and one gate launch whatever nb; then BOTH routes are queued and the gate lets one run:
+//   every base a subgroup point   G::sum_kernel: all nb tables into one accumulator per lane
+//   otherwise                     the columns through the generic kernel one by one (G::column: the kernels of c12381_g1_mul_batch /
+//                                 c12381_g2_mul_batch), each into proj[half, half + n) and folded into proj[0, n) (two projective arrays
+//                                 whatever nb), as bbs_message_points sums its columns
+// The skipped route's kernels return at their first load.  Nothing waits for the host.  The route is written once (fixed_sum_dev,
+// fixed_sum_host); sum_g1 / sum_g2 hold what differs between the groups and nothing else.
+static_assert(C12381_G1_FIXED_SUM_MAX == G1_FIXED_SUM_MAX && C12381_G2_FIXED_SUM_MAX == G2_FIXED_SUM_MAX, "public and device bound of nb");
+extern "C++" {                                                      // templates inside the entry points' extern "C" block
+struct sum_g1 : host_g1 {
+    static constexpr table_array SUM = TA_FB_G1_SUM;
+    static constexpr size_t PROJ_DWORDS = 3 * NL;                     // of one projective point
+    static constexpr auto gate_kernel = g1_fixed_sum_gate_kernel;
+    static constexpr auto sum_kernel = g1_fixed_sum_kernel;
+    static constexpr auto fold_kernel = g1_fixed_sum_fold_kernel;
+    static bool fmt_ok(int fmt) { return g1_fmt(fmt); }
+    static int column(c12381_ctx* c, size_t n, const uint8_t* base, const uint8_t* sc, uint8_t*, int, size_t stride, size_t col_off, const int32_t* gate) {
+        return g1_mul_to_proj(c, n, base, sc, stride, 0, col_off, gate);
+    }
+    static int finish(c12381_ctx* c, size_t n, const int32_t* proj, size_t stride, uint8_t* out, int fmt) { return g1_finish(c, n, proj, stride, out, fmt); }
+};
+struct sum_g2 : host_g2 {
+    static constexpr table_array SUM = TA_FB_G2_SUM;
+    static constexpr size_t PROJ_DWORDS = 6 * NL;
+    static constexpr auto gate_kernel = g2_fixed_sum_gate_kernel;
+    static constexpr auto sum_kernel = g2_fixed_sum_kernel;
+    static constexpr auto fold_kernel = g2_fixed_sum_fold_kernel;
+    static bool fmt_ok(int fmt) { return g2_fmt(fmt); }
+    static int column(c12381_ctx* c, size_t n, const uint8_t* base, const uint8_t* sc, uint8_t* out, int fmt, size_t stride, size_t col_off, const int32_t* gate) {
+        return g2_mul_dev_strided(c, n, base, 0, sc, out, fmt, gate, true, false, stride, col_off);
+    }
+    static int finish(c12381_ctx* c, size_t n, const int32_t*, size_t stride, uint8_t* out, int fmt) { return g2_finish(c, n, out, fmt, stride); }
+};
+template <class G>
+static int fixed_sum_args(size_t nb, const void* bases, const void* sc, const void* out, int fmt) {
+    return (nb < 1 || nb > (size_t)G::SUM.count || !bases || !sc || !out || !G::fmt_ok(fmt)) ? C12381_E_ARG : 0;
 }
-int c12381_g2_mul_fixed_sum_batch_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc, uint8_t* out,
-                                      int fmt) {
-    int rc = bind(c); if (rc || (rc = g2_fixed_sum_args(nb, bases192, sc, out, fmt))) return rc;
+template <class G>
+static int fixed_sum_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases, const uint8_t* addend, const uint8_t* sc, uint8_t* out, int fmt) {
+    int rc = bind(c); if (rc || (rc = fixed_sum_args<G>(nb, bases, sc, out, fmt))) return rc;
     if (n == 0) return 0;
     const bool fb = fixed_base_enabled();
     cached t;
-    if ((rc = g2_fixed_tables(c, TA_FB_G2_SUM, fb ? (int)nb : 0, bases192, t))) return rc;      // without tables: the gate buffer alone
+    if ((rc = fixed_tables<G>(c, G::SUM, fb ? (int)nb : 0, bases, t))) return rc;               // without tables: the gate buffer alone
     const int32_t *gate = t.gate, *tabs = t.tabs;
     const size_t half = round_up(n, 64), stride = 2 * half;       // proj[0, n): the sums; proj[half, half + n): the generic route's current column
-    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)6 * NL * stride * 4))) return rc;
+    if ((rc = ensure(c, c12381_ctx::WS_PROJ, G::PROJ_DWORDS * stride * 4))) return rc;
     int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
-    hipLaunchKernelGGL(g2_fixed_sum_gate_kernel, dim3(1), dim3(64), 0, c->stream, (int)nb, bases192, addend192, t.gate, tabs, t.stride, fb ? 1 : 0, c->d_flag);
+    hipLaunchKernelGGL(G::gate_kernel, dim3(1), dim3(64), 0, c->stream, (int)nb, bases, addend, t.gate, tabs, t.stride, fb ? 1 : 0, c->d_flag);
     HIPCK(c, hipGetLastError());
     if (fb) {
-        hipLaunchKernelGGL(g2_fixed_sum_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (int)nb, gate, tabs, t.stride, sc, addend192, proj, stride);
+        hipLaunchKernelGGL(G::sum_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (int)nb, gate, tabs, t.stride, sc, addend, proj, stride);
         HIPCK(c, hipGetLastError());
     }
     for (size_t col = 0; col < nb; ++col) {
-        if ((rc = g2_mul_dev_strided(c, n, bases192 + 192 * col, 0, sc + 32 * n * col, out, fmt, gate, true, false, stride, col ? half : 0))) return rc;
+        if ((rc = G::column(c, n, bases + G::POINT_BYTES * col, sc + 32 * n * col, out, fmt, stride, col ? half : 0, gate))) return rc;
         if (col == 0 && nb > 1) continue;                          // the first column is written in place
-        hipLaunchKernelGGL(g2_fixed_sum_fold_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, gate, proj, stride, half, col ? 1 : 0,
-                           col + 1 == nb ? 1 : 0, addend192);
+        hipLaunchKernelGGL(G::fold_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, gate, proj, stride, half, col ? 1 : 0,
+                           col + 1 == nb ? 1 : 0, addend);
         HIPCK(c, hipGetLastError());
     }
-    return g2_finish(c, n, out, fmt, stride);
+    return G::finish(c, n, proj, stride, out, fmt);
 }
-int c12381_g2_mul_fixed_sum_batch(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c); if (rc || (rc = g2_fixed_sum_args(nb, bases192, sc, out, fmt))) return rc;
+template <class G>
+static int fixed_sum_host(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases, const uint8_t* addend, const uint8_t* sc, uint8_t* out, int fmt) {
+    int rc = bind(c); if (rc || (rc = fixed_sum_args<G>(nb, bases, sc, out, fmt))) return rc;
     if (n == 0) return 0;
     staging s;
-    if ((rc = stage(c, s, {{bases192, 192 * nb}, {addend192, 192}, {sc, 32 * n * nb}}, {{out, (size_t)fmt * n}}))) return rc;
-    if ((rc = c12381_g2_mul_fixed_sum_batch_dev(c, n, nb, s.in[0], s.in[1], s.in[2], s.out[0], fmt))) return rc;
+    if ((rc = stage(c, s, {{bases, G::POINT_BYTES * nb}, {addend, (size_t)G::POINT_BYTES}, {sc, 32 * n * nb}}, {{out, (size_t)fmt * n}}))) return rc;
+    if ((rc = fixed_sum_dev<G>(c, n, nb, s.in[0], s.in[1], s.in[2], s.out[0], fmt))) return rc;
     return unstage(c, s);
+}
+}  // extern "C++"
+int c12381_g1_mul_fixed_sum_batch_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc, uint8_t* out,
+                                      int fmt) { return fixed_sum_dev<sum_g1>(c, n, nb, bases96, addend96, sc, out, fmt); }
+int c12381_g1_mul_fixed_sum_batch(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc, uint8_t* out, int fmt) {
+    return fixed_sum_host<sum_g1>(c, n, nb, bases96, addend96, sc, out, fmt);
+}
+int c12381_g2_mul_fixed_sum_batch_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc, uint8_t* out,
+                                      int fmt) { return fixed_sum_dev<sum_g2>(c, n, nb, bases192, addend192, sc, out, fmt); }
+int c12381_g2_mul_fixed_sum_batch(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc, uint8_t* out, int fmt) {
+    return fixed_sum_host<sum_g2>(c, n, nb, bases192, addend192, sc, out, fmt);
 }
 
 // B_j = g1 + r_j h0 + sum_i m_ij h_i for a batch of BBS+ signatures (bbs+.cpp:51, :72): (nmsg + 1) columns of n scalar

@@ -116,18 +116,6 @@ C12381_HD void g1_fixed_eval(g1p& acc, const int32_t* tab, const uint32_t (&kin)
     g1_set_inf(acc);
     g1_fixed_eval_add(acc, tab, kin);
 }
-// acc = sum_(i < nb) [k_i]B_i from nb tables `tab_stride` dwords apart, scalar(i, k) handing out the lane's k_i: one accumulator across
-// all bases, base by base (the table offset is the same for every lane of a wavefront), up to 32 nb mixed additions and no doubling
-template <class SC>
-C12381_HD void g1_fixed_eval_sum(g1p& acc, const int32_t* tabs, size_t tab_stride, int nb, const SC& scalar) {
-    g1_set_inf(acc);
-#pragma unroll 1
-    for (int i = 0; i < nb; ++i) {
-        uint32_t k[8];
-        scalar(i, k);
-        g1_fixed_eval_add(acc, tabs + (size_t)i * tab_stride, k);
-    }
-}
 template <int I>
 C12381_HD void g2_fixed_digit(g2p& acc, const int32_t* tab, const uint32_t (&u)[2]) {
 #pragma unroll 1
@@ -171,17 +159,69 @@ C12381_HDN void g2_fixed_eval(g2p& acc, const int32_t* tab, const uint32_t (&kin
     g2_set_inf(acc);
     g2_fixed_eval_digits(acc, tab, kin);
 }
-// acc = sum_(i < nb) [k_i]Q_i from nb tables `tab_stride` dwords apart, scalar(i, k) handing out the lane's k_i: one accumulator across
-// all bases, base by base (the table offset is the same for every lane of a wavefront), up to 32 nb additions and no doubling
-template <class SC>
-C12381_HD void g2_fixed_eval_sum(g2p& acc, const int32_t* tabs, size_t tab_stride, int nb, const SC& scalar) {
-    g2_set_inf(acc);
+
+// ---- The two groups as the routines that are the same text in both see them: the table entry and the per-lane sum here, the kernel bodies of
+// k_fixed.hip and the host routes of c12381_hip.hip through descriptions derived from these.  What differs in substance stays per group
+// above: the evaluation (GLV, 2 x 16 windows | GS behind psi, 4 x 8 windows), the subgroup test, the doublings of an entry.
+struct fb_g1 {
+    using point = g1p; using coord = fp;
+    static constexpr int POINT_BYTES = 96, WINDOWS = FB_G1_WINDOWS, ENTRY_DWORDS = FB_G1_DWORDS;
+    static C12381_HD void set_inf(g1p& p) { g1_set_inf(p); }
+    static C12381_HD void norm1(g1p& r, const g1p& p) { g1_norm1(r, p); }
+    static C12381_HD void add(g1p& p, const g1p& q) { g1_add(p, q); }
+    static C12381_HD bool in_subgroup(const g1p& p) { return g1_in_subgroup(p); }
+    static C12381_HD void eval_add(g1p& acc, const int32_t* tab, const uint32_t (&k)[8]) { g1_fixed_eval_add(acc, tab, k); }
+    static C12381_HD void entry(g1p& acc, const g1p& base, uint32_t d, int shift) { g1_fixed_entry(acc, base, d, shift); }
+    static C12381_HD void store_affine(int32_t* dst, const g1p& acc) {       // the table keeps (X / Z, Y / Z)
+        fp zn, zi, ax, ay;
+        fp_norm1(zn, acc.z);
+        fp_inv(zi, zn);
+        g1p an;
+        g1_norm1(an, acc);
+        g1_to_affine(ax, ay, an, zi);
+        msm_store_pt(dst, ax, ay);
+    }
+};
+struct fb_g2 {
+    using point = g2p; using coord = fp2;
+    static constexpr int POINT_BYTES = 192, WINDOWS = FB_G2_WINDOWS, ENTRY_DWORDS = FB_G2_DWORDS;
+    static C12381_HD void set_inf(g2p& p) { g2_set_inf(p); }
+    static C12381_HD void norm1(g2p& r, const g2p& p) { g2_norm1(r, p); }
+    static C12381_HD void add(g2p& p, const g2p& q) { g2_add(p, q); }
+    static C12381_HD bool in_subgroup(const g2p& p) { return g2_in_subgroup(p); }
+    static C12381_HD void eval_add(g2p& acc, const int32_t* tab, const uint32_t (&k)[8]) { g2_fixed_eval_add(acc, tab, k); }
+    static C12381_HD void entry(g2p& acc, const g2p& base, uint32_t d, int shift) { g2_fixed_entry(acc, base, d, shift); }
+    static C12381_HD void store_affine(int32_t* dst, const g2p& acc) {
+        fp2 zn, zi, ax, ay;
+        fp2_norm1(zn, acc.z);
+        fp2_inv(zi, zn);
+        fp2_mul(ax, acc.x, zi); fp2_mul(ay, acc.y, zi);
+        fp2_norm1(ax, ax); fp2_norm1(ay, ay);
+        fb_store_g2(dst, ax, ay);
+    }
+};
+// entry L = j FB_ENTRIES + d - 1 of the table of `base` (Z = 1): [d 2^(8j)]base, affine.  The table kernels' lanes and the host simulations
+// of tests/host_sim/ build their entries with this one routine.
+template <class G>
+C12381_HD void fixed_table_put(int32_t* dst, const typename G::point& base, size_t L) {
+    typename G::point acc;
+    G::entry(acc, base, (uint32_t)(L % FB_ENTRIES) + 1u, 8 * (int)(L / FB_ENTRIES));
+    G::store_affine(dst, acc);
+}
+// acc = sum_(i < nb) [k_i]B_i from nb tables `tab_stride` dwords apart, scalar(i, k) handing out the lane's k_i: one accumulator across
+// all bases, base by base (the table offset is the same for every lane of a wavefront), up to 32 nb mixed additions and no doubling
+template <class G, class SC>
+C12381_HD void fixed_eval_sum(typename G::point& acc, const int32_t* tabs, size_t tab_stride, int nb, const SC& scalar) {
+    G::set_inf(acc);
 #pragma unroll 1
     for (int i = 0; i < nb; ++i) {
         uint32_t k[8];
         scalar(i, k);
-        g2_fixed_eval_add(acc, tabs + (size_t)i * tab_stride, k);
+        G::eval_add(acc, tabs + (size_t)i * tab_stride, k);
     }
 }
+// the per-group spellings of the sum, for callers that name the group (the body is fixed_eval_sum alone)
+template <class SC> C12381_HD void g1_fixed_eval_sum(g1p& acc, const int32_t* tabs, size_t tab_stride, int nb, const SC& scalar) { fixed_eval_sum<fb_g1>(acc, tabs, tab_stride, nb, scalar); }
+template <class SC> C12381_HD void g2_fixed_eval_sum(g2p& acc, const int32_t* tabs, size_t tab_stride, int nb, const SC& scalar) { fixed_eval_sum<fb_g2>(acc, tabs, tab_stride, nb, scalar); }
 
 }  // namespace c12381

@@ -76,12 +76,9 @@ __global__ void __launch_bounds__(BLOCK, 2) g2_finish_kernel(size_t n, const int
 __global__ void __launch_bounds__(BLOCK, 2) g2_lift_kernel(size_t n, const uint8_t* pts, int32_t* proj, size_t stride, int* bad_flag) {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    g2p p, inf_pt;
+    g2p p;
     bool inf, ok;
-    g2_parse192(p.x, p.y, inf, ok, pts + 192 * i);
-    fp2_one(p.z);
-    g2_set_inf(inf_pt);
-    fp2_select(p.x, inf, inf_pt.x, p.x); fp2_select(p.y, inf, inf_pt.y, p.y); fp2_select(p.z, inf, inf_pt.z, p.z);
+    g2_parse192_proj(p, inf, ok, pts + 192 * i);
     if (!ok) *bad_flag = 1;
     g2_store_proj(proj, stride, i, p, !ok);
 }

@@ -121,6 +121,14 @@ __device__ __forceinline__ void g2_parse192(fp2& x, fp2& y, bool& inf, bool& ok,
     fp2_load_raw96(x, p); fp2_load_raw96(y, p + 96);
     ok = inf || g2_on_curve(x, y);
 }
+// the same as a projective point: (x : y : 1), or the point at infinity for the all-zero record (as g1_parse96_proj)
+__device__ __forceinline__ void g2_parse192_proj(g2p& p, bool& inf, bool& ok, const uint8_t* src) {
+    g2p inf_pt;
+    g2_parse192(p.x, p.y, inf, ok, src);
+    fp2_one(p.z);
+    g2_set_inf(inf_pt);
+    fp2_select(p.x, inf, inf_pt.x, p.x); fp2_select(p.y, inf, inf_pt.y, p.y); fp2_select(p.z, inf, inf_pt.z, p.z);
+}
 // The 97-byte form (g2_point.hpp:73-77 in front of ECP2_fromOctet ecp2_BLS12381.cpp:225-266): leading 0x00 = infinity; any tag other
 // than 0x04 is "compressed, sign = tag & 1" (ECP2_setx: an Fp2 square root); 0x04 announces the 193-byte form and is rejected here.
 __device__ __noinline__ void g2_parse97(fp2& x, fp2& y, bool& inf, bool& ok, const uint8_t* sp) {

@@ -1,124 +1,32 @@
-// TEST HARNESS (CPU): the per-lane sum over shared bases of fixed_base.hpp (g1_fixed_eval_sum: nb tables of multiples, one accumulator per
-// lane across all bases) compiled for the host with C12381_CHECK_BOUNDS, lane by lane; the addend is added as g1_fixed_sum_kernel adds it.
-// Table entries are built lazily with g1_fixed_entry, exactly as the table kernel computes them, and kept per base for the life of the
-// process, so a test file pays for an entry once.  Not a product path.
-#include <cstdint>
-#include <cstring>
-#include <map>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "../../crypto12381_amd/csrc/fp.hpp"
-#include "../../crypto12381_amd/csrc/codec.hpp"
-#include "../../crypto12381_amd/csrc/g1.hpp"
-#include "../../crypto12381_amd/csrc/fixed_base.hpp"
+// TEST HARNESS (CPU): the per-lane sum over shared G1 bases under the bounds checker: fixed_sum_sim.hpp with the G1 description; the
+// addend is added as g1_fixed_sum_kernel adds it.  Not a product path.
+#include "fixed_sum_sim.hpp"
 
 using namespace c12381;
 
 namespace {
 
-constexpr size_t ENTRIES = (size_t)FB_G1_WINDOWS * FB_ENTRIES;
-constexpr size_t TAB_STRIDE = ENTRIES * FB_G1_DWORDS;             // dwords between the tables of two bases (no headers here)
-
-struct table {
-    g1p base;
-    std::vector<int32_t> entries = std::vector<int32_t>(ENTRIES * FB_G1_DWORDS, 0);
-    std::vector<char> done = std::vector<char>(ENTRIES, 0);
-};
-std::map<std::string, table> g_tables;                            // by the base's 96 bytes
-
-bool parse96(g1p& p, const uint8_t* src) {                        // -> false for the all-zero record (infinity)
-    uint32_t rp[24];
-    std::memcpy(rp, src, 96);
-    if (raw_all_zero(rp, 24)) { g1_set_inf(p); return false; }
-    fp_from_raw48(p.x, rp); fp_from_raw48(p.y, rp + 12); fp_one(p.z);
-    return true;
-}
-
-void build_entry(table& t, size_t L) {
-    const int j = (int)(L / FB_ENTRIES);
-    const uint32_t d = (uint32_t)(L % FB_ENTRIES) + 1u;
-    g1p acc, an;
-    g1_fixed_entry(acc, t.base, d, 8 * j);
-    fp zn, zi, ax, ay, axn, ayn;
-    fp_norm1(zn, acc.z); fp_inv(zi, zn);
-    g1_norm1(an, acc);
-    g1_to_affine(ax, ay, an, zi);
-    fp_norm1(axn, ax); fp_norm1(ayn, ay);
-    msm_store_pt(t.entries.data() + L * FB_G1_DWORDS, axn, ayn);
-}
-
-// the scalar of base i for lane j of a base-major array, as the kernel's functor hands it out
-struct sim_scalars {
-    const uint8_t* sc; size_t n, j;
-    void operator()(int i, uint32_t (&k)[8]) const {
-        uint32_t rs[8];
-        std::memcpy(rs, sc + 32 * ((size_t)i * n + j), 32);
-        scalar_from_raw32(k, rs);
+struct sim_g1 : fb_g1 {
+    static bool parse(g1p& p, const uint8_t* src) {
+        uint32_t rp[24];
+        std::memcpy(rp, src, 96);
+        if (raw_all_zero(rp, 24)) { g1_set_inf(p); return false; }
+        fp_from_raw48(p.x, rp); fp_from_raw48(p.y, rp + 12); fp_one(p.z);
+        return true;
     }
-};
-
-}  // namespace
-
-extern "C" {
-
-// out[j] = addend + sum_(i < nb) [scalars[i n + j]] bases[i] for n lanes through the table path (96-byte affine points on the curve, all-zero =
-// infinity; addend96 may be null; 32-byte big-endian scalars, base-major) -> 96-byte affine results (all-zero = infinity).
-// Returns -2 when a base is the point at infinity or not in the order-r subgroup (the library runs the generic route then).
-int sim_g1_fixed_sum_batch(size_t n, int nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* scalars32, uint8_t* out) {
-    if (nb < 1 || nb > 32) return -1;
-    std::vector<table*> tabs((size_t)nb);
-    for (int i = 0; i < nb; ++i) {
-        const std::string key((const char*)bases96 + 96 * i, 96);
-        auto it = g_tables.find(key);
-        if (it == g_tables.end()) {
-            g1p b;
-            if (!parse96(b, bases96 + 96 * i) || !g1_in_subgroup(b)) return -2;
-            it = g_tables.emplace(key, table()).first;
-            it->second.base = b;
-        }
-        tabs[(size_t)i] = &it->second;
+    template <class F>
+    static void entries(const uint32_t (&k)[8], F f) {                    // the windows of g1_fixed_eval_add
+        uint32_t k0[4], k1[4];
+        scalar_glv_split(k0, k1, k);
+        for (int w = 0; w < FB_G1_WINDOWS; ++w)
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t d = ((h ? k1 : k0)[w >> 2] >> (8 * (w & 3))) & 255u;
+                if (d) f((size_t)w * FB_ENTRIES + (d - 1));
+            }
     }
-    // the entries this batch reads and no table has yet
-    std::vector<std::pair<table*, size_t>> need;
-    for (int i = 0; i < nb; ++i)
-        for (size_t j = 0; j < n; ++j) {
-            uint32_t k[8], k0[4], k1[4];
-            sim_scalars{scalars32, n, j}(i, k);
-            scalar_mod_r(k);
-            scalar_glv_split(k0, k1, k);
-            for (int w = 0; w < FB_G1_WINDOWS; ++w)
-                for (int h = 0; h < 2; ++h) {
-                    const uint32_t d = ((h ? k1 : k0)[w >> 2] >> (8 * (w & 3))) & 255u;
-                    if (!d) continue;
-                    const size_t L = (size_t)w * FB_ENTRIES + (d - 1);
-                    if (tabs[(size_t)i]->done[L]) continue;
-                    tabs[(size_t)i]->done[L] = 1;
-                    need.emplace_back(tabs[(size_t)i], L);
-                }
-        }
-    const size_t T = need.size() < 64 ? 1 : 8;
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < T; ++t)
-        th.emplace_back([&, t] { for (size_t e = t; e < need.size(); e += T) build_entry(*need[e].first, need[e].second); });
-    for (auto& x : th) x.join();
-    // one contiguous image of the nb tables, TAB_STRIDE apart, as the kernel sees them
-    std::vector<int32_t> imgv((size_t)nb * TAB_STRIDE + 4);
-    int32_t* img = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(imgv.data()) + 15) & ~(uintptr_t)15);
-    for (int i = 0; i < nb; ++i) std::memcpy(img + (size_t)i * TAB_STRIDE, tabs[(size_t)i]->entries.data(), TAB_STRIDE * 4);
-    for (size_t j = 0; j < n; ++j) {
-        g1p acc, o;
-        g1_fixed_eval_sum(acc, img, TAB_STRIDE, nb, sim_scalars{scalars32, n, j});
-        g1_norm1(o, acc);
-        if (addend96) {
-            g1p q;
-            parse96(q, addend96);
-            g1_add(o, q);
-            g1_norm1(o);
-        }
-        uint8_t* dst = out + 96 * j;
-        if (g1_is_inf(o)) { std::memset(dst, 0, 96); continue; }
+    static void settle(g1p& p) { g1_norm1(p); }
+    static bool is_inf(const g1p& p) { return g1_is_inf(p); }
+    static void encode(uint8_t* dst, const g1p& o) {
         fp zn, zi, ax, ay;
         fp_norm1(zn, o.z); fp_inv(zi, zn);
         g1_to_affine(ax, ay, o, zi);
@@ -126,7 +34,11 @@ int sim_g1_fixed_sum_batch(size_t n, int nb, const uint8_t* bases96, const uint8
         fp_to_raw48(rx, ax); fp_to_raw48(ry, ay);
         std::memcpy(dst, rx, 48); std::memcpy(dst + 48, ry, 48);
     }
-    return 0;
-}
+};
 
-}  // extern "C"
+}  // namespace
+
+// 96-byte points; see fixed_sum_sim::sim::batch
+extern "C" int sim_g1_fixed_sum_batch(size_t n, int nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* scalars32, uint8_t* out) {
+    return fixed_sum_sim::sim<sim_g1>::batch(n, nb, bases96, addend96, scalars32, out);
+}

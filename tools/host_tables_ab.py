@@ -7,9 +7,10 @@ library and a SHA-256 of the output.  A leg is marked OUTSIDE when B's median is
 
     python tools/host_tables_ab.py [--reps 5] [--out profiles/host_tables_refactor_ab.txt] <A.so | default> <B.so | default>
 
-Legs (sizes of tools/fixed_base_bench.py, g1_fixed_sum_bench.py, fixed_g2_bench.py, bbs04_bench.py --tiled and bench.py):
+Legs (sizes of tools/fixed_base_bench.py, g1_fixed_sum_bench.py, g2_fixed_sum_bench.py, fixed_g2_bench.py, bbs04_bench.py --tiled and bench.py):
   g1_mul_fixed 2^20 | g1_mul_fixed_sum 2^20, nb = 2 and 32 | pair_fixed_g2 2^16 | bbs04 verify, sign 2^18 (1024 distinct, tiled)
-  | BBS+ verify 2^18 (one message block) | BBS+ verify from the wire formats 2^18 (16 h_i, 12-byte messages)"""
+  | BBS+ verify 2^18 (one message block) | BBS+ verify from the wire formats 2^18 (16 h_i, 12-byte messages)
+  | g2_mul_fixed 2^18 | g2_mul_fixed_sum 2^18, nb = 2 and 32 | PS verify 2^18, 8 messages (the sizes of g2_fixed_sum_bench.py)"""
 import argparse
 import hashlib
 import os
@@ -91,6 +92,27 @@ def child():
     dsig, draw = d(s145.tobytes()), d(raw.tobytes())
     legs["bbs_plus_wire"] = (lambda: c.bbs_plus_verify_wire_dev(nb, NH, RAW, dwire[0].data_ptr(), dwire[1].data_ptr(), dwire[2].data_ptr(), dsig.data_ptr(),
                                                                 draw.data_ptr(), okw.data_ptr()), okw)
+    # the G2 legs at the sizes of tools/g2_fixed_sum_bench.py: 2^18 lanes; PS with 8 messages (1024 distinct signatures, tiled, every 7th with a wrong message)
+    R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+    q2, kq, o2 = d(G2), rand(32 * 32 * nb), out(192 * nb)
+    legs["g2_mul_fixed"] = (lambda: c.g2_mul_fixed_dev(nb, q2.data_ptr(), kq.data_ptr(), o2.data_ptr(), 192), o2)
+    bases2 = d(c.g2_mul_fixed(G2, red(57, 32).tobytes(), 192))
+    legs["g2_fixed_sum nb=2"] = (lambda: c.g2_mul_fixed_sum_dev(nb, 2, bases2.data_ptr(), kq.data_ptr(), o2.data_ptr(), None, 192), o2)
+    legs["g2_fixed_sum nb=32"] = (lambda: c.g2_mul_fixed_sum_dev(nb, 32, bases2.data_ptr(), kq.data_ptr(), o2.data_ptr(), None, 192), o2)
+    NM, DIST = 8, 1024
+    b32 = lambda k: (k % R).to_bytes(32, "big")
+    ints = lambda seed, m: [int.from_bytes(bytes(r), "big") % R for r in red(seed, m)]
+    px, py = ints(58, 1)[0], ints(59, NM)
+    X2, Y2 = c.g2_mul(G2, b32(px), 192), c.g2_mul(G2 * NM, b"".join(b32(v) for v in py), 192)
+    pm = [ints(60 + i, DIST) for i in range(NM)]
+    s1 = c.g1_mul(G1 * DIST, b"".join(b32(v or 1) for v in ints(70, DIST)), 96)
+    s2 = c.g1_mul(s1, b"".join(b32(px + sum(py[i] * pm[i][j] for i in range(NM))) for j in range(DIST)), 96)
+    for j in range(0, DIST, 7):
+        pm[j % NM][j] = (pm[j % NM][j] + 1) % R
+    tile = lambda b, w: np.tile(np.frombuffer(b, dtype=np.uint8).reshape(DIST, w), (nb // DIST, 1)).tobytes()
+    dps = [d(G2), d(X2), d(Y2), d(tile(s1, 96)), d(tile(s2, 96)), d(b"".join(tile(b"".join(b32(v) for v in col), 32) for col in pm))]
+    okp = out(nb)
+    legs["ps_verify nmsg=8"] = (lambda: c.ps_verify_dev(nb, NM, *[v.data_ptr() for v in dps], okp.data_ptr()), okp)
     torch.cuda.synchronize(dev)
     assert c.sync() == 0
     print("READY " + "|".join(legs), flush=True)
