@@ -5,7 +5,9 @@
 //   root, then the 11-isogeny in projective form) -> ECP_cfp (:1252-1273: multiplication by 1 - x).
 // This is NOT RFC 9380 hash_to_curve (one field element, no expand_message); it shares the RFC's constants.
 // The field sequence of the reference is followed step by step so that the degenerate inputs (u = 0, a zero
-// denominator: inverse of 0 is 0, 0 counts as a non-residue) give the same point on E' as the reference does.
+// denominator: inverse of 0 is 0, 0 counts as a non-residue) give what the reference gives: the pair (0, 0), which is not on E', whose
+// image (x, 0) is not on E, and which the doubling chain of the cofactor sends to infinity.  A u whose x lies in the isogeny's kernel
+// gives Z = xden yden = 0 with X = 0: infinity.  tests/h2c_zp_cases.py lists these inputs.
 #pragma once
 #include "codec.hpp"
 #include "g1.hpp"

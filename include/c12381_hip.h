@@ -93,7 +93,8 @@ int c12381_version(void);
 /* Fp (test / roofline hook) --------------------------------------------------------------- */
 /* op: 0 mul, 1 add, 2 sub, 3 sqr, 4 neg, 5 inv.  Replaces FP_nres + FP_mul/FP_add/FP_sub/FP_sqr/
  * FP_neg/FP_inv + FP_redc (fp_BLS12381.cpp:223,396,485,500,466,588,817,234).  b may be NULL for
- * unary ops. */
+ * unary ops.  Inputs are 48-byte big-endian values below 2^384, taken mod p; outputs are canonical;
+ * the inverse of 0 is 0. */
 int c12381_fp_op_batch(c12381_ctx* ctx, int op, size_t n, const uint8_t* a48, const uint8_t* b48, uint8_t* out48);
 int c12381_fp_op_batch_dev(c12381_ctx* ctx, int op, size_t n, const uint8_t* a48, const uint8_t* b48, uint8_t* out48);
 /* register-resident chain of `iters` Montgomery multiplications per element (x <- x*y), used to
@@ -387,7 +388,9 @@ int c12381_bbs_plus_verify_aggregate_dev(c12381_ctx* ctx, size_t n, size_t nmsg,
 int c12381_g1_from_hash_batch(c12381_ctx* ctx, size_t n, const uint8_t* digests64, uint8_t* out, int out_fmt);
 int c12381_g1_from_hash_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* digests64, uint8_t* out, int out_fmt);
 /* map_to_point(point1&, const fp&) alone (:113 -> 154-157 -> ECP_map2point): 48-byte field elements (taken mod p, as
- * residue/FP_nres does) -> 96-byte affine points of E, NOT yet multiplied by the cofactor. */
+ * residue/FP_nres does) -> 96-byte affine points of E, NOT yet multiplied by the cofactor.  For u = 0 and u^2 = -1/11 (a zero
+ * SSWU denominator) the result is the reference's pair (x, 0), which is NOT on the curve, and no error is reported; for the u that
+ * land on the kernel of the 11-isogeny it is infinity (96 zero bytes).  c12381_g1_from_hash_batch gives infinity for both kinds. */
 int c12381_g1_map_to_point_batch(c12381_ctx* ctx, size_t n, const uint8_t* u48, uint8_t* out96);
 /* multiply_cofactor(point1&) alone (:116 -> 159-162 -> ECP_cfp): P -> [1 - x]P = [0xd201000000010001]P as a plain
  * multiple.  (Not c12381_g1_mul_batch: `multiply` is PAIR_G1mul, whose GLV evaluation differs from the plain
