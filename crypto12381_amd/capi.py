@@ -18,6 +18,7 @@ E_ARG, E_HIP, E_POINT, E_NOMEM, E_INTERNAL = -1, -2, -3, -4, -5
 F_IN_SUBGROUP = 1
 F_MILLER_ONLY = 2
 F_COMPRESSED_IN = 4
+PS_MSG_HASH, PS_MSG_ENCODE = 0, 1
 
 
 class C12381Error(RuntimeError):
@@ -136,6 +137,14 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp]
         for name in ("c12381_bbs04_issue_batch", "c12381_bbs04_issue_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, vp]
+        for name in ("c12381_ps_verify_wire_batch", "c12381_ps_verify_wire_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, ci] + [vp] * 6
+        for name in ("c12381_ps_sign_batch", "c12381_ps_sign_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, ci] + [vp] * 5
+        for name in ("c12381_ps_randomize_batch", "c12381_ps_randomize_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, vp]
+        for name in ("c12381_ps_verify_aggregate", "c12381_ps_verify_aggregate_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 8
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -352,6 +361,61 @@ class Context:
 
     def ps_verify_dev(self, n, nmsg, g2, X2, Y2, s1, s2, m, ok):
         self._ck(self.lib.c12381_ps_verify_batch_dev(self.h, n, nmsg, _p(g2), _p(X2), _p(Y2), _p(s1), _p(s2), _p(m), _p(ok)))
+
+    def ps_verify_wire(self, g2_97: bytes, X2_97: bytes, Y2_97: bytes, sigs98: bytes, msgs: bytes, msg_len: int, mode: int, strict: bool = True) -> bytes:
+        """PS verify from the wire formats: key points (97 B each, Y2 holds nY of them), signatures (98 B each), messages of msg_len bytes each;
+        mode PS_MSG_HASH (nY = 1) or PS_MSG_ENCODE.  One byte per signature: 1 / 0, or 0xff where the reference would throw.  A key point that
+        does not decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise."""
+        n, nY = len(sigs98) // 98, len(Y2_97) // 97
+        out = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ps_verify_wire_batch(self.h, n, nY, msg_len, mode, _p(g2_97), _p(X2_97), _p(Y2_97) if nY else None, _p(sigs98),
+                                                      _p(msgs) if msg_len else None, _p(out)), allow_point=not strict)
+        return out.raw[:n]
+
+    def ps_verify_wire_dev(self, n, nY, msg_len, mode, g2_ptr, X2_ptr, Y2_ptr, sig_ptr, msg_ptr, ok_ptr):
+        self._ck(self.lib.c12381_ps_verify_wire_batch_dev(self.h, n, nY, msg_len, mode, _p(g2_ptr), _p(X2_ptr), _p(Y2_ptr), _p(sig_ptr), _p(msg_ptr),
+                                                          _p(ok_ptr)))
+
+    def ps_sign(self, x48: bytes, y48: bytes, msgs: bytes, t32: bytes, msg_len: int, mode: int, strict: bool = True) -> bytes:
+        """PS sign: secret key x (48 B) and y (nY x 48 B), messages of msg_len bytes each, the caller's randomness t (32 B per signature) ->
+        n x 98-byte signatures serialize(G^t, G^(t e)).  x or a used y_i >= r is C12381_E_ARG (every byte 0xff): raised when strict, returned
+        as bytes otherwise.  Not constant-time."""
+        n, nY = len(t32) // 32, len(y48) // 48
+        out = ctypes.create_string_buffer(max(98 * n, 1))
+        rc = self.lib.c12381_ps_sign_batch(self.h, n, nY, msg_len, mode, _p(x48), _p(y48) if nY else None, _p(msgs) if msg_len else None, _p(t32), _p(out))
+        if not (rc == E_ARG and not strict and out.raw[:98 * n] == b"\xff" * (98 * n) and n):
+            self._ck(rc)
+        return out.raw[:98 * n]
+
+    def ps_sign_dev(self, n, nY, msg_len, mode, x_ptr, y_ptr, msg_ptr, t_ptr, sig_ptr):
+        self._ck(self.lib.c12381_ps_sign_batch_dev(self.h, n, nY, msg_len, mode, _p(x_ptr), _p(y_ptr), _p(msg_ptr), _p(t_ptr), _p(sig_ptr)))
+
+    def ps_randomize(self, sigs98: bytes, r32: bytes):
+        """PS randomnize: (n x 98-byte signatures serialize(σ1^r, σ2^r), n status bytes: 0, or 0xff — and 98 bytes of 0xff — where σ1 or σ2
+        does not decode)"""
+        n = len(sigs98) // 98
+        out = ctypes.create_string_buffer(max(98 * n, 1))
+        st = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ps_randomize_batch(self.h, n, _p(sigs98), _p(r32), _p(out), _p(st)))
+        return out.raw[:98 * n], st.raw[:n]
+
+    def ps_randomize_dev(self, n, sig_ptr, r_ptr, out_ptr, status_ptr):
+        self._ck(self.lib.c12381_ps_randomize_batch_dev(self.h, n, _p(sig_ptr), _p(r_ptr), _p(out_ptr), _p(status_ptr)))
+
+    def ps_verify_aggregate(self, g2: bytes, X2: bytes, Y2: bytes, s1: bytes, s2: bytes, m: bytes, rho: bytes, strict: bool = True) -> bool:
+        """ONE verdict for a PS batch by a random linear combination (rho: n x 32 B caller-drawn scalars; inputs as ps_verify).  True: every
+        signature verifies (up to 2^-k for k-bit rho); False settles nothing — run ps_verify.  A signature point off the curve is
+        C12381_E_POINT: raised when strict, False otherwise."""
+        n = len(s1) // 96
+        nmsg = len(Y2) // 192
+        out = ctypes.c_int(0)
+        self._ck(self.lib.c12381_ps_verify_aggregate(self.h, n, nmsg, _p(g2), _p(X2), _p(Y2) if nmsg else None, _p(s1) if n else None,
+                                                     _p(s2) if n else None, _p(m) if nmsg and n else None, _p(rho) if n else None, ctypes.byref(out)),
+                 allow_point=not strict)
+        return out.value == 1
+
+    def ps_verify_aggregate_dev(self, n, nmsg, g2, X2, Y2, s1, s2, m, rho, all_ok):
+        self._ck(self.lib.c12381_ps_verify_aggregate_dev(self.h, n, nmsg, _p(g2), _p(X2), _p(Y2), _p(s1), _p(s2), _p(m), _p(rho), _p(all_ok)))
 
     def pair_eq(self, a1: bytes, a2: bytes, b1: bytes, b2: bytes, strict: bool = True) -> bytes:
         n = len(a1) // 96

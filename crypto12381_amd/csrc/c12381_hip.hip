@@ -73,8 +73,8 @@ struct c12381_ctx {
     // WS_STAGE holds the caller's buffers of a host form (stage / unstage).  No _dev path uses it and no _dev path calls a host form
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
-           WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
-           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_COUNT };
+           WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_FB_G1_4, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_PS, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;
@@ -175,7 +175,7 @@ int g1_finish(c12381_ctx* c, size_t n, const int32_t* proj, size_t stride, uint8
 }
 // Status words raised by the kernels since the last read: [0] an input point was not on the curve (its outputs are 0xff),
 // [1] a library-internal failure (a work-queue hand-over timed out: the affected outputs are 0xff as well), [2] a device-side argument
-// check failed (bbs04 open: a gmsk scalar >= r; its status bytes are 0xff).  Every host
+// check failed (bbs04 open: a gmsk scalar >= r, its status bytes are 0xff; PS sign: x or a used y_i >= r, its signatures are 0xff).  Every host
 // entry point ends here, so a word raised by an earlier asynchronous _dev call is reported by the next host call or
 // c12381_sync() on the same context, whichever comes first — _dev callers separate logical operations with c12381_sync().
 int read_flag(c12381_ctx* c) {
@@ -187,7 +187,7 @@ int read_flag(c12381_ctx* c) {
         return C12381_E_INTERNAL;
     }
     if (c->h_flag[2]) {
-        std::snprintf(c->err, sizeof c->err, "a secret scalar is not below r (bbs04 open: gmsk)");
+        std::snprintf(c->err, sizeof c->err, "a secret scalar is not below r (bbs04 open: gmsk; PS sign: x, y)");
         return C12381_E_ARG;
     }
     return c->h_flag[0] ? C12381_E_POINT : 0;
@@ -280,10 +280,12 @@ static_assert(FIXED_G2_MAX <= TABLE_ARRAY_MAX && G1_FIXED_SUM_MAX <= TABLE_ARRAY
 constexpr size_t table_dwords(size_t entries) { return (HDR_DWORDS + entries + 63) / 64 * 64; }
 constexpr size_t FB_G1_ENTRIES = (size_t)FB_G1_WINDOWS * FB_ENTRIES, FB_G2_ENTRIES = (size_t)FB_G2_WINDOWS * FB_ENTRIES;
 constexpr size_t FQ_TAB_DWORDS = table_dwords(FQ_TABLE_DWORDS);
-// G1 multiples: the four slots that g1_mul_fixed (0), the BBS+ columns (h0, h_1, h_2, h_3) and bbs04 (u, v, h, g1) share, and the nb tables
-// of the per-lane sums; G2 multiples: the slot of g2_mul_fixed, BBS+ and bbs04, and the nb tables of the G2 per-lane sums; line tables: one Q (pair_fixed_g2), BBS+'s w and g2 (rule 1), the k points of a product.  bbs04's
+// G1 multiples: the four slots that g1_mul_fixed (0), the BBS+ columns (h0, h_1, h_2, h_3) and bbs04 (u, v, h, g1) share, slot 4 (PS_GEN_SLOT)
+// for the default generator under PS sign alone, and the nb tables of the per-lane sums; G2 multiples: the slot of g2_mul_fixed, BBS+ and bbs04, and the nb tables of the G2 per-lane sums; line tables: one Q (pair_fixed_g2), BBS+'s w and g2 (rule 1), the k points of a product.  bbs04's
 // product (rule 0) and BBS+ have a workspace each, so neither evicts the other's tables.
 constexpr table_array fb_g1_slot(int i) { return {c12381_ctx::WS_FB_G1_0 + i, 1, table_dwords(FB_G1_ENTRIES * FB_G1_DWORDS), 0, 96}; }
+constexpr int PS_GEN_SLOT = 4;
+static_assert(c12381_ctx::WS_FB_G1_0 + PS_GEN_SLOT == c12381_ctx::WS_FB_G1_4, "the fixed-base slots are consecutive workspaces");
 constexpr table_array TA_FB_G1_SUM = {c12381_ctx::WS_FB_G1_SUM, G1_FIXED_SUM_MAX, table_dwords(FB_G1_ENTRIES * FB_G1_DWORDS), GATE_DWORDS, 96};
 constexpr table_array TA_FB_G2 = {c12381_ctx::WS_FB_G2, 1, table_dwords(FB_G2_ENTRIES * FB_G2_DWORDS), 0, 192};
 constexpr table_array TA_FB_G2_SUM = {c12381_ctx::WS_FB_G2_SUM, G2_FIXED_SUM_MAX, table_dwords(FB_G2_ENTRIES * FB_G2_DWORDS), GATE_DWORDS, 192};
@@ -544,7 +546,7 @@ static bool msm_use_buckets(size_t n) {
 
 extern "C" {
 
-int c12381_version(void) { return (0 << 16) | 5; }
+int c12381_version(void) { return (0 << 16) | 6; }
 
 int c12381_create(int device, c12381_ctx** out) {
     if (!out) return C12381_E_ARG;
@@ -1354,6 +1356,188 @@ int c12381_ps_verify_batch(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* 
     if ((rc = stage(c, s, {{g2_192, 192}, {X2_192, 192}, {Y2_192, 192 * nmsg}, {s1_96, 96 * n}, {s2_96, 96 * n}, {m_32, 32 * n * nmsg}}, {{ok, n}}))) return rc;
     if ((rc = c12381_ps_verify_batch_dev(c, n, nmsg, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.in[5], s.out[0]))) return rc;
     return unstage(c, s);
+}
+
+// ---------------------------------------------------------------- PS from the wire formats: verify, sign, randomnize; the aggregate verdict
+// What a caller of examples/ps/src/ps.cpp holds: 98-byte signatures serialize(σ1, σ2), 97-byte key points, 48-byte Zp secrets, raw message
+// bytes.  WS_PS is the workspace of all four entries (none calls another).  msg_mode -> number of message scalars (ps.hpp ps_msg_scalars):
+// C12381_PS_MSG_HASH one digest, nY = 1 required; C12381_PS_MSG_ENCODE ceil(msg_len / 31) units, more than nY is "message is too long".
+static_assert(C12381_PS_MSG_HASH == 0 && C12381_PS_MSG_ENCODE == 1, "ps.hpp PS_MSG_HASH / PS_MSG_ENCODE");
+static int ps_msg_units(int mode, size_t nY, size_t msg_len, size_t& units) {
+    if (mode == C12381_PS_MSG_HASH) { units = 1; return nY == 1 ? 0 : C12381_E_ARG; }
+    if (mode != C12381_PS_MSG_ENCODE) return C12381_E_ARG;
+    units = (msg_len + 30) / 31;
+    return units > nY ? C12381_E_ARG : 0;
+}
+// verify (ps.cpp:26-33, :84-99): ps_wire_prep_kernel and the 2 n square roots of the signatures on the context's stream, the 2 + units public
+// points on the side stream (three launches of the G2 decompression kernel straight from the caller's pointers), c12381_ps_verify_batch_dev
+// on the decoded columns, ps_wire_finish_kernel for the 0xff lanes.  Only the Y2 entries the message uses are decoded.
+static int ps_wire_args(size_t nY, size_t msg_len, int mode, const void* g2, const void* X2, const void* Y2, const void* sig, const void* msgs, const void* ok,
+                        size_t& units) {
+    if (!g2 || !X2 || !sig || !ok || (nY && !Y2) || (msg_len && !msgs)) return C12381_E_ARG;
+    return ps_msg_units(mode, nY, msg_len, units);
+}
+int c12381_ps_verify_wire_batch_dev(c12381_ctx* c, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* g2_97, const uint8_t* X2_97,
+                                    const uint8_t* Y2_97, const uint8_t* sig_98, const uint8_t* msgs, uint8_t* ok) {
+    size_t units = 0;
+    int rc = bind(c); if (rc || (rc = ps_wire_args(nY, msg_len, msg_mode, g2_97, X2_97, Y2_97, sig_98, msgs, ok, units))) return rc;
+    if (n == 0) return 0;
+    const size_t npub = 2 + units;
+    // slab: [pub G2 192s: g2, X2, Y2...][pub statuses] | per signature: s49 x 2, s96 x 2, m x units, status x 2
+    const size_t o_p192 = 0, o_stp = o_p192 + 192 * npub, o_s49 = round_up(o_stp + npub, 256), o_s96 = round_up(o_s49 + 98 * n, 256), o_m = o_s96 + 192 * n,
+                 o_st = round_up(o_m + 32 * n * units, 256), bytes = o_st + round_up(2 * n, 256);
+    if ((rc = ensure(c, c12381_ctx::WS_PS, bytes))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_PS];
+    if ((rc = fork_side(c))) return rc;                                     // the caller's inputs are ordered on the context's stream
+    hipLaunchKernelGGL(g2_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)1, g2_97, d + o_p192, d + o_stp, 0);
+    hipLaunchKernelGGL(g2_decompress_kernel, dim3(1), dim3(BLOCK), 0, c->side, (size_t)1, X2_97, d + o_p192 + 192, d + o_stp + 1, 0);
+    if (units) hipLaunchKernelGGL(g2_decompress_kernel, dim3(grid_for(units)), dim3(BLOCK), 0, c->side, units, Y2_97, d + o_p192 + 384, d + o_stp + 2, 0);
+    HIPCK(c, hipGetLastError());
+    hipLaunchKernelGGL(ps_wire_prep_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, msg_len, msg_mode, units, sig_98, msgs, d + o_s49, d + o_m);
+    hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(2 * n)), dim3(BLOCK), 0, c->stream, 2 * n, d + o_s49, d + o_s96, d + o_st, 0);
+    HIPCK(c, hipGetLastError());
+    if ((rc = join_side(c))) return rc;
+    if ((rc = c12381_ps_verify_batch_dev(c, n, units, d + o_p192, d + o_p192 + 192, d + o_p192 + 384, d + o_s96, d + o_s96 + 96 * n, d + o_m, ok))) return rc;
+    hipLaunchKernelGGL(ps_wire_finish_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, npub, d + o_st, d + o_stp, ok, c->d_flag);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+int c12381_ps_verify_wire_batch(c12381_ctx* c, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* g2_97, const uint8_t* X2_97,
+                                const uint8_t* Y2_97, const uint8_t* sig_98, const uint8_t* msgs, uint8_t* ok) {
+    size_t units = 0;
+    int rc = bind(c); if (rc || (rc = ps_wire_args(nY, msg_len, msg_mode, g2_97, X2_97, Y2_97, sig_98, msgs, ok, units))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{g2_97, 97}, {X2_97, 97}, {Y2_97, 97 * nY}, {sig_98, 98 * n}, {msg_len ? msgs : nullptr, msg_len * n}}, {{ok, n}}))) return rc;
+    if ((rc = c12381_ps_verify_wire_batch_dev(c, n, nY, msg_len, msg_mode, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.out[0]))) return rc;
+    return unstage(c, s);
+}
+// sign (ps.cpp:17-24, :68-82).  The reference's h = random-select_in<*G1> is the default generator raised to a random scalar t
+// (g1_point.hpp:355-369), so (σ1, σ2) = (G^t, (G^t)^e) = (G^t, G^(t e)), e = x + sum_i y_i m_i: G^t lies in G1, where multiply() is the plain
+// multiple.  ps_sign_prep_kernel writes t_j and t_j e_j interleaved; ONE fixed-base column of 2 n lanes on G (consts.hpp, written out by
+// ps_generator_kernel) with 49-byte output is the array of 98-byte signatures.  G's table has fixed-base slot PS_GEN_SLOT to itself: no
+// other entry builds a table there, and sign builds none elsewhere, so it neither evicts nor loses a table to c12381_g1_mul_fixed_batch,
+// BBS+ or bbs04.
+static int ps_sign_args(size_t nY, size_t msg_len, int mode, const void* x, const void* y, const void* msgs, const void* t, const void* sig, size_t& units) {
+    if (!x || !t || !sig || (nY && !y) || (msg_len && !msgs)) return C12381_E_ARG;
+    return ps_msg_units(mode, nY, msg_len, units);
+}
+int c12381_ps_sign_batch_dev(c12381_ctx* c, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* x_48, const uint8_t* y_48, const uint8_t* msgs,
+                             const uint8_t* t_32, uint8_t* sig_98) {
+    size_t units = 0;
+    int rc = bind(c); if (rc || (rc = ps_sign_args(nY, msg_len, msg_mode, x_48, y_48, msgs, t_32, sig_98, units))) return rc;
+    if (n == 0) return 0;
+    const size_t o_gen = 0, o_key = 128, o_sc = 256, stride = round_up(2 * n, 64);
+    if ((rc = ensure(c, c12381_ctx::WS_PS, o_sc + 64 * n))) return rc;
+    if ((rc = ensure(c, c12381_ctx::WS_PROJ, (size_t)3 * NL * stride * 4))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_PS];
+    hipLaunchKernelGGL(ps_generator_kernel, dim3(1), dim3(BLOCK), 0, c->stream, d + o_gen);
+    hipLaunchKernelGGL(ps_sign_prep_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, units, msg_len, msg_mode, x_48, y_48, msgs, t_32, d + o_sc, d + o_key,
+                       c->d_flag);
+    HIPCK(c, hipGetLastError());
+    const bool fb = fixed_base_enabled();
+    if (fb && (rc = g1_fixed_table(c, PS_GEN_SLOT, d + o_gen))) return rc;
+    if ((rc = g1_fixed_column(c, 2 * n, d + o_gen, PS_GEN_SLOT, d + o_sc, stride, 0, fb))) return rc;
+    if ((rc = g1_finish(c, 2 * n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, sig_98, 49))) return rc;
+    hipLaunchKernelGGL(ps_sign_finish_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (const uint8_t*)d + o_key, sig_98);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+int c12381_ps_sign_batch(c12381_ctx* c, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* x_48, const uint8_t* y_48, const uint8_t* msgs,
+                         const uint8_t* t_32, uint8_t* sig_98) {
+    size_t units = 0;
+    int rc = bind(c); if (rc || (rc = ps_sign_args(nY, msg_len, msg_mode, x_48, y_48, msgs, t_32, sig_98, units))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{x_48, 48}, {y_48, 48 * nY}, {msg_len ? msgs : nullptr, msg_len * n}, {t_32, 32 * n}}, {{sig_98, 98 * n}}))) return rc;
+    if ((rc = c12381_ps_sign_batch_dev(c, n, nY, msg_len, msg_mode, s.in[0], s.in[1], s.in[2], s.in[3], s.out[0]))) return rc;
+    return unstage(c, s);
+}
+// randomnize (ps.cpp:35-40): (σ1^r, σ2^r), `^` = multiply.  The 98-byte signatures ARE 2 n records of 49 bytes: decode them in place, one
+// generic column of 2 n lanes (r_j for both lanes of signature j), 49-byte output straight into out_98.  A record that does not decode
+// multiplies as infinity and raises nothing; ps_randomize_finish_kernel marks its signature.
+static int ps_randomize_args(const void* sig, const void* r, const void* out, const void* status) { return (!sig || !r || !out || !status) ? C12381_E_ARG : 0; }
+int c12381_ps_randomize_batch_dev(c12381_ctx* c, size_t n, const uint8_t* sig_98, const uint8_t* r_32, uint8_t* out_98, uint8_t* status) {
+    int rc = bind(c); if (rc || (rc = ps_randomize_args(sig_98, r_32, out_98, status))) return rc;
+    if (n == 0) return 0;
+    const size_t o_s96 = 0, o_sc = o_s96 + 192 * n, o_st = round_up(o_sc + 64 * n, 256), stride = round_up(2 * n, 64);
+    if ((rc = ensure(c, c12381_ctx::WS_PS, o_st + 2 * n))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_PS];
+    hipLaunchKernelGGL(g1_decompress_kernel, dim3(grid_for(2 * n)), dim3(BLOCK), 0, c->stream, 2 * n, sig_98, d + o_s96, d + o_st, 0);
+    hipLaunchKernelGGL(ps_randomize_prep_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, r_32, d + o_sc);
+    HIPCK(c, hipGetLastError());
+    if ((rc = g1_mul_to_proj(c, 2 * n, d + o_s96, d + o_sc, stride))) return rc;
+    if ((rc = g1_finish(c, 2 * n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, out_98, 49))) return rc;
+    hipLaunchKernelGGL(ps_randomize_finish_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, n, (const uint8_t*)d + o_st, out_98, status);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+int c12381_ps_randomize_batch(c12381_ctx* c, size_t n, const uint8_t* sig_98, const uint8_t* r_32, uint8_t* out_98, uint8_t* status) {
+    int rc = bind(c); if (rc || (rc = ps_randomize_args(sig_98, r_32, out_98, status))) return rc;
+    if (n == 0) return 0;
+    staging s;
+    if ((rc = stage(c, s, {{sig_98, 98 * n}, {r_32, 32 * n}}, {{out_98, 98 * n}, {status, n}}))) return rc;
+    if ((rc = c12381_ps_randomize_batch_dev(c, n, s.in[0], s.in[1], s.out[0], s.out[1]))) return rc;
+    return unstage(c, s);
+}
+// Aggregate verdict (optional, as BBS+'s; the reference verifies one signature per call, ps.cpp:84-99).  With caller-drawn rho_j,
+//   prod_j [ e(-σ2_j, g2) e(σ1_j, X2) prod_i e(m_ij σ1_j, Y2_i) ]^rho_j
+//     = e(-sum_j rho_j σ2_j, g2) * e(sum_j rho_j σ1_j, X2) * prod_i e(sum_j (rho_j m_ij) σ1_j, Y2_i):
+// nmsg scalar columns rho_j m_ij (zp_op_kernel), nmsg + 2 bucket products over the signature points, one negation (the prep kernel's
+// neg_mask) and ONE (nmsg + 2)-way product over the line tables of c12381_ps_verify_batch's fast route with n = 1.
+// Completeness: the factor of lane j is the rho_j-th power of the product that route tests, so a batch it accepts in every lane yields 1.
+// The bucket products go through multiply()'s GLV form; off the subgroup that adds cofactor points to a sum, and so does every cofactor
+// component of a σ itself: all of them pair to 1 against elements of G2, which is why the keys must be in G2 (the tables' rule 1: a key
+// outside G2 or at infinity leaves the gate shut and the verdict 0).  Soundness: a rejected lane has a factor f_j != 1 of prime order r, and
+// prod_j f_j^rho_j = 1 fixes rho_j mod r given the others: probability at most 2^-k over k-bit uniform rho_j (k <= 254).
+// all_ok = 0 settles nothing: an invalid signature, a key outside G2, or a point off the curve (the bucket products leave it out and raise
+// C12381_E_POINT; ps_aggregate_finish_kernel then clears the verdict) — run c12381_ps_verify_batch.
+static int ps_aggregate_args(size_t n, size_t nmsg, const void* g2, const void* X2, const void* Y2, const void* s1, const void* s2, const void* m, const void* rho,
+                             const void* all_ok) {
+    if (!g2 || !X2 || !all_ok || (nmsg && !Y2) || (n && (!s1 || !s2 || !rho || (nmsg && !m)))) return C12381_E_ARG;
+    return nmsg + 2 > (size_t)C12381_FIXED_G2_MAX ? C12381_E_ARG : 0;
+}
+int c12381_ps_verify_aggregate_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192, const uint8_t* s1_96,
+                                   const uint8_t* s2_96, const uint8_t* m_32, const uint8_t* rho_32, uint8_t* all_ok) {
+    int rc = bind(c); if (rc || (rc = ps_aggregate_args(n, nmsg, g2_192, X2_192, Y2_192, s1_96, s2_96, m_32, rho_32, all_ok))) return rc;
+    if (n == 0) { HIPCK(c, hipMemsetAsync(all_ok, 1, 1, c->stream)); return 0; }
+    HIPCK(c, hipMemsetAsync(all_ok, 0, 1, c->stream));
+    const int k = (int)nmsg + 2;
+    g2_cols q = {};
+    q.p[0] = g2_192; q.p[1] = X2_192;
+    for (size_t i = 0; i < nmsg; ++i) q.p[2 + i] = Y2_192 + 192 * i;
+    cached t;
+    if ((rc = lines_tables(c, TA_FQ_K, k, q, 1, t))) return rc;
+    const size_t o_sum = 0, o_col = round_up(96 * (size_t)k, 256);          // the k sums | one scalar column, rewritten per message (stream order)
+    if ((rc = ensure(c, c12381_ctx::WS_PS, o_col + 32 * n))) return rc;
+    uint8_t* d = (uint8_t*)c->ws[c12381_ctx::WS_PS];
+    g1_cols cols = {};
+    for (int j = 0; j < k; ++j) cols.p[j] = d + o_sum + 96 * j;
+    if ((rc = c12381_g1_msm_dev(c, n, s2_96, rho_32, d + o_sum, 96))) return rc;
+    if ((rc = c12381_g1_msm_dev(c, n, s1_96, rho_32, d + o_sum + 96, 96))) return rc;
+    for (size_t i = 0; i < nmsg; ++i) {
+        hipLaunchKernelGGL(zp_op_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, 0, n, rho_32, m_32 + 32 * n * i, d + o_col);
+        HIPCK(c, hipGetLastError());
+        if ((rc = c12381_g1_msm_dev(c, n, s1_96, d + o_col, d + o_sum + 96 * (2 + i), 96))) return rc;
+    }
+    if ((rc = launch_prodk(c, 1, k, cols, 1u, t, all_ok, true, false, t.gate + GATE_OTHER))) return rc;
+    hipLaunchKernelGGL(ps_aggregate_finish_kernel, dim3(1), dim3(BLOCK), 0, c->stream, all_ok, (const int*)c->d_flag);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+int c12381_ps_verify_aggregate(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192, const uint8_t* s1_96,
+                               const uint8_t* s2_96, const uint8_t* m_32, const uint8_t* rho_32, int* all_ok) {
+    int rc = bind(c); if (rc || (rc = ps_aggregate_args(n, nmsg, g2_192, X2_192, Y2_192, s1_96, s2_96, m_32, rho_32, all_ok))) return rc;
+    *all_ok = 0;
+    if (n == 0) { *all_ok = 1; return 0; }
+    uint8_t verdict = 0;
+    staging s;
+    if ((rc = stage(c, s, {{g2_192, 192}, {X2_192, 192}, {Y2_192, 192 * nmsg}, {s1_96, 96 * n}, {s2_96, 96 * n}, {m_32, 32 * n * nmsg}, {rho_32, 32 * n}},
+                    {{&verdict, 1}}))) return rc;
+    if ((rc = c12381_ps_verify_aggregate_dev(c, n, nmsg, s.in[0], s.in[1], s.in[2], s.in[3], s.in[4], s.in[5], s.in[6], s.out[0]))) return rc;
+    rc = unstage(c, s);                                          // synchronises the stream
+    *all_ok = (rc == 0 && verdict == 1) ? 1 : 0;
+    return rc;
 }
 
 static int pair_eq_args(const void* a1, const void* a2, const void* b1, const void* b2, const void* ok) { return (!a1 || !a2 || !b1 || !b2 || !ok) ? C12381_E_ARG : 0; }

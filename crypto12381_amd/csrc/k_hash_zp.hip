@@ -8,6 +8,7 @@
 #include "kernels_common.hpp"
 #include "fr.hpp"
 #include "h2c.hpp"
+#include "ps.hpp"
 
 using namespace c12381;
 
@@ -190,8 +191,7 @@ __global__ void __launch_bounds__(BLOCK, 2) zp_fold_cols_kernel(size_t n, const 
 // parse<G1>(pp.h) (49 bytes each), parse<G2>(pk) (97 bytes), encode_to<Zp>(message), parse<G1, Zp, Zp>(signature) (49 + 48 + 48).
 // bbs_wire_pub_kernel gathers the public points into the strides the decompression kernels read; bbs_wire_prep_kernel does the
 // per-signature part: A -> 49-byte array, x and r -> 32-byte scalars with parse<Zp>'s range check (48 big-endian bytes below r,
-// zp_number.hpp:226-236), message bytes -> encode_to<Zp> units (zp_number.hpp:1011-1037: 31-byte units behind a 0x01 byte, a short
-// last unit left-aligned), message-major.  status[j] = 0: the reference would throw for signature j.
+// zp_number.hpp:226-236), message bytes -> encode_to<Zp> units (ps.hpp encode_zp_unit), message-major.  status[j] = 0: the reference would throw for signature j.
 __global__ void __launch_bounds__(BLOCK, 2) bbs_wire_pub_kernel(size_t nblk, const uint8_t* g1_g2_h0, const uint8_t* h49, const uint8_t* pk97,
                                                              uint8_t* g1s49, uint8_t* g2s97) {
     const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -216,13 +216,7 @@ __global__ void __launch_bounds__(BLOCK, 2) bbs_wire_prep_kernel(size_t n, size_
     status[j] = (okx && okr) ? 1 : 0;
     const uint8_t* msg = msgs + msg_len * j;
 #pragma unroll 1
-    for (size_t i = 0; i < nblk; ++i) {
-        uint8_t* o = m32 + 32 * (i * n + j);
-        const size_t len = (i + 1) * 31 <= msg_len ? 31 : msg_len - i * 31;
-        o[0] = 1;
-#pragma unroll 1
-        for (size_t b = 0; b < 31; ++b) o[1 + b] = b < len ? msg[31 * i + b] : 0;
-    }
+    for (size_t i = 0; i < nblk; ++i) encode_zp_unit(m32 + 32 * (i * n + j), msg, msg_len, i);
 }
 // ok[j] <- 0xff where the reference would have thrown: malformed x / r, A not decodable, or public material not decodable
 __global__ void __launch_bounds__(BLOCK, 2) bbs_wire_finish_kernel(size_t n, size_t npub1, const uint8_t* st_sig, const uint8_t* st_a, const uint8_t* st_pub1,

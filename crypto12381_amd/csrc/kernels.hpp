@@ -8,6 +8,7 @@
 //   k_pairk.hip  K-way pairing products against fixed G2 points (line tables, prep, work-queue kernels)
 //   k_fixed.hip  fixed-base tables and their evaluation (public-parameter columns of BBS+)
 //   k_bbs04.hip  SHA3-512 (sha3.hpp) and the bbs04 group-signature stages around the scalar multiplications and the pairing product
+//   k_ps.hip     the PS signature stages (ps.hpp) around decompression, the fixed-base column, the bucket products and the pairing product
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -132,6 +133,15 @@ __global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_t3_kernel(size_t n, int32
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_combine_kernel(size_t n, int32_t* proj, size_t stride);
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_sign_finish_kernel(size_t n, size_t L, const uint8_t* tr, const uint8_t* gsk97, const uint8_t* rnd224, const uint8_t* t49, const uint8_t* st_a, const uint8_t* st_pub, uint8_t* sig435, uint8_t* status, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) bbs04_issue_pack_kernel(size_t n, const uint8_t* a49, const uint8_t* x32, const uint8_t* st_pub, uint8_t* gsk97, int* bad_flag);
+// k_ps.hip: PS signatures from the wire formats (msg_mode: ps.hpp PS_MSG_HASH / PS_MSG_ENCODE)
+__global__ void __launch_bounds__(BLOCK, 2) ps_wire_prep_kernel(size_t n, size_t msg_len, int mode, size_t nmsg, const uint8_t* sig98, const uint8_t* msgs, uint8_t* s49, uint8_t* m32);
+__global__ void __launch_bounds__(BLOCK, 2) ps_wire_finish_kernel(size_t n, size_t npub, const uint8_t* st_sig, const uint8_t* st_pub, uint8_t* ok, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ps_generator_kernel(uint8_t* out96);
+__global__ void __launch_bounds__(BLOCK, 2) ps_sign_prep_kernel(size_t n, size_t nused, size_t msg_len, int mode, const uint8_t* x48, const uint8_t* y48, const uint8_t* msgs, const uint8_t* t32, uint8_t* sc, uint8_t* key_ok, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ps_sign_finish_kernel(size_t n, const uint8_t* key_ok, uint8_t* sig98);
+__global__ void __launch_bounds__(BLOCK, 2) ps_randomize_prep_kernel(size_t n, const uint8_t* r32, uint8_t* sc);
+__global__ void __launch_bounds__(BLOCK, 2) ps_randomize_finish_kernel(size_t n, const uint8_t* st, uint8_t* out98, uint8_t* status);
+__global__ void __launch_bounds__(BLOCK, 2) ps_aggregate_finish_kernel(uint8_t* all_ok, const int* bad_flag);
 // k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
 constexpr int TABLE_ARRAY_MAX = 32;
 struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };

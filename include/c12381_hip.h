@@ -508,6 +508,76 @@ int c12381_bbs04_sign_batch_dev(c12381_ctx* ctx, size_t n, size_t msg_len, const
 int c12381_bbs04_issue_batch(c12381_ctx* ctx, size_t n, const uint8_t* gpk_390, const uint8_t* gamma_32, const uint8_t* x_32, uint8_t* gsk_97);
 int c12381_bbs04_issue_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* gpk_390, const uint8_t* gamma_32, const uint8_t* x_32, uint8_t* gsk_97);
 
+/* PS signatures (examples/ps/src/ps.cpp) from the WIRE formats ----------------------------------------------------------------------- */
+/* Wire layouts (examples/ps/include/ps.hpp):
+ *   signature   serialize(σ1, σ2)                                   49 + 49 = 98 bytes
+ *   public key  g2 97 B, X2 97 B, Y2 nY x 97 B, as three pointers    (the single-message PublicKey, 291 B, is these fields laid out contiguously:
+ *                                                                    pass pk, pk + 97, pk + 194)
+ *   secret key  x 48 B, y nY x 48 B, as two pointers                 (the single-message PrivateKey, 96 B: sk, sk + 48); parse<Zp>'s range check
+ *                                                                    (48 big-endian bytes below r, zp_number.hpp:226-236)
+ *   messages    msg_len raw bytes each, contiguous (msg_len = 0 allowed, msgs may then be NULL)
+ * Points decode as everywhere in this library (from_bytes with the header layer's "leading 0x00 = infinity", g1_point.hpp:87-111 /
+ * g2_point.hpp:73-77; x taken mod p; no subgroup check).
+ * msg_mode, shared by verify and sign:
+ *   C12381_PS_MSG_HASH    m = SHA3-512(message bytes) mod r: hash(message).to(Zp) of ps.cpp:20, :29 (hash_state feeds a span<const char> byte by
+ *                         byte with no length prefix, set.hpp:355-384).  Requires nY = 1.
+ *   C12381_PS_MSG_ENCODE  m = encode_to<Zp>(message) (zp_number.hpp:1011-1037): ceil(msg_len / 31) units (ps.cpp:70, :86).  More units than nY is
+ *                         the reference's "message is too long": C12381_E_ARG.  Only the first ceil(msg_len / 31) entries of Y2 / y take part:
+ *                         the others are neither decoded nor range-checked.
+ * Message reads: C12381_PS_MSG_HASH reads the messages as c12381_sha3_512_batch does (aligned 32-bit words: up to 3 bytes either side of a
+ * message are read, never used, never beyond the words that hold its bytes); C12381_PS_MSG_ENCODE reads them bytewise.  Signatures, keys and
+ * secrets are read bytewise: no alignment requirement on them.
+ * Argument errors (C12381_E_ARG) are checked before the empty-batch rule: a null pointer (Y2 / y may be NULL when nY = 0), an unknown
+ * msg_mode, C12381_PS_MSG_HASH with nY != 1, a message too long for nY.  n = 0 then returns C12381_OK and touches nothing. */
+#define C12381_PS_MSG_HASH 0
+#define C12381_PS_MSG_ENCODE 1
+/* c12381_ps_verify_wire_batch: ok[j] = verify(pk, msg_j, sig_j) (ps.cpp:26-33; :84-99): parse, hash or encode, and c12381_ps_verify_batch in one
+ * call.  ok[j] = 1 / 0 as verify returns; 0xff where the reference would throw on signature j (σ1 or σ2 does not decode: a bad tag, an x with
+ * no point on the curve).  A public point in use that does not decode makes every lane 0xff and returns C12381_E_POINT. */
+int c12381_ps_verify_wire_batch(c12381_ctx* ctx, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* g2_97, const uint8_t* X2_97,
+                                const uint8_t* Y2_97, const uint8_t* sig_98, const uint8_t* msgs, uint8_t* ok);
+int c12381_ps_verify_wire_batch_dev(c12381_ctx* ctx, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* g2_97, const uint8_t* X2_97,
+                                    const uint8_t* Y2_97, const uint8_t* sig_98, const uint8_t* msgs, uint8_t* ok);
+/* c12381_ps_sign_batch: sig[j] = sign(sk, msg_j) (ps.cpp:17-24; :68-82) with the caller's randomness: t_32[j] is the scalar the reference draws for
+ * h = random-select_in<*G1>, which is the default generator G raised to it (g1_point.hpp:355-369); any value below 2^256, reduced mod r first.
+ * Value: the bytes of serialize(G^t, (G^t)^e), e = x + sum_i y_i m_i mod r, as the reference evaluates them with multiply (G^t lies in G1, so
+ * (G^t)^e = G^(t e): two multiples of one fixed base per signature, from its table).  For t = 0 mod r both components, for e = 0 mod r the second
+ * one, are the point at infinity: 49 zero bytes.
+ * Status: there is no per-signature failure and no status array.  x or a used y_i >= r is where the reference's parse<Zp> throws: every output
+ * byte is then 0xff and the call returns C12381_E_ARG (the _dev form reports it at the next c12381_sync, as c12381_bbs04_open_batch does for
+ * gmsk); the context stays usable.
+ * The generator's table has a fixed-base slot of its own: the call never evicts the table c12381_g1_mul_fixed_batch (or BBS+, bbs04) holds.
+ * NOT constant-time: the table look-ups take data-dependent addresses.  The secrets the call is given (x, y, t) and values derived from them
+ * (t e) stay in the context's device workspaces (and, for the host form, its staging buffer) until a later call overwrites them or c12381_trim
+ * frees them; nothing is wiped. */
+int c12381_ps_sign_batch(c12381_ctx* ctx, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* x_48, const uint8_t* y_48, const uint8_t* msgs,
+                         const uint8_t* t_32, uint8_t* sig_98);
+int c12381_ps_sign_batch_dev(c12381_ctx* ctx, size_t n, size_t nY, size_t msg_len, int msg_mode, const uint8_t* x_48, const uint8_t* y_48, const uint8_t* msgs,
+                             const uint8_t* t_32, uint8_t* sig_98);
+/* c12381_ps_randomize_batch: out[j] = randomnize(sig_j) (ps.cpp:35-40) = serialize(σ1^r, σ2^r) with the caller's r_32[j] (any value below 2^256).
+ * `^` is multiply (PAIR_G1mul), exact for every curve point: each component is what c12381_g1_mul_batch returns on the decoded point.
+ * status[j] = 0, or 0xff with 98 bytes of 0xff where σ1 or σ2 does not decode; the other lanes are unaffected and the call returns C12381_OK.
+ * out_98 may be sig_98. */
+int c12381_ps_randomize_batch(c12381_ctx* ctx, size_t n, const uint8_t* sig_98, const uint8_t* r_32, uint8_t* out_98, uint8_t* status);
+int c12381_ps_randomize_batch_dev(c12381_ctx* ctx, size_t n, const uint8_t* sig_98, const uint8_t* r_32, uint8_t* out_98, uint8_t* status);
+/* Optional aggregate mode of c12381_ps_verify_batch (decoded inputs as there; the reference has no counterpart, it verifies one signature per
+ * call, ps.cpp:84-99), the random-linear-combination form BBS+ has above.  ONE verdict for the batch:
+ *   *all_ok = 1  iff g2, X2 and every Y2_i are elements of G2 other than infinity and
+ *                e(-sum_j rho_j σ2_j, g2) * e(sum_j rho_j σ1_j, X2) * prod_i e(sum_j (rho_j m[i*n + j]) σ1_j, Y2_i) == 1,
+ * evaluated as nmsg scalar columns mod r, nmsg + 2 bucket products over the signature points and ONE product of nmsg + 2 pairings.
+ * rho: n x 32 B scalars drawn by the caller, unpredictable to whoever produced the signatures (128 random bits each suffice).
+ * If c12381_ps_verify_batch accepts every lane, *all_ok = 1: the product is prod_j [e(σ2_j, g2)^-1 e(σ1_j, X2 + sum_i m_ij Y2_i)]^rho_j, and the
+ * cofactor components of points outside G1 — those of the σ and those the bucket products' GLV form adds off the subgroup — pair to 1
+ * against elements of G2.  If it rejects a lane, *all_ok = 1 with probability at most 2^-k over rho drawn uniformly from k-bit values
+ * (k <= 254).  *all_ok = 0 settles nothing (an invalid signature, or keys outside G2): run the per-signature entry then.
+ * nmsg + 2 <= C12381_FIXED_G2_MAX, otherwise C12381_E_ARG.  n = 0 gives 1.  A signature point off the curve gives *all_ok = 0 and C12381_E_POINT
+ * (the _dev form: the next c12381_sync; it also writes 0 when an earlier _dev call on the context left that status unread).  The _dev form
+ * writes one byte. */
+int c12381_ps_verify_aggregate(c12381_ctx* ctx, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                               const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, const uint8_t* rho_32, int* all_ok);
+int c12381_ps_verify_aggregate_dev(c12381_ctx* ctx, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                                   const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, const uint8_t* rho_32, uint8_t* all_ok);
+
 #ifdef __cplusplus
 }
 #endif
