@@ -55,6 +55,14 @@ class NH(int):
     pass
 
 
+class Count(int):
+    """a count or mode the entry bounds; `bad`: values it refuses"""
+    def __new__(cls, v, bad):
+        o = int.__new__(cls, v)
+        o.bad = bad
+        return o
+
+
 def _bad(rec):
     """the record of one point with its last byte changed: off the curve (test_invalid_points_poison_only_their_lane)"""
     return rec[:-1] + bytes([rec[-1] ^ 1])
@@ -89,6 +97,20 @@ def _entries(n, bad=True):
     if bad:
         sigs = sigs[:145] + C1[24] + sigs[145 + 49:]
     digests = scalars(320, 2 * n)
+    nb, nY = 2, 2
+    z48 = lambda sc32: b"".join(bytes(16) + sc32[32 * j:32 * j + 32] for j in range(len(sc32) // 32))     # 48-byte Zp fields below r
+    sc_k = scalars(330, n * k)
+    ps_pub = [In(Q[0]), In(Q[1]), In(Q[2] + Q[3])]                           # g2, X2, Y2_0, Y2_1
+    ps_m = scalars(331, n * nmsg)
+    ps_sigs = b"".join(C1[5 + j] + C1[9 + j] for j in range(n))             # 98-byte wire signatures
+    if bad:
+        ps_sigs = ps_sigs[:98] + C1[24] + ps_sigs[98 + 49:]
+    msgs = digests[:msg_len * n]
+    gpk = b"".join(C1[:4]) + C2[0] + C2[1]                                    # bbs04: g1, h, u, v | g2, w
+    sig435 = b"".join(C1[5 + j] + C1[6 + j] + C1[7 + j] + z48(scalars(340 + j, 6)) for j in range(n))
+    if bad:
+        sig435 = sig435[:435] + C1[24] + sig435[435 + 49:]
+    gsk = b"".join(C1[5 + j] + z48(scalars(350 + j, 1)) for j in range(n))
     E = [
         ("fp_op_batch", "fp_op_batch_dev", [Op(0), n, In(fp), In(fp[::-1]), Out(48 * n)], False),
         ("g1_mul_batch", "g1_mul_batch_dev", [n, In(p_n), In(sc), Out(49 * n), Fmt(49)], bad),
@@ -132,6 +154,32 @@ def _entries(n, bad=True):
         ("zp_op_batch", "zp_op_batch_dev", [Op(4), n, In(sc), OptIn(sc), Out(32 * n)], False),
         ("zp_from_hash_batch", None, [n, In(digests), Out(32 * n)], False),
         ("zp_inner_product", "zp_inner_product_dev", [n, In(sc), OptIn(sc[::-1]), Out(32)], False),
+        ("g1_mul_sum_batch", "g1_mul_sum_batch_dev", [n, Count(k, (0, 5)), In(prod_p), In(sc_k), Out(49 * n), Fmt(49), Flags(0)], bad),
+        ("pair_product_fixed_g2_batch", "pair_product_fixed_g2_batch_dev",
+         [n, Count(k, (0, 9)), In(prod_p), In(Q[0] + Q[1]), Out(576 * n), Flags(0)], bad),
+        ("ps_verify_batch", "ps_verify_batch_dev", [n, nmsg] + ps_pub + [In(p_n), In(good_p), In(ps_m), Out(n)], bad),
+        ("g1_mul_fixed_sum_batch", "g1_mul_fixed_sum_batch_dev",
+         [n, Count(nb, (0, 33)), In(P[0] + P[1]), OptIn(P[2]), In(scalars(332, n * nb)), Out(49 * n), Fmt(49)], False),
+        ("g2_mul_fixed_sum_batch", "g2_mul_fixed_sum_batch_dev",
+         [n, Count(nb, (0, 33)), In(Q[0] + Q[1]), OptIn(Q[2]), In(scalars(333, n * nb)), Out(97 * n), Fmt(97)], False),
+        ("sha3_512_batch", "sha3_512_batch_dev", [n, msg_len, In(msgs), Out(64 * n)], False),
+        # bad records of the wire entries below are reported through status bytes, not C12381_E_POINT
+        ("bbs04_verify_batch", "bbs04_verify_batch_dev", [n, msg_len, In(gpk), In(sig435), In(msgs), Out(n)], False),
+        ("bbs04_open_batch", "bbs04_open_batch_dev", [n, In(z48(scalars(341, 2))), In(sig435), Out(49 * n), Out(n)], False),
+        ("bbs04_sign_batch", "bbs04_sign_batch_dev",
+         [n, msg_len, In(gpk), In(gsk), In(msgs), In(scalars(342, 7 * n)), Out(435 * n), Out(n)], False),
+        ("bbs04_issue_batch", "bbs04_issue_batch_dev", [n, In(gpk), In(scalars(343, 1)), In(sc), Out(97 * n)], False),
+        ("ps_verify_wire_batch", "ps_verify_wire_batch_dev",
+         [n, Count(nY, (1,)), msg_len, Count(1, (2,)), In(C2[0]), In(C2[1]), In(C2[2] + C2[3]), In(ps_sigs), In(msgs), Out(n)], False),
+        ("ps_verify_wire_batch", "ps_verify_wire_batch_dev",
+         [n, Count(1, (2,)), msg_len, Count(0, (2,)), In(C2[0]), In(C2[1]), In(C2[2]), In(ps_sigs), In(msgs), Out(n)], False),
+        ("ps_sign_batch", "ps_sign_batch_dev",
+         [n, Count(nY, (1,)), msg_len, Count(1, (2,)), In(z48(scalars(344, 1))), In(z48(scalars(345, nY))), In(msgs), In(sc), Out(98 * n)], False),
+        ("ps_sign_batch", "ps_sign_batch_dev",
+         [n, Count(1, (2,)), msg_len, Count(0, (2,)), In(z48(scalars(344, 1))), In(z48(scalars(345, 1))), In(msgs), In(sc), Out(98 * n)], False),
+        ("ps_randomize_batch", "ps_randomize_batch_dev", [n, In(ps_sigs), In(sc), Out(98 * n), Out(n)], False),
+        ("ps_verify_aggregate", "ps_verify_aggregate_dev",
+         [n, nmsg] + ps_pub + [In(p_n), In(good_p), In(ps_m), In(scalars(334, n, 1 << 64)), Out(4)], bad),
     ]
     return E
 
@@ -193,12 +241,16 @@ def _arg_error_cases(args):
             yield "k MAX_PROD + 1", args[:i] + [K(4)] + args[i + 1:]
         elif isinstance(a, NH):
             yield "nblk > nh", args[:i] + [NH(1)] + args[i + 1:]
+        elif isinstance(a, Count):
+            for v in a.bad:
+                yield "arg %d = %d" % (i, v), args[:i] + [v] + args[i + 1:]
 
 
 _FORMS = [(host, dev) for host, dev, _, _ in _entries(3)]
 # host entries whose empty batch has a value: identity bytes of the output format, the zero scalar, a "valid" verdict
 _EMPTY_VALUES = {"g1_msm": bytes(49), "g1_msm_flags": bytes(96), "g1_sum": bytes(49), "g1_sum_of_products": bytes(96), "g2_msm": bytes(97),
-                 "zp_inner_product": bytes(32), "bbs_plus_verify_aggregate": (1).to_bytes(4, "little")}
+                 "zp_inner_product": bytes(32), "bbs_plus_verify_aggregate": (1).to_bytes(4, "little"),
+                 "ps_verify_aggregate": (1).to_bytes(4, "little")}
 
 
 @pytest.mark.parametrize("i", [i for i, (_, dev) in enumerate(_FORMS) if dev])
@@ -213,7 +265,7 @@ def test_host_form_equals_dev_form(ctx, i):
     assert rc_h == st, (host, rc_h, st)
     if bad:
         assert rc_h == E_POINT, host
-    if host == "bbs_plus_verify_aggregate":
+    if host in ("bbs_plus_verify_aggregate", "ps_verify_aggregate"):
         # the host form's verdict is an int that is 1 only when the call succeeded; the _dev form writes the verdict byte
         assert out_h[0] == (0 if bad else out_d[0][0]).to_bytes(4, "little")
         return

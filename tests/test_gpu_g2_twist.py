@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 TRI = 21                                    # pairings per wavefront (TRI_PER_WAVE)
 DUO = 32                                    # G2 multiplications per wavefront
-QUEUE_WAVES = 2048                          # c12381_hip.hip PAIR_QUEUE_WAVES: more wavefront groups than this take the work queue
+QUEUE_WAVES = 2048                          # api_pair.hip PAIR_QUEUE_WAVES: more wavefront groups than this take the work queue
 BIG = QUEUE_WAVES * TRI + 1                 # 2049 groups, the last one ragged: one lane alone
 
 

@@ -1,4 +1,4 @@
-"""The device-built tables that several entry points share (c12381_hip.hip cached_tables): the four G1 fixed-base slots (g1_mul_fixed, the
+"""The device-built tables that several entry points share (csrc/host.hpp cached_tables): the four G1 fixed-base slots (g1_mul_fixed, the
 BBS+ message columns, bbs04's u, v, h, g1), the two line tables of BBS+ with their gate, and the line tables of the k-way product that bbs04
 uses.  A table is rebuilt exactly when its point (or rule) changes, whoever asked for it last: calls of different owners are interleaved
 here, routes are flipped inside one slot, and every result is the port oracle's.  n = 65 (one wavefront and one lane), nmsg = 5 (two

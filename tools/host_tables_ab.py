@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of two builds of the C ABI on the entry points that go through the host's table cache (c12381_hip.hip cached_tables), in ONE GPU
+"""A/B of two builds of the C ABI on the entry points that go through the host's table cache (csrc/host.hpp cached_tables), in ONE GPU
 session.  One child process per library stays alive with its inputs resident on the device; the parent lets them run one call at a time,
 alternately (A B A B ...), so that clock drift of the box hits both alike.  Per leg: median / min / max wall ms of --reps calls per
 library and a SHA-256 of the output.  A leg is marked OUTSIDE when B's median is not within the min-max spread of A's own repeats
@@ -10,7 +10,12 @@ library and a SHA-256 of the output.  A leg is marked OUTSIDE when B's median is
 Legs (sizes of tools/fixed_base_bench.py, g1_fixed_sum_bench.py, g2_fixed_sum_bench.py, fixed_g2_bench.py, bbs04_bench.py --tiled and bench.py):
   g1_mul_fixed 2^20 | g1_mul_fixed_sum 2^20, nb = 2 and 32 | pair_fixed_g2 2^16 | bbs04 verify, sign 2^18 (1024 distinct, tiled)
   | BBS+ verify 2^18 (one message block) | BBS+ verify from the wire formats 2^18 (16 h_i, 12-byte messages)
-  | g2_mul_fixed 2^18 | g2_mul_fixed_sum 2^18, nb = 2 and 32 | PS verify 2^18, 8 messages (the sizes of g2_fixed_sum_bench.py)"""
+  | g2_mul_fixed 2^18 | g2_mul_fixed_sum 2^18, nb = 2 and 32 | PS verify 2^18, 8 messages (the sizes of g2_fixed_sum_bench.py)
+  | PS sign and PS verify from the wire formats 2^18 (the sizes of tools/ps_bench.py: 32-byte messages, C12381_PS_MSG_ENCODE, nY = 3)
+
+    python tools/host_tables_ab.py --trace [--legs a,b]      (under rocprofv3 --kernel-trace, one library per run)
+makes one call of each leg after a warm-up call, between two marker launches (fp_mulchain_kernel, which no leg uses, on 256 (i + 1) threads
+for leg i); tools/launch_compare.py cuts two such traces at the markers and compares the launches of every leg."""
 import argparse
 import hashlib
 import os
@@ -23,7 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def child():
+def child(trace=None):
+    """trace: None = serve the legs named on stdin; a list = one traced call of each of these legs (all when empty)"""
     import numpy as np
     import torch
     torch.cuda.init()
@@ -113,8 +119,34 @@ def child():
     dps = [d(G2), d(X2), d(Y2), d(tile(s1, 96)), d(tile(s2, 96)), d(b"".join(tile(b"".join(b32(v) for v in col), 32) for col in pm))]
     okp = out(nb)
     legs["ps_verify nmsg=8"] = (lambda: c.ps_verify_dev(nb, NM, *[v.data_ptr() for v in dps], okp.data_ptr()), okp)
+    # PS from the wire formats at the sizes of tools/ps_bench.py; the key is (g2, x g2, y_i g2) on the generator, so every signature verifies
+    from crypto12381_amd.capi import PS_MSG_ENCODE
+    NY, ML = 3, 32
+    kx, ky = ints(80, 1)[0], ints(81, NY)
+    pk97 = (c.g2_mul(G2, b32(1), 97), c.g2_mul(G2, b32(kx), 97), c.g2_mul(G2 * NY, b"".join(b32(v) for v in ky), 97))
+    dkey = [d(kx.to_bytes(48, "big")), d(b"".join(v.to_bytes(48, "big") for v in ky))] + [d(b) for b in pk97]
+    dmsg, dt32, sig_ps, ok_ps = rand(ML * nb), rand(32 * nb), out(98 * nb), out(nb)
+    legs["ps_sign"] = (lambda: c.ps_sign_dev(nb, NY, ML, PS_MSG_ENCODE, dkey[0].data_ptr(), dkey[1].data_ptr(), dmsg.data_ptr(), dt32.data_ptr(),
+                                             sig_ps.data_ptr()), sig_ps)
+    legs["ps_verify_wire"] = (lambda: c.ps_verify_wire_dev(nb, NY, ML, PS_MSG_ENCODE, dkey[2].data_ptr(), dkey[3].data_ptr(), dkey[4].data_ptr(),
+                                                           sig_ps.data_ptr(), dmsg.data_ptr(), ok_ps.data_ptr()), ok_ps)      # on ps_sign's signatures
     torch.cuda.synchronize(dev)
     assert c.sync() == 0
+    if trace is not None:
+        mark = out(48 * 256 * (len(legs) + 1))
+        for i, name in enumerate(legs):
+            if trace and name not in trace:
+                continue
+            fn, res = legs[name]
+            fn()
+            assert c.sync() == 0
+            marker = lambda: c.lib.c12381_fp_mulchain_dev(c.h, 256 * (i + 1), 0, mark.data_ptr(), mark.data_ptr(), mark.data_ptr())
+            assert marker() == 0
+            fn()
+            assert marker() == 0 and c.sync() == 0
+            print("TRACED %d %s %s" % (i, name.replace(" ", "_"), hashlib.sha256(res.cpu().numpy().tobytes()).hexdigest()[:16]), flush=True)
+        c.close()
+        return
     print("READY " + "|".join(legs), flush=True)
     for line in sys.stdin:
         name = line.strip()
@@ -134,10 +166,12 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--trace", action="store_true", help="one marked call of each leg after a warm-up call, for a kernel trace of this library")
+    ap.add_argument("--legs", default="", help="with --trace: comma-separated leg names (default: all)")
     ap.add_argument("libs", nargs="*")
     a = ap.parse_args()
-    if a.child:
-        child()
+    if a.child or a.trace:
+        child([x for x in a.legs.split(",") if x] if a.trace else None)
         return
     assert len(a.libs) == 2, "two libraries: A (the baseline) and B"
     kids = []
