@@ -58,13 +58,13 @@ static unsigned grid_tri(size_t n) {
     return (unsigned)((waves * 64 + BLOCK - 1) / BLOCK);
 }
 // Work-queue variant (k_pair3.hip): used when the batch is more than one machine-filling round of wavefronts, where the
-// plain grid would end in a mostly idle round.  C12381_PAIR_QUEUE=0 / 1 forces it off / on (A/B measurements, tests).
-constexpr size_t PAIR_QUEUE_WAVES = 2048;                  // resident wavefronts at 2 per SIMD
+// plain grid would end in a mostly idle round (PAIR_QUEUE_WAVES, host_layouts.hpp: the resident wavefronts at 2 per SIMD).
+// C12381_PAIR_QUEUE=0 / 1 forces it off / on (A/B measurements, tests).
 static int pair_queue_mode() {
     static const int v = [] { const char* e = tuning_env("C12381_PAIR_QUEUE"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     return v;
 }
-// bound of the hand-over spin in the queue kernels (k_pair3.hip queue_wait): 2^20 sleeps of 4096 cycles, about two
+// bound of the hand-over spin in the queue kernels (pair_queue.hpp queue_wait_rlx / queue_wait): 2^20 sleeps of 4096 cycles, about two
 // seconds — three orders of magnitude beyond a task.  C12381_PAIR_SPIN_LIMIT overrides it; a negative value makes every
 // wait fail (tests of the poison path).
 static int pair_spin_limit() {
@@ -105,45 +105,35 @@ static bool pair_use_queue(size_t n) {
     if (m >= 0) return m == 1;
     return (n + TRI_PER_WAVE - 1) / TRI_PER_WAVE > PAIR_QUEUE_WAVES;
 }
-// the kernels' rule for how many groups bypass the queue (k_pair3.hip queue_direct_groups), mirrored for the slab size
-static size_t queue_direct_groups_host(size_t ngroups, size_t nwaves) {
-    if (ngroups <= nwaves) return 0;
-    size_t queued = ngroups / 3;
-    if (queued < nwaves / 2) queued = nwaves / 2;
-    if (queued > 2 * nwaves) queued = 2 * nwaves;
-    if (g_queue_groups_host > 0) queued = (size_t)g_queue_groups_host < ngroups ? (size_t)g_queue_groups_host : ngroups;
-    return ngroups - queued;
-}
-// state slab: [flags: one word per group][task counter][whole-group counter][pad to 256 B][one block per QUEUED group] — whole
-// groups keep their state in registers and the LDS slot; 2^18 BBS+ verifications: 4096 blocks (344 MB) instead of 12484 (1.0 GB).
+// The queue of one launch: the slab (host_layouts.hpp pair_queue_layout — the split rule lives there and is evaluated here; the kernels take
+// ndirect as an argument, all but gt3_pow_queue_kernel, which keeps a transcription of the rule: k_pair3.hip) and, for the tagged form, this launch's epoch.
 // tagged (every kernel but the GT power): blocks of PAIR_QUEUE_STATE_BYTES in 8-byte tagged words, `epoch` = this launch's tag base.  The slab
 // then only ever holds tagged words or zeros (zeroed when it is allocated and when the 28-bit epoch wraps), so a word of an earlier launch —
 // at whatever offset that launch's group count put it — can never carry the tag of this one.  The GT power keeps the fenced 16-byte rows in a
 // slab of its own.
-static int pair_queue_setup(c12381_ctx* c, size_t n, uint4*& state, unsigned int*& flags, unsigned int*& counter, unsigned& blocks, unsigned int* epoch = nullptr) {
-    const size_t groups = (n + TRI_PER_WAVE - 1) / TRI_PER_WAVE;
-    const size_t head = round_up((groups + 2) * 4, 256);          // flags | task counter | whole-group counter
-    const size_t waves = groups < PAIR_QUEUE_WAVES ? groups : PAIR_QUEUE_WAVES;
-    blocks = (unsigned)((waves * 64 + BLOCK - 1) / BLOCK);
-    const size_t nwaves = (size_t)blocks * (BLOCK / 64);
-    const size_t nq = groups - queue_direct_groups_host(groups, nwaves);
-    const bool tagged = epoch != nullptr;
+static_assert(QUEUE_GROUP_ELEMS == TRI_PER_WAVE && QUEUE_WAVES_PER_BLOCK * 64 == BLOCK && QUEUE_BLOCK_TAGGED == PAIR_QUEUE_STATE_BYTES &&
+              QUEUE_BLOCK_FENCED == (size_t)PAIR_QUEUE_STATE_ROWS * 1024, "host_layouts.hpp: the queue's figures are those of kernels.hpp");
+struct pair_queue : pair_queue_slab {           // the layout's values as they are, plus the epoch; the kernels' pointer types
+    unsigned int epoch;
+    uint4* st() const { return (uint4*)state; }
+    unsigned int* fl() const { return (unsigned int*)flags; }
+    unsigned int* ct() const { return (unsigned int*)counter; }
+};
+static int pair_queue_setup(c12381_ctx* c, size_t n, pair_queue& pq, bool tagged = true) {
     const int slot = tagged ? c12381_ctx::WS_PAIR_ST : c12381_ctx::WS_POW_ST;
-    const size_t bytes = head + nq * (tagged ? PAIR_QUEUE_STATE_BYTES : (size_t)PAIR_QUEUE_STATE_ROWS * 1024);
-    int rc;
+    const size_t bytes = pair_queue_layout(nullptr, n, tagged, g_queue_groups_host).bytes;          // sizing pass, then the workspace (host_layouts.hpp)
     bool fresh = c->ws_bytes[slot] < bytes;
+    int rc;
     if ((rc = ensure(c, slot, bytes))) return rc;
+    static_cast<pair_queue_slab&>(pq) = pair_queue_layout(c->ws[slot], n, tagged, g_queue_groups_host);
+    pq.epoch = 0;
     if (tagged) {
         c->queue_epoch = (c->queue_epoch + 1u) & 0x0fffffffu;
         if (c->queue_epoch == 0) { c->queue_epoch = 1; fresh = true; }
         if (fresh) HIPCK(c, hipMemsetAsync(c->ws[slot], 0, c->ws_bytes[slot], c->stream));
-        *epoch = c->queue_epoch;
+        pq.epoch = c->queue_epoch;
     }
-    uint8_t* base = (uint8_t*)c->ws[slot];
-    flags = (unsigned int*)base;
-    counter = flags + groups;
-    state = (uint4*)(base + head);
-    HIPCK(c, hipMemsetAsync(base, 0, (groups + 2) * 4, c->stream));
+    HIPCK(c, hipMemsetAsync(pq.flags, 0, (size_t)(pq.counter - pq.flags) + 8, c->stream));       // flags and both counters
     return 0;
 }
 static int launch_pair(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt) {
@@ -151,10 +141,11 @@ static int launch_pair(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t
     if (pair_lanes() == 1) { LAUNCH(c, pair_kernel, n, n, g1, g2, gt, c->d_flag); return 0; }
 #endif
     if (pair_use_queue(n)) {
-        uint4* st; unsigned int *fl, *ct, ep; unsigned blocks; int rc;
-        if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
+        pair_queue pq; int rc;
+        if ((rc = pair_queue_setup(c, n, pq))) return rc;
         unsigned long long* const stp = pair_stamps(c, n);
-        LAUNCH_ON(c, pair3_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, g1, g2, gt, c->d_flag, st, fl, ct, pair_spin_limit(), ep, stp,
+        LAUNCH_ON(c, pair3_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, g1, g2, gt, c->d_flag, pq.st(), pq.fl(), pq.ct(), pq.ndirect,
+                  pair_spin_limit(), pq.epoch, stp,
                   stp ? stp + c->stamps_tasks * 4 : nullptr);
     } else LAUNCH_ON(c, pair3_kernel, dim3(grid_tri(n)), dim3(BLOCK), c->stream, n, g1, g2, gt, c->d_flag);
     return 0;
@@ -165,10 +156,11 @@ int c12381_host::launch_pair_eq(c12381_ctx* c, size_t n, const uint8_t* a1, cons
     if (pair_lanes() == 1) { LAUNCH(c, pair_eq_kernel, n, n, a1, a2, b1, b2, b2_stride, ok, c->d_flag); return 0; }
 #endif
     if (pair_use_queue(n)) {
-        uint4* st; unsigned int *fl, *ct, ep; unsigned blocks; int rc;
-        if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
-        LAUNCH_ON(c, pair3_eq_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, a1, a2, b1, b2, b2_stride, ok, c->d_flag, st, fl, ct, skip_if, pair_spin_limit(),
-                  ep);
+        pair_queue pq; int rc;
+        if ((rc = pair_queue_setup(c, n, pq))) return rc;
+        LAUNCH_ON(c, pair3_eq_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, a1, a2, b1, b2, b2_stride, ok, c->d_flag, pq.st(), pq.fl(), pq.ct(),
+                  skip_if, pq.ndirect, pair_spin_limit(),
+                  pq.epoch);
     } else LAUNCH_ON(c, pair3_eq_kernel, dim3(grid_tri(n)), dim3(BLOCK), c->stream, n, a1, a2, b1, b2, b2_stride, ok, c->d_flag, skip_if);
     return 0;
 }
@@ -180,11 +172,12 @@ int c12381_pair_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, const uint
     int rc = bind(c) ?: pair_args(g1, g2, gt, 0u);
     if (rc || n == 0) return rc;
     if (pair_lanes() != 1 && pair_use_queue(n)) {            // workspace and its reset stay outside the timed bracket
-        uint4* st; unsigned int *fl, *ct, ep; unsigned blocks;
-        if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
+        pair_queue pq;
+        if ((rc = pair_queue_setup(c, n, pq))) return rc;
         timed tm(c, 3);
         unsigned long long* const stp = pair_stamps(c, n);
-        LAUNCH_ON(c, pair3_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, g1, g2, gt, c->d_flag, st, fl, ct, pair_spin_limit(), ep, stp,
+        LAUNCH_ON(c, pair3_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, g1, g2, gt, c->d_flag, pq.st(), pq.fl(), pq.ct(), pq.ndirect,
+                  pair_spin_limit(), pq.epoch, stp,
                   stp ? stp + c->stamps_tasks * 4 : nullptr);
         return 0;
     }
@@ -240,11 +233,11 @@ int c12381_pair_fixed_g2_batch_dev(c12381_ctx* c, size_t n, const uint8_t* g1, c
     q.p[0] = g2_192;
     cached t;
     if ((rc = lines_tables(c, TA_FQ_P, 1, q, fq_rule(0), t))) return rc;
-    uint4* st; unsigned int *fl, *ct; unsigned blocks;
-    unsigned int ep;
-    if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
+    pair_queue pq;
+    if ((rc = pair_queue_setup(c, n, pq))) return rc;
     timed tm(c, 3);
-    LAUNCH_ON(c, pair3_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, g1, (const int32_t*)t.tabs, gt, c->d_flag, st, fl, ct, pair_spin_limit(), ep);
+    LAUNCH_ON(c, pair3_fixed_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, g1, (const int32_t*)t.tabs, gt, c->d_flag, pq.st(), pq.fl(), pq.ct(),
+              pq.ndirect, pair_spin_limit(), pq.epoch);
     return 0;
 }
 int c12381_pair_fixed_g2_batch(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8_t* g2_192, uint8_t* gt) {
@@ -264,23 +257,21 @@ int c12381_host::launch_prodk(c12381_ctx* c, size_t n, int k, const g1_cols& col
     int32_t* pts = (int32_t*)c->ws[c12381_ctx::WS_FQK_PTS];
     uint32_t* mask = (uint32_t*)((uint8_t*)pts + rec_bytes);
     LAUNCH(c, pairk_prep_kernel, n, n, k, cols, neg_mask, pts, mask, prep_skip);
-    uint4* st; unsigned int *fl, *ct, ep; unsigned blocks;
-    if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
-    const size_t groups = (n + TRI_PER_WAVE - 1) / TRI_PER_WAVE;
-    const size_t ndirect = queue_direct_groups_host(groups, (size_t)blocks * (BLOCK / 64));
+    pair_queue pq;
+    if ((rc = pair_queue_setup(c, n, pq))) return rc;
     if (eq)
-        LAUNCH_ON(c, pair3_prodk_fixed_eq_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines, t.stride, out,
-                  c->d_flag, st, fl, ct, gate, ndirect, pair_spin_limit(), ep);
+        LAUNCH_ON(c, pair3_prodk_fixed_eq_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines, t.stride, out,
+                  c->d_flag, pq.st(), pq.fl(), pq.ct(), gate, pq.ndirect, pair_spin_limit(), pq.epoch);
     else
-        LAUNCH_ON(c, pair3_prodk_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines, t.stride, out,
-                  c->d_flag, st, fl, ct, gate, ndirect, miller_only ? 1 : 0, pair_spin_limit(), ep);
+        LAUNCH_ON(c, pair3_prodk_fixed_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, k, (const int32_t*)pts, (const uint32_t*)mask, lines, t.stride, out,
+                  c->d_flag, pq.st(), pq.fl(), pq.ct(), gate, pq.ndirect, miller_only ? 1 : 0, pair_spin_limit(), pq.epoch);
     return 0;
 }
 int c12381_host::launch_prod_fixed(c12381_ctx* c, size_t n, const uint8_t* a_96, const uint8_t* b_96, const cached& lines, uint8_t* ok, const int32_t* gate) {
-    uint4* st; unsigned int *fl, *ct, ep; unsigned blocks; int rc;
-    if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
-    LAUNCH_ON(c, pair3_prod_fixed_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, a_96, b_96, (const int32_t*)lines.tabs + HDR_DWORDS,
-              (const int32_t*)lines.tabs + lines.stride + HDR_DWORDS, ok, c->d_flag, st, fl, ct, gate, pair_spin_limit(), ep);
+    pair_queue pq; int rc;
+    if ((rc = pair_queue_setup(c, n, pq))) return rc;
+    LAUNCH_ON(c, pair3_prod_fixed_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, a_96, b_96, (const int32_t*)lines.tabs + HDR_DWORDS,
+              (const int32_t*)lines.tabs + lines.stride + HDR_DWORDS, ok, c->d_flag, pq.st(), pq.fl(), pq.ct(), gate, pq.ndirect, pair_spin_limit(), pq.epoch);
     return 0;
 }
 // gt[i] = prod_{j < k} e(g1s[j * n + i], g2s[j]): the k line tables are built with need_g2 = 0 (exact for every point of the twist, infinity
@@ -324,9 +315,10 @@ static int launch_miller(c12381_ctx* c, size_t n, const uint8_t* g1, const uint8
     if (pair_lanes() == 1) { LAUNCH(c, miller_kernel, n, n, g1, g2, out, c->d_flag); return 0; }
 #endif
     if (pair_use_queue(n)) {              // more than one machine round of wavefront tasks: quarter-loop tasks from the work queue
-        uint4* st; unsigned int *fl, *ct, ep; unsigned blocks; int rc;
-        if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
-        LAUNCH_ON(c, miller3_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, g1, g2, out, c->d_flag, st, fl, ct, pair_spin_limit(), ep, pair_wave_stats(c, n));
+        pair_queue pq; int rc;
+        if ((rc = pair_queue_setup(c, n, pq))) return rc;
+        LAUNCH_ON(c, miller3_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, g1, g2, out, c->d_flag, pq.st(), pq.fl(), pq.ct(), pq.ndirect,
+                  pair_spin_limit(), pq.epoch, pair_wave_stats(c, n));
     } else LAUNCH_ON(c, miller3_kernel, dim3(grid_tri(n)), dim3(BLOCK), c->stream, n, g1, g2, out, c->d_flag);
     return 0;
 }
@@ -335,21 +327,22 @@ static int launch_gt_op(c12381_ctx* c, int op, size_t n, const uint8_t* a, const
     if (pair_lanes() == 1) { LAUNCH(c, gt_op_kernel, n, op, n, a, b, out); return 0; }
 #endif
     if (op == 3 && pair_use_queue(n)) {   // final exponentiations alone, more than one machine round: its six steps as queue tasks
-        uint4* st; unsigned int *fl, *ct, ep; unsigned blocks; int rc;
-        if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks, &ep))) return rc;
-        LAUNCH_ON(c, fexp3_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, a, out, c->d_flag, st, fl, ct, pair_spin_limit(), ep, pair_wave_stats(c, n));
+        pair_queue pq; int rc;
+        if ((rc = pair_queue_setup(c, n, pq))) return rc;
+        LAUNCH_ON(c, fexp3_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, a, out, c->d_flag, pq.st(), pq.fl(), pq.ct(), pq.ndirect,
+                  pair_spin_limit(), pq.epoch, pair_wave_stats(c, n));
     } else if (op == 2 && pair_use_queue(n)) {
         // the power, more than one machine round: five tasks per queued group (k_pair3.hip gt3_pow_queue_kernel); one table per wavefront of the
         // grid and one per queued group (at most 2048 + 4096 tables of 224 KB)
-        uint4* st; unsigned int *fl, *ct; unsigned blocks; int rc;
-        if ((rc = pair_queue_setup(c, n, st, fl, ct, blocks))) return rc;
-        const size_t groups = (n + TRI_PER_WAVE - 1) / TRI_PER_WAVE, nwaves = (size_t)blocks * (BLOCK / 64);
-        const size_t tables = nwaves + (groups - queue_direct_groups_host(groups, nwaves));
+        pair_queue pq; int rc;
+        if ((rc = pair_queue_setup(c, n, pq, false))) return rc;
+        const size_t tables = pq.nwaves + pq.nq;
         // the rule queues at most 2 x the grid: 6144 tables = 1.4 GB, held until c12381_trim / c12381_destroy; a tuning override beyond that is refused
         if (tables > 3 * PAIR_QUEUE_WAVES) { std::snprintf(c->err, sizeof c->err, "GT power: %zu tables exceed the workspace budget (queued-groups override too large)", tables); return C12381_E_ARG; }
         if ((rc = ensure(c, c12381_ctx::WS_GT_POW, tables * GT_POW_TAB_BYTES_PER_WAVE))) return rc;
-        LAUNCH_ON(c, gt3_pow_queue_kernel, dim3(blocks), dim3(BLOCK), c->stream, n, a, b, out, c->d_flag, (uint4*)c->ws[c12381_ctx::WS_GT_POW], st, fl, ct,
-                  pair_spin_limit());
+        LAUNCH_ON(c, gt3_pow_queue_kernel, dim3(pq.blocks), dim3(BLOCK), c->stream, n, a, b, out, c->d_flag, (uint4*)c->ws[c12381_ctx::WS_GT_POW], pq.st(),
+                  pq.fl(), pq.ct(),
+                  pair_spin_limit());        // this kernel evaluates the split itself (k_pair3.hip gt_pow_direct_groups): the same rule, the same override
     } else if (op == 2) {
         // the power in one plain launch: at most PAIR_QUEUE_WAVES wavefronts get here (longer batches took the queue above), each with its table
         // of x^0 .. x^15 behind it (224 KB per wavefront).  Only an experiments run with the queue forced off can be longer: it runs the

@@ -399,7 +399,7 @@ int c12381_create(int device, c12381_ctx** out) {
         hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess) { c12381_destroy(c); return C12381_E_HIP; }
     if (hipMalloc((void**)&c->d_flag, FLAG_WORDS * sizeof(int)) != hipSuccess || hipHostMalloc((void**)&c->h_flag, FLAG_WORDS * sizeof(int)) != hipSuccess ||
         hipMemset(c->d_flag, 0, FLAG_WORDS * sizeof(int)) != hipSuccess) { c12381_destroy(c); return C12381_E_HIP; }
-    if (const char* e = tuning_env("C12381_QUEUE_GROUPS")) { g_queue_groups_host = std::atoi(e); set_queue_groups_override(g_queue_groups_host); }      // tuning runs only
+    if (const char* e = tuning_env("C12381_QUEUE_GROUPS")) { g_queue_groups_host = std::atoi(e); set_queue_groups_override(g_queue_groups_host); }      // tuning runs only; the device copy: gt3_pow_queue_kernel
     *out = c;
     return 0;
 }

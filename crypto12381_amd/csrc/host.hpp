@@ -41,10 +41,10 @@ struct c12381_ctx {
     // diagnostic (experiments builds, C12381_PAIR_STAMPS): per-task time stamps of the last queue pairing launch, on this context's device
     unsigned long long* stamps = nullptr;
     size_t stamps_tasks = 0;
-    // ... followed by 12 words per wavefront of the grid (k_pair3.hip queue_wave_stats) for the last queue launch of pairings, Miller loops or
+    // ... followed by 12 words per wavefront of the grid (pair_queue.hpp queue_wave_stats) for the last queue launch of pairings, Miller loops or
     // final exponentiations; c12381_sync() writes both regions to the file
     static constexpr size_t STAMP_WAVES = 4096;
-    // launch counter of the work-queue kernels whose state travels in tagged words (k_pair3.hip stw_store): 28 bits, never 0
+    // launch counter of the work-queue kernels whose state travels in tagged words (pair_queue.hpp stw_store): 28 bits, never 0
     uint32_t queue_epoch = 0;
 };
 
@@ -56,7 +56,7 @@ using namespace c12381;
 // one-lane pairing kernels nor the forced-failure hooks: a stray variable in a caller's environment cannot select another path.
 // tuning_env is getenv in an experiments build and null otherwise (c12381_hip.hip, one of the two host units that look at the define).
 const char* tuning_env(const char* name);
-extern int g_queue_groups_host;                 // experiments builds: C12381_QUEUE_GROUPS (c12381_hip.hip; the device copy is set alongside, k_pair3.hip)
+extern int g_queue_groups_host;                 // experiments builds: C12381_QUEUE_GROUPS (c12381_hip.hip): the override of the queue's split, api_pair.hip pair_queue_setup; a device copy for gt3_pow_queue_kernel alone
 extern const size_t MSM_MAX_TERMS;              // terms per bucket-method pass (c12381_hip.hip)
 bool fixed_base_enabled();                      // C12381_FIXED_BASE=0 switches the table-driven routes off (c12381_hip.hip)
 int pair_lanes();                               // 3; C12381_PAIR_LANES=1: the one-lane-per-pairing kernels (api_pair.hip)

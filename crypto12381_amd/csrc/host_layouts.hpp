@@ -120,4 +120,47 @@ inline bbs04_issue_slab bbs04_issue_layout(void* base, size_t m) {
     return s;
 }
 
+// ---------------------------------------------------------------- pairing work queue (WS_PAIR_ST; the GT power: WS_POW_ST)
+// The figures of the queue kernels (api_pair.hip asserts them against kernels.hpp): 21 pairings per wavefront group, 4 wavefronts per
+// workgroup, a grid that fills the machine at 2 wavefronts per SIMD, and a queued group's state block in the tagged / the fenced form.
+constexpr size_t QUEUE_GROUP_ELEMS = 21, QUEUE_WAVES_PER_BLOCK = 4, PAIR_QUEUE_WAVES = 2048;
+constexpr size_t QUEUE_BLOCK_TAGGED = (size_t)168 * 64 * 8, QUEUE_BLOCK_FENCED = (size_t)42 * 1024;
+// THE split of the hybrid schedule, evaluated here (the kernels take ndirect as an argument; gt3_pow_queue_kernel alone keeps a transcription,
+// k_pair3.hip gt_pow_direct_groups, which has to stay this text): how many of `ngroups`
+// groups the `nwaves` wavefronts of the grid run whole, ahead of the queue; the rest goes through the queue in tasks.
+// Groups left to the tenth-length queue tasks at the end of a launch.  Measured on MI355X (profiles/r02_ab_queued_groups.txt):
+// 2^16 pairings (3121 groups, 2048 resident wavefronts): 2048 queued 21.8 ms, 1024 queued 19.4 ms, 512 queued 20.1 ms;
+// 2^18 BBS+ verifications (12484 groups): 2048 queued 82.0 ms, 1024 queued 82.4 ms, 512 queued 88.9 ms, 256 queued 97.3 ms —
+// the more whole groups a wavefront runs, the further apart the wavefronts finish: a third of the groups, between half a
+// grid and two grids (re-measured with the normalised line tables: 12484 groups, 2048 queued 83.2 ms, 4096 80.5, 6144 80.4, all 82.1).
+// A batch that fits the grid is queued whole (the queue forced on for a small batch: tests of the queue path).
+// override_groups > 0 (tuning runs, C12381_QUEUE_GROUPS in an experiments build): that many groups go through the queue.
+inline size_t queue_direct_groups(size_t ngroups, size_t nwaves, int override_groups) {
+    if (ngroups <= nwaves) return 0;
+    size_t queued = ngroups / 3;
+    if (queued < nwaves / 2) queued = nwaves / 2;
+    if (queued > 2 * nwaves) queued = 2 * nwaves;
+    if (override_groups > 0) queued = (size_t)override_groups < ngroups ? (size_t)override_groups : ngroups;
+    return ngroups - queued;
+}
+// [flags: one word per group][task counter][whole-group counter][pad to 256 B][one state block per QUEUED group] — whole groups keep
+// their state in registers and the LDS slot; 2^18 BBS+ verifications: 4096 blocks (344 MB) instead of 12484 (1.0 GB).  `blocks`
+// workgroups = `nwaves` wavefronts are launched; groups [0, ndirect) run whole, queued group ndirect + j owns block j of `state`.
+struct pair_queue_slab { uint8_t *flags, *counter, *state; unsigned blocks; size_t nwaves, ndirect, nq, bytes; };
+inline pair_queue_slab pair_queue_layout(void* base, size_t n, bool tagged, int override_groups) {
+    const size_t groups = (n + QUEUE_GROUP_ELEMS - 1) / QUEUE_GROUP_ELEMS;
+    const size_t waves = groups < PAIR_QUEUE_WAVES ? groups : PAIR_QUEUE_WAVES;
+    carver f(base);
+    pair_queue_slab s;
+    s.flags = f.take((groups + 2) * 4);
+    s.counter = s.flags ? s.flags + groups * 4 : nullptr;
+    s.blocks = (unsigned)((waves + QUEUE_WAVES_PER_BLOCK - 1) / QUEUE_WAVES_PER_BLOCK);
+    s.nwaves = (size_t)s.blocks * QUEUE_WAVES_PER_BLOCK;
+    s.ndirect = queue_direct_groups(groups, s.nwaves, override_groups);
+    s.nq = groups - s.ndirect;
+    s.state = f.take(s.nq * (tagged ? QUEUE_BLOCK_TAGGED : QUEUE_BLOCK_FENCED));
+    s.bytes = f.bytes;
+    return s;
+}
+
 }  // namespace c12381_host

@@ -55,11 +55,7 @@ __global__ void __launch_bounds__(BLOCK, 2) pairk_prep_kernel(size_t n, int k, g
         fp x, y;
         bool inf, ok;
         g1_parse96(x, y, inf, ok, cols.p[c] + 96 * i);
-        if ((neg_mask >> c) & 1u) {
-            fp ny;
-            fp_neg(ny, y);
-            fp_norm1(y, ny);
-        }
+        if ((neg_mask >> c) & 1u) fp_negate(y);
         if (!ok) m |= 0x80000000u;
         if (!ok || inf) m |= 1u << c;
         fqk_store_pt(pts + ((size_t)c * n + i) * FQK_PT_DWORDS, x, y);
@@ -78,112 +74,68 @@ __global__ void __launch_bounds__(BLOCK, 2) g2_bcast_kernel(size_t n, const uint
 
 namespace {
 
-// output of one element: EQ = ok byte (1 / 0, 0xff for an invalid element), otherwise the GT value (poisoned when invalid).
-// f12t_is_one exchanges across the triple: every lane calls it.
-template <bool EQ>
-__device__ __forceinline__ void pairk_store(uint8_t* out, size_t e, const fp4& F, bool valid, bool active, int* bad_flag, const tri& t) {
-    if (EQ) {
-        const bool one = f12t_is_one(F, t);
-        if (active && t.role == 0) {
-            if (!valid) *bad_flag = 1;
-            out[e] = valid ? (one ? 1 : 0) : 0xff;
-        }
-    } else if (active) {
-        if (!valid) { *bad_flag = 1; gt_poison(out + 576 * e, t.role); }
-        else gt_store_coeff(out + 576 * e, F, t.role);
-    }
-}
-
-// The work queue of pair3_fixed_queue_body (k_pair3.hip) over K tables: wavefronts first claim whole groups of 21 elements (counter[1])
-// up to `ndirect` (the host's queue_direct_groups rule), the rest goes through the queue in tasks — MILLER_TASKS_PER_GROUP quarters of the
-// loop, then the six steps of the final exponentiation (none with miller_only) — whose state travels in tagged words; a timed-out
-// hand-over poisons the group.  table_ok = false: every output is poisoned (a G2 point off the twist).
+// The work queue of pair_queue.hpp over K tables (the form of pair3_fixed_queue_body, k_pair3.hip): MILLER_TASKS_PER_GROUP quarters of the
+// loop, carrying only F, then the six steps of the final exponentiation (none with miller_only: the last Miller task ends the group).
+// table_ok = false: every output is poisoned (a G2 point off the twist).
 template <bool EQ>
 __device__ __forceinline__ void pairk_queue_body(size_t n, int k, const int32_t* pts, const uint32_t* mask, const int32_t* tabs, int tab_stride,
                                                  uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter,
                                                  size_t ndirect, bool miller_only, int spin_limit, uint32_t epoch, bool table_ok, fp4& H) {
     uint8_t* const stw = reinterpret_cast<uint8_t*>(state);
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned trip = lane / 3u;
-    tri t;
-    t.role = lane == 63u ? 0 : (int)(lane - 3u * trip);
-    t.base = lane == 63u ? 63 : (int)(3u * trip);
+    const tri t = tri_of_lane(lane);
     const size_t ngroups = (n + TRI_PER_WAVE - 1) / TRI_PER_WAVE;
     const size_t col_stride = n * FQK_PT_DWORDS;
     constexpr unsigned int MILLER_TASKS = MILLER_TASKS_PER_GROUP;
     const unsigned int TASKS = miller_only ? MILLER_TASKS : MILLER_TASKS + 6;
-    for (;;) {
-        const unsigned int gc = atomicAdd(counter + 1, lane == 0 ? 1u : 0u);
-        const size_t g = (size_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)gc);
+    for (;;) {                                                 // whole groups first
+        const size_t g = queue_claim(counter + 1, lane);
         if (g >= ndirect) break;
-        const size_t e = g * TRI_PER_WAVE + (lane == 63u ? TRI_PER_WAVE - 1 : trip);
-        const bool active = lane < 63u && e < n;
-        const size_t i = e < n ? e : n - 1;
-        const uint32_t m = mask[i];
+        const queue_elem q = queue_elem_of(g, lane, n);
+        const uint32_t m = mask[q.i];
         const bool valid = table_ok && (m >> 31) == 0;
         { fp4 one; f12t_one(one, t); slot_store(H, one); }
-        miller3_rangek_fixed(H, pts + i * FQK_PT_DWORDS, col_stride, table_ok ? m : ~0u, k, tabs, tab_stride, 64, 1, t);
+        miller3_rangek_fixed(H, pts + q.i * FQK_PT_DWORDS, col_stride, table_ok ? m : ~0u, k, tabs, tab_stride, 64, 1, t);
         f12t_conj_h(H, t);
         fp4 F;
         slot_load(F, H);
         if (!miller_only) f12t_final_exp_ws(F, H, t);
-        pairk_store<EQ>(out, e, F, valid, active, bad_flag, t);
+        pair_out<EQ>(out, q.e, F, valid, q.active, bad_flag, t);
     }
     const size_t nq = ngroups - ndirect;
     const size_t ntasks = nq * TASKS;
     for (;;) {
-        const unsigned int claimed = atomicAdd(counter, lane == 0 ? 1u : 0u);
-        const unsigned int task = (unsigned int)__builtin_amdgcn_readfirstlane((int)claimed);
+        const unsigned int task = queue_claim(counter, lane);
         if ((size_t)task >= ntasks) break;
-        const unsigned int p = (unsigned int)(task / nq);
-        const size_t g = ndirect + task % nq;
-        const size_t e = g * TRI_PER_WAVE + (lane == 63u ? TRI_PER_WAVE - 1 : trip);
-        const bool active = lane < 63u && e < n;
-        const size_t i = e < n ? e : n - 1;
-        bool poisoned = queue_wait_rlx(flags, g, p, spin_limit);
-        uint8_t* st = wave_uniform(stw + (g - ndirect) * PAIR_QUEUE_STATE_BYTES);        // only the queued groups own a state block (pair_queue_setup)
-        const uint32_t tag_in = st_tag(epoch, p - 1u), tag_out = st_tag(epoch, p);
+        const queue_task tk = queue_task_of(task, nq, ndirect, stw, epoch);
+        const unsigned int p = tk.p;
+        const queue_elem q = queue_elem_of(tk.g, lane, n);
+        bool poisoned = queue_wait_rlx(flags, tk.g, p, spin_limit);
         uint32_t m = ~0u;
-        if (!poisoned && (p < MILLER_TASKS || p == TASKS - 1)) m = mask[i];
+        if (!poisoned && (p < MILLER_TASKS || p == TASKS - 1)) m = mask[q.i];
         const bool valid = table_ok && (m >> 31) == 0;
         if (!poisoned && p < MILLER_TASKS) {
             {
                 fp4 f;
-                if (p == 0) f12t_one(f, t); else poisoned = !stw_load<fp4, ST_DW_F>(f, st + STW_F * 1024, lane, tag_in, spin_limit);
+                if (p == 0) f12t_one(f, t); else poisoned = !stw_load<fp4, ST_DW_F>(f, tk.st + STW_F * 1024, lane, tk.tag_in, spin_limit);
                 slot_store(H, f);
             }
             if (!poisoned) {
                 const int hi = 64 - MILLER_ITERS_PER_TASK * (int)p, lo = hi - (MILLER_ITERS_PER_TASK - 1);
-                miller3_rangek_fixed(H, pts + i * FQK_PT_DWORDS, col_stride, table_ok ? m : ~0u, k, tabs, tab_stride, hi, lo, t);
+                miller3_rangek_fixed(H, pts + q.i * FQK_PT_DWORDS, col_stride, table_ok ? m : ~0u, k, tabs, tab_stride, hi, lo, t);
                 if (p == MILLER_TASKS - 1) f12t_conj_h(H, t);
                 fp4 f;
                 slot_load(f, H);
-                if (p == TASKS - 1) pairk_store<EQ>(out, e, f, valid, active, bad_flag, t);      // miller_only: the last Miller task ends the group
-                else stw_store<fp4, ST_DW_F>(st + STW_F * 1024, lane, f, tag_out);
+                if (p == TASKS - 1) pair_out<EQ>(out, q.e, f, valid, q.active, bad_flag, t);      // miller_only: the last Miller task ends the group
+                else stw_store<fp4, ST_DW_F>(tk.st + STW_F * 1024, lane, f, tk.tag_out);
             }
         } else if (!poisoned) {
-            const int step = (int)(p - MILLER_TASKS);
-            fp4 r, y1, aux;
-            bool got = stw_load<fp4, ST_DW_F>(r, st + STW_F * 1024, lane, tag_in, spin_limit);
-            if (step >= 1) got = stw_load<fp4, ST_DW_F>(y1, st + STW_Y1 * 1024, lane, st_tag(epoch, MILLER_TASKS), spin_limit) && got;       // written by step 0
-            if (step == 5) got = stw_load<fp4, ST_DW_F>(aux, st + STW_TC1 * 1024, lane, st_tag(epoch, MILLER_TASKS + 4u), spin_limit) && got;  // written by step 4
-            poisoned = !got;
-            if (!poisoned) {
-                f12t_final_exp_step(step, r, y1, aux, H, t);
-                if (step < 5) {
-                    stw_store<fp4, ST_DW_F>(st + STW_F * 1024, lane, r, tag_out);
-                    if (step == 0) stw_store<fp4, ST_DW_F>(st + STW_Y1 * 1024, lane, y1, tag_out);
-                    if (step == 4) stw_store<fp4, ST_DW_F>(st + STW_TC1 * 1024, lane, aux, tag_out);
-                } else {
-                    pairk_store<EQ>(out, e, r, valid, active, bad_flag, t);
-                }
-            }
+            fp4 r;
+            poisoned = queue_fexp_task(tk, MILLER_TASKS, nullptr, r, lane, epoch, spin_limit, H, t);
+            if (!poisoned && p == TASKS - 1) pair_out<EQ>(out, q.e, r, valid, q.active, bad_flag, t);
         }
-        if (poisoned && p == TASKS - 1 && active) {        // the group's state was never completed: 0xff outputs, C12381_E_INTERNAL
-            bad_flag[1] = 1;
-            if (EQ) { if (t.role == 0) out[e] = 0xff; } else gt_poison(out + 576 * e, t.role);
-        }
-        queue_publish_rlx(flags, g, p, poisoned, lane);
+        if (poisoned && p == TASKS - 1) pair_out_poisoned<EQ>(out, q.e, q.active, bad_flag, t);
+        queue_publish_rlx(flags, tk.g, p, poisoned, lane);
     }
 }
 

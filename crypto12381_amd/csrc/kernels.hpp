@@ -27,7 +27,7 @@ constexpr int HDR_REBUILD = 49;                  // set by fixed_cache_check_ker
 constexpr int HDR_MAGIC = 50;                    // the header has been written before
 constexpr int HDR_RULE = 51;                     // validity rule the flag was computed under (line tables)
 constexpr int HDR_DWORDS = 64;                   // table data starts here
-int set_queue_groups_override(int v);             // k_pair3.hip: tuning switch (C12381_QUEUE_GROUPS)
+int set_queue_groups_override(int v);             // k_pair3.hip: tuning switch (C12381_QUEUE_GROUPS), read by gt3_pow_queue_kernel alone
 constexpr int GATE_OTHER = 49;                   // (gate + GATE_OTHER)[HDR_VALID] = the complement of gate[HDR_VALID]
 
 // Waves per SIMD of the three scalar-multiplication kernels (register budget 512 / occupancy: 256, 168 or 128 VGPRs).  Three per SIMD were
@@ -85,12 +85,12 @@ __global__ void __launch_bounds__(BLOCK, 2) fp_raw_kernel(int op, size_t n, cons
 __global__ void __launch_bounds__(BLOCK, 2) pair3_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_prod_kernel(size_t n, int k, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, int* bad_flag, int miller_only);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_eq_kernel(size_t n, const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, size_t b2_stride, uint8_t* out, int* bad_flag, const int32_t* skip_if);
-__global__ void __launch_bounds__(BLOCK, 2) miller3_queue_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch, unsigned long long* wstats);
-__global__ void __launch_bounds__(BLOCK, 2) fexp3_queue_kernel(size_t n, const uint8_t* in576, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch, unsigned long long* wstats);
-__global__ void __launch_bounds__(BLOCK, 2) pair3_queue_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch, unsigned long long* stamps, unsigned long long* wstats);
-__global__ void __launch_bounds__(BLOCK, 2) pair3_eq_queue_kernel(size_t n, const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, size_t b2_stride, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* skip_if, int spin_limit, unsigned int epoch);
-__global__ void __launch_bounds__(BLOCK, 2) pair3_prod_fixed_queue_kernel(size_t n, const uint8_t* a96, const uint8_t* c96, const int32_t* tabw, const int32_t* tabg, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* run_if, int spin_limit, unsigned int epoch);
-__global__ void __launch_bounds__(BLOCK, 2) pair3_fixed_queue_kernel(size_t n, const uint8_t* g1_96, const int32_t* buf, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, int spin_limit, unsigned int epoch);
+__global__ void __launch_bounds__(BLOCK, 2) miller3_queue_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, size_t ndirect, int spin_limit, unsigned int epoch, unsigned long long* wstats);
+__global__ void __launch_bounds__(BLOCK, 2) fexp3_queue_kernel(size_t n, const uint8_t* in576, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, size_t ndirect, int spin_limit, unsigned int epoch, unsigned long long* wstats);
+__global__ void __launch_bounds__(BLOCK, 2) pair3_queue_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, size_t ndirect, int spin_limit, unsigned int epoch, unsigned long long* stamps, unsigned long long* wstats);
+__global__ void __launch_bounds__(BLOCK, 2) pair3_eq_queue_kernel(size_t n, const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, size_t b2_stride, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* skip_if, size_t ndirect, int spin_limit, unsigned int epoch);
+__global__ void __launch_bounds__(BLOCK, 2) pair3_prod_fixed_queue_kernel(size_t n, const uint8_t* a96, const uint8_t* c96, const int32_t* tabw, const int32_t* tabg, uint8_t* out, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, const int32_t* run_if, size_t ndirect, int spin_limit, unsigned int epoch);
+__global__ void __launch_bounds__(BLOCK, 2) pair3_fixed_queue_kernel(size_t n, const uint8_t* g1_96, const int32_t* buf, uint8_t* gt, int* bad_flag, uint4* state, unsigned int* flags, unsigned int* counter, size_t ndirect, int spin_limit, unsigned int epoch);
 // k_pairk.hip: K-way products of pairings against fixed G2 points (C12381_FIXED_G2_MAX = FIXED_G2_MAX); the point columns travel by value
 constexpr int FIXED_G2_MAX = 8;
 struct g1_cols { const uint8_t* p[FIXED_G2_MAX]; };
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(BLOCK, 2) gt3_pow_queue_kernel(size_t n, const
 constexpr size_t GT_POW_TAB_BYTES_PER_WAVE = (size_t)16 * 14 * 64 * 16;   // 16 entries x 14 rows (one Fp4 per lane) x 64 lanes x 16 bytes
 __global__ void __launch_bounds__(BLOCK, 2) gt3_is_unity_kernel(size_t n, const uint8_t* a, uint8_t* out);
 constexpr int PAIR_QUEUE_STATE_ROWS = 42;        // 16-byte rows x 64 lanes per group of 21 pairings (F, tc1, tc2, y1): the fenced form (GT power queue)
-constexpr size_t PAIR_QUEUE_STATE_BYTES = (size_t)168 * 64 * 8;   // a queued group's block: 168 32-bit words per lane, each in an 8-byte tagged word (k_pair3.hip stw_store)
+constexpr size_t PAIR_QUEUE_STATE_BYTES = (size_t)168 * 64 * 8;   // a queued group's block: 168 32-bit words per lane, each in an 8-byte tagged word (pair_queue.hpp stw_store)
 __global__ void __launch_bounds__(BLOCK, 2) g1_from_hash_kernel(size_t n, const uint8_t* in, int mode, int32_t* proj, size_t proj_stride, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) zp_op_kernel(int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 __global__ void __launch_bounds__(BLOCK, 2) zp_fold_cols_kernel(size_t n, const uint8_t* a, size_t a_col_stride, const uint8_t* r32, const uint8_t* m32, int first, size_t T, uint8_t* out);

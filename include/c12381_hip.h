@@ -76,7 +76,8 @@ int c12381_sync(c12381_ctx* ctx);
 int c12381_wait_event(c12381_ctx* ctx, void* hip_event);
 int c12381_record_event(c12381_ctx* ctx, void* hip_event);
 /* Device workspaces grow to the largest call a context has served and are kept for the next one (a 2^20 G1 batch: 2.95 GB of window tables;
- * a GT power of 2^16 elements: 1.4 GB of power tables; 2^18 BBS+ verifications: a 344 MB state slab).  c12381_trim waits for the context's
+ * a GT power of 2^16 elements: 1.4 GB of power tables; 2^18 BBS+ verifications: a 344 MB state slab of the pairing work queue, one per
+ * context, so a second streaming context doubles it).  c12381_trim waits for the context's
  * streams and frees all of them; cached fixed-base / line tables are rebuilt by the next call that needs them.  (The reference's seam never
  * allocates: src/miracl_core_interface.cpp works on caller-owned PODs.) */
 int c12381_trim(c12381_ctx* ctx);

@@ -37,7 +37,61 @@ static void check(const char* what, uint8_t* base, size_t bytes, size_t sized, s
     uint8_t* base = (uint8_t*)std::malloc(sized); \
     const slab s = layout(base, __VA_ARGS__)
 
+// today's rule for the groups that bypass the queue, transcribed literally: pair_queue_layout has to give these values
+static size_t rule_direct(size_t ngroups, size_t nwaves, int ov) {
+    if (ngroups <= nwaves) return 0;
+    size_t queued = ngroups / 3;
+    if (queued < nwaves / 2) queued = nwaves / 2;
+    if (queued > 2 * nwaves) queued = 2 * nwaves;
+    if (ov > 0) queued = (size_t)ov < ngroups ? (size_t)ov : ngroups;
+    return ngroups - queued;
+}
+// The queue slab of the pairing kernels for n elements: head of groups + 2 words (flags, task counter, whole-group counter), one state block per
+// QUEUED group (the kernels index block g - ndirect for g in [ndirect, groups)), the split equal to the transcription above.  Sizing only —
+// 2^18 verifications are 344 MB — except for the head, which is carved and written.
+static void check_queue(size_t n, bool tagged, int ov) {
+    auto die = [&](const char* why) { std::fprintf(stderr, "pair_queue n=%zu tagged=%d override=%d: %s\n", n, (int)tagged, ov, why); std::exit(1); };
+    const size_t groups = (n + 20) / 21, waves = groups < 2048 ? groups : 2048, blocks = (waves + 3) / 4, nwaves = blocks * 4;
+    const size_t block_bytes = tagged ? (size_t)168 * 64 * 8 : (size_t)42 * 1024;
+    const pair_queue_slab z = pair_queue_layout(nullptr, n, tagged, ov);
+    if (z.flags || z.counter || z.state) die("sizing pass hands out pointers");
+    if (z.blocks != blocks || z.nwaves != nwaves) die("grid");
+    if (z.ndirect + z.nq != groups) die("ndirect + nq != groups");
+    if (z.ndirect != rule_direct(groups, nwaves, ov)) die("ndirect differs from the rule");
+    const bool all_queued = groups <= nwaves || (ov > 0 && (size_t)ov >= groups);
+    if ((z.ndirect == 0) != all_queued) die("every group queued exactly when the batch fits the grid or the override covers it");
+    if (z.nq == 0) die("nq == 0");                               // the rule never queues nothing: half a grid at least, an override is > 0
+    const size_t head = (groups + 2) * 4;
+    std::vector<uint8_t> fake(1);                                // offsets only: the slab is not allocated
+    const pair_queue_slab s = pair_queue_layout(fake.data(), n, tagged, ov);
+    const size_t o_flags = (size_t)(s.flags - fake.data()), o_counter = (size_t)(s.counter - fake.data()), o_state = (size_t)(s.state - fake.data());
+    if (s.bytes != z.bytes || s.ndirect != z.ndirect || s.nq != z.nq) die("sizing pass differs");
+    if (o_flags != 0 || o_counter != groups * 4) die("head: flags, then the two counters");
+    if (o_state % 256 || o_state < head) die("state starts inside the head or unaligned");
+    for (size_t g = z.ndirect; g < groups; ++g) {               // every block a queued group indexes
+        const size_t lo = o_state + (g - z.ndirect) * block_bytes;
+        if (lo < o_state || lo + block_bytes > z.bytes) die("a queued group's block lies outside the slab");
+    }
+    uint8_t* hd = (uint8_t*)std::malloc(head);                   // what pair_queue_setup zeroes per launch: exactly the head
+    const pair_queue_slab h = pair_queue_layout(hd, n, tagged, ov);
+    std::memset(h.flags, 0, (size_t)(h.counter - h.flags) + 8);
+    std::free(hd);
+    ++g_checked;
+}
+
 int main() {
+    for (bool tagged : {true, false}) {                         // n = 0 (no entry launches it): no group, an empty head of the two counters
+        const pair_queue_slab z = pair_queue_layout(nullptr, 0, tagged, 0);
+        if (z.ndirect != 0 || z.nq != 0 || z.blocks != 0 || z.bytes != 256) { std::fprintf(stderr, "pair_queue n=0\n"); return 1; }
+    }
+    {                                                           // pairing work queue: group counts around every edge of the rule, each n with its neighbours
+        const size_t GROUPS[] = {1, 2047, 2048, 2049, 3121, 6144, 6145, 12484};
+        const int OVERRIDES[] = {0, 1, 1024, 20000};            // 20000: above every group count here
+        for (size_t gr : GROUPS)
+            for (size_t n : {gr * 21 - 1, gr * 21, gr * 21 + 1})
+                for (int ov : OVERRIDES)
+                    for (bool tagged : {true, false}) check_queue(n, tagged, ov);
+    }
     const size_t NS[] = {1, 3, 64, 65, 257}, LENS[] = {0, 1, 31, 32, 40}, SMALL[] = {0, 1, 2};
     const size_t FIXED_G2_MAX = 8;                              // C12381_FIXED_G2_MAX: k = nmsg + 2 of the PS aggregate goes up to it
     for (size_t n : NS) {

@@ -268,6 +268,21 @@ def test_work_queue_kernels_on_the_tiled_pattern(ctx, oracle_port, pts, pattern)
     assert _differs(ctx.pair_product_fixed_g2(P + B1, t13 + t23, 2), _tile(oracle_port.gt_op("mul", f13, f23), 576, BIG), 576) == []
 
 
+def test_split_and_miller_only_queue_kernels_on_the_tiled_pattern(ctx, oracle_port, pts, pattern):
+    """the same 2049 groups (1025 whole, 1024 through the queue, the last one a single lane) for the two queue kernels the test above does not
+    reach in this regime: the final exponentiation alone (six tasks per queued group, step 0 reads the input array) on the tiled Miller
+    values, and the K-way fixed product with F_MILLER_ONLY (the last Miller task ends the group); the oracle's values of the pattern, tiled"""
+    from crypto12381_amd.capi import F_MILLER_ONLY
+    p1, q2, labels, mil, gt = pattern
+    n = len(labels)
+    assert _differs(ctx.fexp(_tile(mil, 576, BIG)), _tile(oracle_port.fexp(mil), 576, BIG), 576, labels) == []
+    b1 = p1[96 * (2 * TRI + 2):] + p1[:96 * (2 * TRI + 2)]
+    t13, t23 = tw.enc192(pts["t13a"]), tw.enc192(pts["t23"])
+    m = oracle_port.gt_op("mul", oracle_port.miller(p1, t13 * n), oracle_port.miller(b1, t23 * n))
+    got = ctx.pair_product_fixed_g2(_tile(p1, 96, BIG) + _tile(b1, 96, BIG), t13 + t23, 2, F_MILLER_ONLY)
+    assert _differs(got, _tile(m, 576, BIG), 576) == []
+
+
 # ---------------------------------------------------------------- verifiers with a fixed G2 argument of order 13
 def test_ps_verify_with_an_order_13_key(ctx, oracle_port, pts):
     """ok[j] = [e(s1_j, X2 + sum m_ij Y2_i) == e(s2_j, g2)] with g2, X2 or Y2 of order 13: not in G2, so the generic route; verdicts

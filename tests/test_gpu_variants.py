@@ -41,6 +41,8 @@ g1s, g2s = cat(g['g1']), cat(g['g2'])
 for k in (0, 5, 7):                                          # table-driven Miller loop (normalised or raw line records) == generic pairing
     q = g2s[192 * k:192 * k + 192]
     assert c.pair_fixed_g2(g1s, q) == c.pair(g1s, q * (len(g1s) // 96))
+assert c.fexp(c.miller(g1s, g2s)) == cat(g['gt'])          # the split forms and the GT power: their queue kernels under C12381_PAIR_QUEUE=1
+assert c.gt_op('pow', cat(g['gt'])[:576 * 4], cat(g['gt_pow_exp'])) == cat(g['gt_pow'])
 g = golden('g1')
 pts, sc = cat(g['points']), cat(g['scalars'])
 assert c.g1_msm(pts, sc, 49).hex() == g['msm49']

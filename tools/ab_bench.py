@@ -4,7 +4,7 @@ wall time per call over a few repetitions, and a SHA-256 of every output so that
 The variants run in child processes (one library per process), interleaved round by round (A B A B ...) so that clock drift of the box
 hits all of them alike.
 
-    python tools/ab_bench.py [--legs g1,g1sum,g2,pair,miller,fexp,msm,bbs] [--reps 3] [--rounds 2] default crypto12381_amd/lib/exp/libX.so ...
+    python tools/ab_bench.py [--legs g1,g1sum,g2,pair,paireq,miller,fexp,pow,msm,bbs,ps] [--reps 3] [--rounds 2] default crypto12381_amd/lib/exp/libX.so ...
 
 `default` = the product library.  Prints one table; exit status 1 if any digest differs from the first variant's or any child failed
 (crash, time-out, no result line): the run stops at the first such child."""
@@ -19,7 +19,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ALL_LEGS = ["g1", "g1sum", "g2", "pair", "miller", "fexp", "msm", "bbs"]
+ALL_LEGS = ["g1", "g1sum", "g2", "pair", "paireq", "miller", "fexp", "pow", "msm", "bbs", "ps"]
 
 
 def child(lib, legs, reps):
@@ -72,7 +72,7 @@ def child(lib, legs, reps):
         dq, dk, o = d(q1k * (n // 1024)), d(sc(5, n)), torch.empty(192 * n, dtype=torch.uint8, device=dev)
         res["g2"] = (*timeit(lambda: c.g2_mul_dev(n, dq.data_ptr(), dk.data_ptr(), o.data_ptr(), 192)), digest(o))
         del dq, dk, o
-    if {"pair", "miller", "fexp"} & set(legs):
+    if {"pair", "paireq", "miller", "fexp", "pow"} & set(legs):
         n = 1 << 16
         # distinct (P_i, Q_j) combinations: P index i mod 1024, Q index (5 i + i div 1024) mod 1024
         qq = b"".join(q1k[192 * ((5 * i + i // 1024) % 1024):192 * ((5 * i + i // 1024) % 1024) + 192] for i in range(n))
@@ -80,6 +80,19 @@ def child(lib, legs, reps):
         gt, mil = torch.empty(576 * n, dtype=torch.uint8, device=dev), torch.empty(576 * n, dtype=torch.uint8, device=dev)
         if "pair" in legs:
             res["pair"] = (*timeit(lambda: c.pair_dev(n, dp.data_ptr(), dq.data_ptr(), gt.data_ptr())), digest(gt))
+        elif "pow" in legs:                  # the bases of the power, untimed
+            c.pair_dev(n, dp.data_ptr(), dq.data_ptr(), gt.data_ptr()); c.sync()
+        if "pow" in legs:                    # GT power of the pairing values (members of the cyclotomic subgroup: the windowed ladder)
+            de, po = d(sc(7, n)), torch.empty(576 * n, dtype=torch.uint8, device=dev)
+            res["pow"] = (*timeit(lambda: c.gt_op_dev("pow", n, gt.data_ptr(), de.data_ptr(), po.data_ptr())), digest(po))
+            del de, po
+        if "paireq" in legs:                 # e(P_i, Q_i) == e(P_(i+1), Q_i): lanes i = 1023 mod 1024 compare a pairing with itself
+            ok = torch.empty(n, dtype=torch.uint8, device=dev)
+            db = torch.roll(dp.view(n, 96), -1, 0).contiguous().view(-1)
+            db.view(n, 96)[1023::1024] = dp.view(n, 96)[1023::1024]
+            res["paireq"] = (*timeit(lambda: c.pair_eq_dev(n, dp.data_ptr(), dq.data_ptr(), db.data_ptr(), dq.data_ptr(), ok.data_ptr())), digest(ok))
+            assert int(ok.sum().item()) == n // 1024, "pair_eq verdicts wrong"
+            del db, ok
         if "miller" in legs or "fexp" in legs:
             res["miller"] = (*timeit(lambda: c.miller_dev(n, dp.data_ptr(), dq.data_ptr(), mil.data_ptr())), digest(mil))
         if "fexp" in legs:
@@ -112,6 +125,14 @@ def child(lib, legs, reps):
         res["bbs"] = (*timeit(lambda: c.bbs_plus_verify_dev(n, 1, dpub[0].data_ptr(), dpub[1].data_ptr(), dpub[2].data_ptr(), dpub[3].data_ptr(),
                                                             dpub[4].data_ptr(), dA.data_ptr(), dx.data_ptr(), dr.data_ptr(), dm.data_ptr(), ok.data_ptr())), digest(ok))
         assert int(ok.sum().item()) == n - len(range(7, n, 1009)), "BBS+ verdicts wrong"
+    if "ps" in legs:                         # PS verification, one message: arbitrary G1 records (verdicts 0 — no early exit, the full product runs)
+        n = 1 << 18
+        dk = [d(q1k[192 * j:192 * j + 192]) for j in (1, 2, 3)]
+        ds1, ds2, dm = d(p1k * (n // 1024)), d((p1k[96 * 5:] + p1k[:96 * 5]) * (n // 1024)), d(sc(8, n))
+        ok = torch.empty(n, dtype=torch.uint8, device=dev)
+        res["ps"] = (*timeit(lambda: c.ps_verify_dev(n, 1, dk[0].data_ptr(), dk[1].data_ptr(), dk[2].data_ptr(), ds1.data_ptr(), ds2.data_ptr(),
+                                                      dm.data_ptr(), ok.data_ptr())), digest(ok))
+        assert int(ok.max().item()) == 0 and int(ok.sum().item()) == 0, "PS verdicts wrong: no record here is a signature"
     c.close()
     print("ABJSON " + json.dumps(res), flush=True)
 

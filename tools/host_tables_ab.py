@@ -56,6 +56,14 @@ def child(trace=None):
     np_ = 1 << 16
     p16, q1, gt = d(c.g1_mul(G1 * 1024, sc(3, 1024), 96) * (np_ // 1024)), d(c.g2_mul(G2, sc(4, 1), 192)), out(576 * np_)
     legs["pair_fixed_g2"] = (lambda: c.pair_fixed_g2_dev(np_, p16.data_ptr(), q1.data_ptr(), gt.data_ptr()), gt)
+    # the work-queue entries with per-element G2 arguments, the split forms and the GT power (3121 groups: 2081 whole, 1040 queued)
+    q16 = d(c.g2_mul(G2 * 1024, sc(4, 1024), 192) * (np_ // 1024))
+    gtp, mil, gtf, gtw, e16, ok16 = out(576 * np_), out(576 * np_), out(576 * np_), out(576 * np_), rand(32 * np_), out(np_)
+    legs["pair"] = (lambda: c.pair_dev(np_, p16.data_ptr(), q16.data_ptr(), gtp.data_ptr()), gtp)
+    legs["pair_eq"] = (lambda: c.pair_eq_dev(np_, p16.data_ptr(), q16.data_ptr(), p16.data_ptr(), q16.data_ptr(), ok16.data_ptr()), ok16)
+    legs["miller"] = (lambda: c.miller_dev(np_, p16.data_ptr(), q16.data_ptr(), mil.data_ptr()), mil)
+    legs["fexp"] = (lambda: c.gt_op_dev("fexp", np_, mil.data_ptr(), None, gtf.data_ptr()), gtf)                # of the Miller values the leg before left
+    legs["gt_pow"] = (lambda: c.gt_op_dev("pow", np_, gtp.data_ptr(), e16.data_ptr(), gtw.data_ptr()), gtw)     # of the pairing values
 
     nb = 1 << 18
     gpk, gsk, msgs, rnd224, sig = make(c, 1024)

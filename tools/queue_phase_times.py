@@ -22,7 +22,8 @@ c.sync()
 a = np.fromfile(path, dtype=np.uint64).reshape(-1, 4)
 groups_all = (n + 20) // 21
 nwaves = 2048
-# the kernel's split (k_pair3.hip queue_direct_groups): whole groups first, the last third (between half a grid and a grid) queued
+# a transcription, for this diagnostic alone, of the host's split (host_layouts.hpp queue_direct_groups, the one rule the library uses):
+# whole groups first, the last third (between half a grid and two grids) queued
 queued = groups_all if groups_all <= nwaves else min(max(groups_all // 3, nwaves // 2), 2 * nwaves)
 if os.environ.get("C12381_QUEUE_GROUPS"):                # experiments build: the override the library reads
     queued = min(int(os.environ["C12381_QUEUE_GROUPS"]), groups_all)
