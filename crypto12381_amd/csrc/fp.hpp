@@ -281,6 +281,52 @@ C12381_HD void fp_sqr(fp& r, const fp& a) {
                     set_bounds(r, top > 268435456.0 ? top : 268435456.0, vb, "fp_sqr"); })
 }
 
+// r = 2 a^2 / R mod p: a square times two (the G = 2Y^2 = Y (2Y) of a Jacobian doubling) in fp_sqr's column scan, 105 + 196
+// multiply-adds against the 196 + 196 of fp_mul(a, 2a).  Column k of a (2a) is sum_(i<j) (2a_i) (2a_j) + (2a_(k/2)) a_(k/2) as integers, so
+// the Montgomery digits and the output limbs are those of fp_mul(r, a, fp_raw_dbl(a)) bit for bit (tests/test_host_sim_g1_loop_forms.py).
+// Both operands of a cross term are limbs of 2a — the raw limb multiple a doubling holds anyway (2Y, for Z3), never stored; 4a is not
+// formed.  Column sum 28 LBa^2, as fp_mul(a, 2a) declares.
+C12381_HD void fp_sqr2(fp& r, const fp& a) {
+    C12381_BOUNDS({ fp d;                              // 2a, the partner fp_mul(a, 2a) would be given
+                    for (int i = 0; i < NL; ++i) d.l[i] = 2 * a.l[i];
+                    d.lb = 2 * a.lb; d.vb = 2 * a.vb;
+                    check_mul_operands(a, d, "fp_sqr2"); })
+    C12381_COUNT(27, 1);
+    int32_t m[NL];
+    int32_t out[NL];
+    int32_t a2[NL];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) a2[i] = 2 * a.l[i];
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+#pragma unroll
+        for (int i = 0; 2 * i < k; ++i) { acc += (int64_t)a2[i] * a2[k - i]; }
+        if ((k & 1) == 0) { acc += (int64_t)a2[k / 2] * a.l[k / 2]; }
+#pragma unroll
+        for (int i = 0; i < k; ++i) { acc += (int64_t)m[i] * FP_P[k - i]; }
+        m[k] = (int32_t)(((uint32_t)acc * FP_N0) & LMASK);
+        acc += (int64_t)m[k] * FP_P[0];
+        acc >>= LB;
+    }
+#pragma unroll
+    for (int k = NL; k < 2 * NL - 1; ++k) {
+#pragma unroll
+        for (int i = k - NL + 1; 2 * i < k; ++i) { acc += (int64_t)a2[i] * a2[k - i]; }
+        if ((k & 1) == 0) { acc += (int64_t)a2[k / 2] * a.l[k / 2]; }
+#pragma unroll
+        for (int i = k - NL + 1; i < NL; ++i) { acc += (int64_t)m[i] * FP_P[k - i]; }
+        out[k - NL] = C12381_LIMB((int32_t)((uint32_t)acc & LMASK));
+        acc >>= LB;
+    }
+    out[NL - 1] = (int32_t)acc;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) r.l[i] = out[i];
+    C12381_BOUNDS({ double vb = 2 * a.vb * a.vb * P_OVER_R + 1.0;
+                    double top = vb * TOP_PER_P + 2.0;
+                    set_bounds(r, top > 268435456.0 ? top : 268435456.0, vb, "fp_sqr2"); })
+}
+
 // ------------------------------------------------------------------ lazy reduction: sums of products
 // One Montgomery reduction for a whole bilinear form  r = (sum_t +-A_t*B_t) / R mod p
 // (the reference's FP2_mul does the same trick with double-length BIGs, fp2_BLS12381.cpp:266-302).

@@ -97,13 +97,15 @@ struct g1j { fp x, y, z; };
 // multiplied again needs no reduction of its own.  With G = 2Y^2 = Y (2Y) — 2Y is there for Z3 — D/2 = X G is a plain product and
 // 8C = 2 G^2, whose square columns ride in the reduction of Y3 (fp_mul_msqr2; 8 B^2 itself would not fit the columns beside
 // E (D - X3)).  Same values: X3 = 9X^4 - 8XY^2, Y3 = 3X^2 (4XY^2 - X3) - 8Y^4, Z3 = 2YZ.  g1j_dblu keeps C: there 8C is an output.
+// G itself is a square times two and is scanned as one (fp_sqr2: 105 column products, not the 196 of Y (2Y); the same limbs): of the six
+// products three are squares' scans (A, G, E^2) and three general (Z3, D/2, E (D - X3)).
 C12381_HD void g1j_dbl(g1j& p) {
     fp a, g, d, e, x3, y3, z3, y2;
     const int32_t cm4 = fp_opaque_const(-4);
     fp_raw_dbl(y2, p.y);
     fp_mul(z3, y2, p.z);                                 // Z3 = 2YZ
     fp_sqr(a, p.x);                                      // A = X^2
-    fp_mul(g, p.y, y2);                                  // G = 2Y^2
+    fp_sqr2(g, p.y);                                     // G = 2Y^2, the limbs of Y (2Y) from a square's columns
     fp_mul(d, p.x, g);                                   // D/2 = 2XY^2
     fp_mul_small(e, a, 3);                               // E = 3A
     fp_sqr_inj(x3, e, [&](int i, int64_t& acc) { fp_inj(acc, d, i, cm4); }, C12381_BV(4 * d.vb), C12381_BV(4 * d.lb));   // X3 = E^2 - 2D
