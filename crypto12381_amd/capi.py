@@ -145,6 +145,10 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, vp, vp, vp, vp]
         for name in ("c12381_ps_verify_aggregate", "c12381_ps_verify_aggregate_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 8
+        for name in ("c12381_ac_bbs_verify_batch", "c12381_ac_bbs_verify_batch_dev"):      # include/c12381_ac.h
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz] + [vp] * 7
+        for name in ("c12381_ac_bbs_pres_batch", "c12381_ac_bbs_pres_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz] + [vp] * 9
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -643,6 +647,51 @@ class Context:
 
     def bbs04_issue_dev(self, n, gpk_ptr, gamma_ptr, x_ptr, gsk_ptr):
         self._ck(self.lib.c12381_bbs04_issue_batch_dev(self.h, n, _p(gpk_ptr), _p(gamma_ptr), _p(x_ptr), _p(gsk_ptr)))
+
+    @staticmethod
+    def _idx(idx):
+        """the disclosure set I as the host array of uint32_t the AC-bbs entries take"""
+        idx = list(idx)
+        return (ctypes.c_uint32 * max(len(idx), 1))(*idx), len(idx)
+
+    def ac_bbs_verify(self, pk243: bytes, Y49: bytes, idx, pres243: bytes, u48: bytes, attr48: bytes, msgs: bytes, msg_len: int,
+                      strict: bool = True) -> bytes:
+        """AC-bbs verify from the wire formats (include/c12381_ac.h): pk.fixed_part (243 B), pk.Y (49 B each), the disclosure set idx,
+        PresInfo.fixed_part (243 B each), PresInfo.u (nJ x 48 B each), the DISCLOSED attributes (nI x 48 B each, in the order of idx) and
+        messages of msg_len bytes each.  One byte per presentation: 1 / 0, or 0xff where the reference would throw.  A pk that does not
+        decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise."""
+        n, nattr = len(pres243) // 243, len(Y49) // 49
+        arr, nI = self._idx(idx)
+        out = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_bbs_verify_batch(self.h, n, nattr, nI, arr, msg_len, _p(pk243), _p(Y49), _p(pres243), _p(u48) if nattr > nI else None,
+                                                     _p(attr48) if nI else None, _p(msgs) if msg_len else None, _p(out)), allow_point=not strict)
+        return out.raw[:n]
+
+    def ac_bbs_verify_dev(self, n, nattr, idx, msg_len, pk_ptr, Y_ptr, pres_ptr, u_ptr, attr_ptr, msg_ptr, ok_ptr):
+        arr, nI = self._idx(idx)
+        self._ck(self.lib.c12381_ac_bbs_verify_batch_dev(self.h, n, nattr, nI, arr, msg_len, _p(pk_ptr), _p(Y_ptr), _p(pres_ptr), _p(u_ptr), _p(attr_ptr),
+                                                         _p(msg_ptr), _p(ok_ptr)))
+
+    def ac_bbs_pres(self, pk243: bytes, Y49: bytes, idx, attr48: bytes, sigs97: bytes, msgs: bytes, rnd: bytes, msg_len: int, strict: bool = True):
+        """AC-bbs pres from the wire formats: the holder's whole attribute spans (nattr x 48 B each), signatures serialize(A, w) (97 B each),
+        messages and the caller's randomness (r, alpha, beta, delta_0 ..: (3 + nJ) x 32 B per presentation) -> (n x 243-byte
+        PresInfo.fixed_part, n x nJ x 48-byte PresInfo.u, n status bytes: 0, or 0xff — and records of 0xff — where the reference would
+        throw).  A pk that does not decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise.  Not
+        constant-time."""
+        n, nattr = len(sigs97) // 97, len(Y49) // 49
+        arr, nI = self._idx(idx)
+        nJ = max(nattr - nI, 0)
+        pres = ctypes.create_string_buffer(max(243 * n, 1))
+        u = ctypes.create_string_buffer(max(48 * nJ * n, 1))
+        st = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_bbs_pres_batch(self.h, n, nattr, nI, arr, msg_len, _p(pk243), _p(Y49), _p(attr48), _p(sigs97),
+                                                   _p(msgs) if msg_len else None, _p(rnd), _p(pres), _p(u), _p(st)), allow_point=not strict)
+        return pres.raw[:243 * n], u.raw[:48 * nJ * n], st.raw[:n]
+
+    def ac_bbs_pres_dev(self, n, nattr, idx, msg_len, pk_ptr, Y_ptr, attr_ptr, sig_ptr, msg_ptr, rnd_ptr, pres_ptr, u_ptr, status_ptr):
+        arr, nI = self._idx(idx)
+        self._ck(self.lib.c12381_ac_bbs_pres_batch_dev(self.h, n, nattr, nI, arr, msg_len, _p(pk_ptr), _p(Y_ptr), _p(attr_ptr), _p(sig_ptr), _p(msg_ptr),
+                                                       _p(rnd_ptr), _p(pres_ptr), _p(u_ptr), _p(status_ptr)))
 
     # ---- device-pointer entry points (ints = device addresses, e.g. torch tensor.data_ptr())
     def bbs_plus_sign(self, g1, h0, h, gamma32, x, r, m) -> bytes:

@@ -151,7 +151,7 @@ int stage(c12381_ctx* c, staging& s, std::initializer_list<host_buf> ins, std::i
 }
 int unstage(c12381_ctx* c, const staging& s) {
     for (size_t i = 0; i < s.nout; ++i)
-        HIPCK(c, hipMemcpyAsync(const_cast<void*>(s.host_out[i].p), s.out[i], s.host_out[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        if (s.host_out[i].bytes) HIPCK(c, hipMemcpyAsync(const_cast<void*>(s.host_out[i].p), s.out[i], s.host_out[i].bytes, hipMemcpyDeviceToHost, c->stream));
     return read_flag(c);
 }
 // Projective tree sum of the n elements at `cur` (SoA with stride `stride`, `words` dwords per element: 3 NL for G1, 6 NL for G2) by the
@@ -1015,14 +1015,18 @@ template <class G>
 static int fixed_sum_args(size_t nb, const void* bases, const void* sc, const void* out, int fmt) {
     return (nb < 1 || nb > (size_t)G::SUM.count || !bases || !sc || !out || !G::fmt_ok(fmt)) ? C12381_E_ARG : 0;
 }
+// The sum over bases [first, first + nb) of a list of `total` bases whose tables ALL stay current at their positions (sc: the nb columns of the
+// range); the public entries are total = nb, first = 0.  A protocol with several sums over parts of one key (api_ac_bbs.hip) keeps every table
+// of the key cached this way.
 template <class G>
-static int fixed_sum_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases, const uint8_t* addend, const uint8_t* sc, uint8_t* out, int fmt) {
-    int rc = bind(c) ?: fixed_sum_args<G>(nb, bases, sc, out, fmt);
-    if (rc || n == 0) return rc;
+static int fixed_sum_range(c12381_ctx* c, size_t n, size_t total, size_t first, size_t nb, const uint8_t* bases, const uint8_t* addend, const uint8_t* sc,
+                           uint8_t* out, int fmt) {
+    int rc;
     const bool fb = fixed_base_enabled();
     cached t;
-    if ((rc = fixed_tables<G>(c, G::SUM, fb ? (int)nb : 0, bases, t))) return rc;               // without tables: the gate buffer alone
-    const int32_t *gate = t.gate, *tabs = t.tabs;
+    if ((rc = fixed_tables<G>(c, G::SUM, fb ? (int)total : 0, bases, t))) return rc;            // without tables: the gate buffer alone
+    bases += G::POINT_BYTES * first;
+    const int32_t *gate = t.gate, *tabs = t.tabs + first * (size_t)t.stride;
     const size_t half = round_up(n, 64), stride = 2 * half;       // proj[0, n): the sums; proj[half, half + n): the generic route's current column
     if ((rc = ensure(c, c12381_ctx::WS_PROJ, G::PROJ_DWORDS * stride * 4))) return rc;
     int32_t* proj = (int32_t*)c->ws[c12381_ctx::WS_PROJ];
@@ -1037,6 +1041,18 @@ static int fixed_sum_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* base
     }
     return G::finish(c, n, proj, stride, out, fmt);
 }
+template <class G>
+static int fixed_sum_dev(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases, const uint8_t* addend, const uint8_t* sc, uint8_t* out, int fmt) {
+    int rc = bind(c) ?: fixed_sum_args<G>(nb, bases, sc, out, fmt);
+    if (rc || n == 0) return rc;
+    return fixed_sum_range<G>(c, n, nb, 0, nb, bases, addend, sc, out, fmt);
+}
+namespace c12381_host __attribute__((visibility("hidden"))) {
+int g1_fixed_sum_range(c12381_ctx* c, size_t n, size_t total, size_t first, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc,
+                       uint8_t* out, int fmt) {
+    return fixed_sum_range<sum_g1>(c, n, total, first, nb, bases96, addend96, sc, out, fmt);
+}
+}  // namespace c12381_host
 template <class G>
 static int fixed_sum_host(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases, const uint8_t* addend, const uint8_t* sc, uint8_t* out, int fmt) {
     int rc = bind(c) ?: fixed_sum_args<G>(nb, bases, sc, out, fmt);

@@ -120,6 +120,41 @@ inline bbs04_issue_slab bbs04_issue_layout(void* base, size_t m) {
     return s;
 }
 
+// ---------------------------------------------------------------- AC-bbs (WS_AC_BBS): both slabs start behind the public block
+constexpr size_t AC_BBS_PUB_BYTES = 8192;
+// the public block: pk.Y gathered into base order (the disclosed attributes' Y in the caller's order, then the hidden ones ascending) as it
+// arrives and decoded, g and tilde_g, tilde_X decoded (straight from pk.fixed_part), and the 3 + nattr status bytes: g, tilde_g, tilde_X, Y ..
+struct ac_bbs_public {
+    uint8_t *y49, *g96, *y96, *g2, *st;  // 32 x 49 B; 96 B; 32 x 96 B; 2 x 192 B; 3 + 32 B
+    explicit ac_bbs_public(uint8_t* d) : y49(d), g96(d + 1792), y96(d + 2048), g2(d + 5120), st(d + 5632) {}
+};
+// verify, per presentation of a chunk: A_, B_, U as they arrive (columns) and decoded, their statuses, the re-encoded A_, B_, U, the terms K, A_, -B_
+// of the k = 3 product and its scalars s, t, c, the nattr fixed-base columns (a_I .., u_J ..), the parse status, the transcript, the product R, the
+// sum over Y_J, R + sum compressed, the pairing verdict: 1359 + 32 nattr + msg_len bytes
+struct ac_bbs_verify_slab { uint8_t *p49, *p96, *st_p, *e49, *q96, *sc3, *sca, *st, *tr, *r96, *s96, *r49, *okp; size_t bytes; };
+inline ac_bbs_verify_slab ac_bbs_verify_layout(void* base, size_t m, size_t nattr, size_t msg_len) {
+    carver f(base, AC_BBS_PUB_BYTES);
+    ac_bbs_verify_slab s;
+    s.p49 = f.take(3 * 49 * m); s.p96 = f.take(3 * 96 * m); s.st_p = f.take(3 * m); s.e49 = f.take(3 * 49 * m); s.q96 = f.take(3 * 96 * m);
+    s.sc3 = f.take(3 * 32 * m); s.sca = f.take(32 * nattr * m); s.st = f.take(m); s.tr = f.take((msg_len + 147) * m); s.r96 = f.take(96 * m);
+    s.s96 = f.take(96 * m); s.r49 = f.take(49 * m); s.okp = f.take(m);
+    s.bytes = f.bytes;
+    return s;
+}
+// pres, per presentation of a chunk: A as it arrives and decoded, its status and the parse status, the nattr attribute columns in base order, the
+// nJ columns delta_j, the scalars r, alpha, -w, beta (the columns of A^r and of the 2 m-lane k = 2 product), its points C, C_I, A_, A_, a sum
+// over Y_J, the products B_, U, the encoded A_, B_, U, c, the transcript: 1273 + 32 (nattr + nJ) + msg_len bytes
+struct ac_bbs_pres_slab { uint8_t *a49, *a96, *st_a, *st, *sca, *scd, *sc2, *q96, *t96, *o96, *e49, *c32, *tr; size_t bytes; };
+inline ac_bbs_pres_slab ac_bbs_pres_layout(void* base, size_t m, size_t nattr, size_t nJ, size_t msg_len) {
+    carver f(base, AC_BBS_PUB_BYTES);
+    ac_bbs_pres_slab s;
+    s.a49 = f.take(49 * m); s.a96 = f.take(96 * m); s.st_a = f.take(m); s.st = f.take(m); s.sca = f.take(32 * nattr * m); s.scd = f.take(32 * nJ * m);
+    s.sc2 = f.take(4 * 32 * m); s.q96 = f.take(4 * 96 * m); s.t96 = f.take(96 * m); s.o96 = f.take(2 * 96 * m); s.e49 = f.take(3 * 49 * m);
+    s.c32 = f.take(32 * m); s.tr = f.take((msg_len + 147) * m);
+    s.bytes = f.bytes;
+    return s;
+}
+
 // ---------------------------------------------------------------- pairing work queue (WS_PAIR_ST; the GT power: WS_POW_ST)
 // The figures of the queue kernels (api_pair.hip asserts them against kernels.hpp): 21 pairings per wavefront group, 4 wavefronts per
 // workgroup, a grid that fills the machine at 2 wavefronts per SIMD, and a queued group's state block in the tagged / the fenced form.

@@ -9,6 +9,7 @@
 //   k_fixed.hip  fixed-base tables and their evaluation (public-parameter columns of BBS+)
 //   k_bbs04.hip  SHA3-512 (sha3.hpp) and the bbs04 group-signature stages around the scalar multiplications and the pairing product
 //   k_ps.hip     the PS signature stages (ps.hpp) around decompression, the fixed-base column, the bucket products and the pairing product
+//   k_ac_bbs.hip the AC-bbs credential stages (ac_bbs.hpp) around decompression, the fixed-base sums, the k-way products and PS verification
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -142,6 +143,16 @@ __global__ void __launch_bounds__(BLOCK, 2) ps_sign_finish_kernel(size_t n, cons
 __global__ void __launch_bounds__(BLOCK, 2) ps_randomize_prep_kernel(size_t n, const uint8_t* r32, uint8_t* sc);
 __global__ void __launch_bounds__(BLOCK, 2) ps_randomize_finish_kernel(size_t n, const uint8_t* st, uint8_t* out98, uint8_t* status);
 __global__ void __launch_bounds__(BLOCK, 2) ps_aggregate_finish_kernel(uint8_t* all_ok, const int* bad_flag);
+// k_ac_bbs.hip: AC-bbs credential presentation and verification (ac_bbs.hpp; the base order travels by value)
+struct ac_bbs_order;
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_key_kernel(size_t nattr, ac_bbs_order ord, const uint8_t* y49, uint8_t* out49);
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_bcast96_kernel(size_t n, const uint8_t* src96, uint8_t* dst96);
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_verify_prep_kernel(size_t n, size_t nI, size_t nJ, const uint8_t* pres243, const uint8_t* u48, const uint8_t* attr48, uint8_t* p49, uint8_t* sc3, uint8_t* sca, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_encode_kernel(size_t n, const uint8_t* a96, const uint8_t* b96, const uint8_t* u96, uint8_t* e49, uint8_t* q96);
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_challenge_kernel(size_t n, size_t msg_len, const uint8_t* msgs, const uint8_t* e49, uint8_t* tr, uint8_t* c32);
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_verify_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* r49, const uint8_t* u49, const uint8_t* okp, uint8_t* ok, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_pres_prep_kernel(size_t n, size_t nattr, size_t nJ, ac_bbs_order ord, const uint8_t* attr48, const uint8_t* sig97, const uint8_t* rnd, uint8_t* a49, uint8_t* sca, uint8_t* scd, uint8_t* sc2, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) ac_bbs_pres_finish_kernel(size_t n, size_t nattr, size_t nJ, ac_bbs_order ord, const uint8_t* attr48, const uint8_t* sig97, const uint8_t* rnd, const uint8_t* e49, const uint8_t* c32, const uint8_t* st, const uint8_t* st_a, const uint8_t* st_pub, uint8_t* pres243, uint8_t* u48, uint8_t* status, int* bad_flag);
 // k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
 constexpr int TABLE_ARRAY_MAX = 32;
 struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };
