@@ -532,14 +532,16 @@ int c12381_fp_mulchain_dev(c12381_ctx* c, size_t n, int iters, const uint8_t* a,
 #ifdef C12381_EXPERIMENTS
 // experiments builds only (not declared in include/c12381_hip.h): the raw-limb test kernel of the Fp / Fp2 leaf (k_fp_raw.hip, fp_raw_ops.hpp).
 // Host buffers: in = n x arity x 14 limbs, k = n x 4 integers, out = n x outputs x 14 limbs; arity / outputs are the op's (C12381_E_ARG otherwise).
+// The op decides the kernel: the whole-element codes run one lane per element, the FH2_* codes two (fp2h_raw_kernel).
 extern "C" int c12381_exp_fp_raw_batch(c12381_ctx* c, int op, size_t n, int arity, int outputs, const int32_t* in, const int32_t* k, int32_t* out) {
     int rc = bind(c); if (rc) return rc;
-    if (op < 0 || op >= FR_OP_COUNT || (fp_raw_arity(op) == 0 && op != FR_QUOT_TOP) || arity != fp_raw_arity(op) || outputs != fp_raw_outputs(op) || !in || !k || !out) return C12381_E_ARG;
+    if (!fp_raw_is_op(op) || arity != fp_raw_arity(op) || outputs != fp_raw_outputs(op) || !in || !k || !out) return C12381_E_ARG;
     if (n == 0) return 0;
     staging s;
     const size_t in_bytes = (arity ? (size_t)arity : 1) * NL * sizeof(int32_t) * n;
     if ((rc = stage(c, s, {{in, in_bytes}, {k, FR_MAX_K * sizeof(int32_t) * n}}, {{out, (size_t)outputs * NL * sizeof(int32_t) * n}}))) return rc;
-    LAUNCH(c, fp_raw_kernel, n, op, n, (const int32_t*)s.in[0], (const int32_t*)s.in[1], (int32_t*)s.out[0]);
+    if (fp_raw_is_two_lane(op)) LAUNCH(c, fp2h_raw_kernel, 2 * n, op, n, (const int32_t*)s.in[0], (const int32_t*)s.in[1], (int32_t*)s.out[0]);
+    else LAUNCH(c, fp_raw_kernel, n, op, n, (const int32_t*)s.in[0], (const int32_t*)s.in[1], (int32_t*)s.out[0]);
     return unstage(c, s);
 }
 #endif

@@ -8,7 +8,8 @@
 //                products, ONE reduction per lane, the same 4 products + 2 reductions per element as fp2_mul
 //   product pair a*b +- c*d: four products, ONE reduction per lane (fp2_mul2)
 //   square       complex squaring: (a + pa)(a - pa) on the real lane, (2 pa) a on the imaginary lane — ONE product per
-//                lane; operand limb bound 2^28.5 (a normalised value)
+//                lane; both factors carry limb bound 2 LB, so 14 * 4 LB^2 + 14 * 2^56 + 2^40 < 2^63: LB <= 382999548 = 2^28.51 (a
+//                normalised value; pinned by test_raw_limbs_at_the_bounds[FH2_SQR], tests/fp_raw_vectors.py)
 //   add/sub/neg  per lane, no communication
 //   partner      one DPP move per dword (quad_perm [1,0,3,2]): adjacent lanes swap inside the VALU, no LDS traffic
 //

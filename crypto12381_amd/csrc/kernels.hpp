@@ -82,6 +82,7 @@ __global__ void __launch_bounds__(BLOCK, 2) miller_kernel(size_t n, const uint8_
 __global__ void __launch_bounds__(BLOCK, 2) gt_op_kernel(int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 __global__ void __launch_bounds__(BLOCK, 2) gt_is_unity_kernel(size_t n, const uint8_t* a, uint8_t* out);
 __global__ void __launch_bounds__(BLOCK, 2) fp_raw_kernel(int op, size_t n, const int32_t* in, const int32_t* kk, int32_t* out);   // k_fp_raw.hip: raw-limb test kernel
+__global__ void __launch_bounds__(BLOCK, 2) fp2h_raw_kernel(int op, size_t n, const int32_t* in, const int32_t* kk, int32_t* out);  // the same, two lanes per element (fp2h.hpp)
 #endif
 __global__ void __launch_bounds__(BLOCK, 2) pair3_kernel(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) pair3_prod_kernel(size_t n, int k, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, int* bad_flag, int miller_only);

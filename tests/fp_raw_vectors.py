@@ -6,6 +6,11 @@ with LBa = 2^31 - 1), top limbs that put sum VBa VBb at the checker's cap 10^6, 
 representations of k p + e for the predicates.  Every vector is checked against its routine's precondition with its real limbs
 and its real value (assertions, nothing is filtered); COUNTS pins the number of vectors per op.
 
+The two-lane form of Fp2 (csrc/fp2h.hpp, ops FH2_*: half an element per lane on the device, both halves in one object on the host) is packed
+like the whole-element ops FP2_* and shares their expected values — the Fp2 formula, never the lane routine's U / V selection or its
+(a + b)(a - b) — and their vectors wherever the preconditions agree; where they do not (FH2_SQR) the limit is derived from the lane
+routine's own column inequality, in the comment above the generator (vectors()).
+
 Expected values are plain integer mathematics, not a transliteration of the column scan: a Montgomery reduction of the integer
 F = sum +-A_t B_t + R sum k_j C_j returns (F + ((-F / p) mod R) p) / R, written with limbs 0..12 in [0, 2^28) and a signed top limb."""
 import random
@@ -27,24 +32,41 @@ INJ_ROOM = 1 << 37                       # column room the injected forms keep f
 OPS = dict(MUL=0, SQR=1, MUL2_ADD=2, MUL2_SUB=3, RED1=4, RED2=5, RED3=6, RED4=7, REDS1=8, REDS2=9, REDS3=10, REDS4=11, INJ=12, INJ_CONST=13,
            SQR_INJ_CONST=14, INJ_LIT=15, QUOT_TOP=16, NORM1=17, NORM1_DBL=18, MUL_SMALL=19, WEAK_REDUCE=20, LINCOMB3P=21, CANON=22, IS_ZERO=23,
            EQUAL=24, SIGN=25, TO_WORDS=26, INV=27, ADD=28, SUB=29, NEG=30, FP2_MUL=32, FP2_SQR=33, FP2_MUL2_ADD=34, FP2_MUL2_SUB=35,
-           FP2_MUL_INJ=36, FP2_MUL_IP=37, FP2_IS_ZERO=38, FP2_INV=39, FP2_SIGN=40)
+           FP2_MUL_INJ=36, FP2_MUL_IP=37, FP2_IS_ZERO=38, FP2_INV=39, FP2_SIGN=40, SQR2=41, MUL_MSQR2=42, FP2_CONJ=43, FP2_CONJ_MUL_CI=44,
+           FP2_CONJ_MUL_NEG_I=45, FP2_CONJ_MUL_A1MI=46, FP2_MUL_FP=47, FP2_NORM1_DBL=48,
+           FH2_ADD=64, FH2_SUB=65, FH2_NEG=66, FH2_DBL=67, FH2_NORM1=68, FH2_MUL_SMALL=69, FH2_SELECT=70, FH2_CONJ=71, FH2_MUL_IP=72, FH2_IS_ZERO=73,
+           FH2_MUL=74, FH2_SQR=75, FH2_MUL2_ADD=76, FH2_MUL2_SUB=77, FH2_MUL_FP=78, FH2_CONJ_MUL_CI=79, FH2_CONJ_MUL_NEG_I=80, FH2_CONJ_MUL_A1MI=81,
+           FH2_ONE=82)
 ARITY = dict(MUL=2, SQR=1, MUL2_ADD=4, MUL2_SUB=4, RED1=2, RED2=4, RED3=6, RED4=8, REDS1=2, REDS2=4, REDS3=6, REDS4=8, INJ=4, INJ_CONST=4,
              SQR_INJ_CONST=3, INJ_LIT=4, QUOT_TOP=0, NORM1=1, NORM1_DBL=1, MUL_SMALL=1, WEAK_REDUCE=1, LINCOMB3P=3, CANON=1, IS_ZERO=1, EQUAL=2,
              SIGN=1, TO_WORDS=1, INV=1, ADD=2, SUB=2, NEG=1, FP2_MUL=4, FP2_SQR=2, FP2_MUL2_ADD=8, FP2_MUL2_SUB=8, FP2_MUL_INJ=6, FP2_MUL_IP=2,
-             FP2_IS_ZERO=2, FP2_INV=2, FP2_SIGN=2)
-OUTPUTS = {name: 2 if name in ("FP2_MUL", "FP2_SQR", "FP2_MUL2_ADD", "FP2_MUL2_SUB", "FP2_MUL_INJ", "FP2_MUL_IP", "FP2_INV") else 1 for name in OPS}
+             FP2_IS_ZERO=2, FP2_INV=2, FP2_SIGN=2, SQR2=1, MUL_MSQR2=3, FP2_CONJ=2, FP2_CONJ_MUL_CI=3, FP2_CONJ_MUL_NEG_I=2, FP2_CONJ_MUL_A1MI=3,
+             FP2_MUL_FP=3, FP2_NORM1_DBL=2,
+             FH2_ADD=4, FH2_SUB=4, FH2_NEG=2, FH2_DBL=2, FH2_NORM1=2, FH2_MUL_SMALL=2, FH2_SELECT=4, FH2_CONJ=2, FH2_MUL_IP=2, FH2_IS_ZERO=2, FH2_MUL=4,
+             FH2_SQR=2, FH2_MUL2_ADD=8, FH2_MUL2_SUB=8, FH2_MUL_FP=3, FH2_CONJ_MUL_CI=3, FH2_CONJ_MUL_NEG_I=2, FH2_CONJ_MUL_A1MI=3, FH2_ONE=0)
+# the two-lane ops always return two elements: both halves, or for the predicate FH2_IS_ZERO the flag of each of the two lanes
+OUTPUTS = {name: 2 if name in ("FP2_MUL", "FP2_SQR", "FP2_MUL2_ADD", "FP2_MUL2_SUB", "FP2_MUL_INJ", "FP2_MUL_IP", "FP2_INV", "FP2_CONJ", "FP2_CONJ_MUL_CI",
+                               "FP2_CONJ_MUL_NEG_I", "FP2_CONJ_MUL_A1MI", "FP2_MUL_FP", "FP2_NORM1_DBL") or name[:4] == "FH2_" else 1 for name in OPS}
 FAMILIES = {
     "product + reduction": ["MUL", "SQR", "MUL2_ADD", "MUL2_SUB", "RED1", "RED2", "RED3", "RED4", "REDS1", "REDS2", "REDS3", "REDS4"],
     "injected reductions": ["INJ", "INJ_CONST", "SQR_INJ_CONST", "INJ_LIT", "QUOT_TOP"],
     "exact carries": ["NORM1", "NORM1_DBL", "MUL_SMALL", "WEAK_REDUCE", "LINCOMB3P"],
     "canonical form and predicates": ["CANON", "IS_ZERO", "EQUAL", "SIGN", "TO_WORDS", "INV"],
     "Fp2": ["FP2_MUL", "FP2_SQR", "FP2_MUL2_ADD", "FP2_MUL2_SUB", "FP2_MUL_INJ", "FP2_MUL_IP", "FP2_IS_ZERO", "FP2_INV", "FP2_SIGN"],
+    "doubling and psi forms": ["SQR2", "MUL_MSQR2", "FP2_CONJ", "FP2_CONJ_MUL_CI", "FP2_CONJ_MUL_NEG_I", "FP2_CONJ_MUL_A1MI", "FP2_MUL_FP", "FP2_NORM1_DBL"],
+    # csrc/fp2h.hpp: half an element per lane on the device (fp2h_raw_kernel), both halves in one object on the host
+    "Fp2, two lanes": ["FH2_ADD", "FH2_SUB", "FH2_NEG", "FH2_DBL", "FH2_NORM1", "FH2_MUL_SMALL", "FH2_SELECT", "FH2_CONJ", "FH2_MUL_IP", "FH2_IS_ZERO", "FH2_MUL",
+                       "FH2_SQR", "FH2_MUL2_ADD", "FH2_MUL2_SUB", "FH2_MUL_FP", "FH2_CONJ_MUL_CI", "FH2_CONJ_MUL_NEG_I", "FH2_CONJ_MUL_A1MI", "FH2_ONE"],
 }
 # vectors per op (asserted after generation; every one of them is run, on the host and on the device)
 COUNTS = dict(MUL=2624, SQR=263, MUL2_ADD=1748, MUL2_SUB=1748, RED1=1748, RED2=1748, RED3=1748, RED4=1748, REDS1=1748, REDS2=1748, REDS3=1748,
               REDS4=1748, INJ=1748, INJ_CONST=1748, SQR_INJ_CONST=263, INJ_LIT=1748, QUOT_TOP=4127, NORM1=361, NORM1_DBL=361, MUL_SMALL=1296,
               WEAK_REDUCE=636, LINCOMB3P=1408, CANON=1240, IS_ZERO=1240, EQUAL=1392, SIGN=1240, TO_WORDS=1240, INV=1240, FP2_MUL=1748,
-              FP2_SQR=263, FP2_MUL2_ADD=1748, FP2_MUL2_SUB=1748, FP2_MUL_INJ=1748, FP2_MUL_IP=361, FP2_IS_ZERO=1240, FP2_INV=263, FP2_SIGN=1240)
+              FP2_SQR=263, FP2_MUL2_ADD=1748, FP2_MUL2_SUB=1748, FP2_MUL_INJ=1748, FP2_MUL_IP=361, FP2_IS_ZERO=1240, FP2_INV=263, FP2_SIGN=1240,
+              SQR2=263, MUL_MSQR2=1640, FP2_CONJ=203, FP2_CONJ_MUL_CI=1748, FP2_CONJ_MUL_NEG_I=203, FP2_CONJ_MUL_A1MI=1748, FP2_MUL_FP=1748,
+              FP2_NORM1_DBL=361, FH2_ADD=351, FH2_SUB=351, FH2_NEG=203, FH2_DBL=203, FH2_NORM1=361, FH2_MUL_SMALL=1296, FH2_SELECT=203, FH2_CONJ=203,
+              FH2_MUL_IP=361, FH2_IS_ZERO=640, FH2_MUL=1748, FH2_SQR=263, FH2_MUL2_ADD=1748, FH2_MUL2_SUB=1748, FH2_MUL_FP=1748, FH2_CONJ_MUL_CI=1748,
+              FH2_CONJ_MUL_NEG_I=203, FH2_CONJ_MUL_A1MI=1748, FH2_ONE=40)
 N_RANDOM = 128                           # uniformly random vectors per op (the only part that may be resized for run time)
 
 
@@ -198,6 +220,8 @@ def products(name, A):
     if name in ("SQR", "SQR_INJ_CONST"): return [(1, A[0], A[0])]
     if name == "MUL2_ADD": return [(1, A[0], A[1]), (1, A[2], A[3])]
     if name == "MUL2_SUB": return [(1, A[0], A[1]), (-1, A[2], A[3])]
+    if name == "SQR2": return [(2, A[0], A[0])]
+    if name == "MUL_MSQR2": return [(1, A[0], A[1]), (-2, A[2], A[2])]
     if name[:3] == "RED":
         T = int(name[-1]); return [((-1) ** t, A[2 * t], A[2 * t + 1]) for t in range(T)]
     raise KeyError(name)
@@ -213,8 +237,17 @@ def injected(name, A, k):
 
 
 def fp2_forms(name, A, k):
-    """per output coordinate: (products, injected)"""
+    """per output coordinate: (products, injected).  A two-lane op FH2_X has the expectation of FP2_X: the Fp2 formula, not the lane routine."""
+    if name[:4] == "FH2_":
+        name = "FP2_" + name[4:]
     a, b = A[0], A[1]
+    if name == "FP2_MUL_FP":                                       # (a + b i) s
+        return [([(1, a, A[2])], []), ([(1, b, A[2])], [])]
+    if name == "FP2_CONJ_MUL_CI":                                  # (a - b i) (c i) = b c + a c i
+        return [([(1, b, A[2])], []), ([(1, a, A[2])], [])]
+    if name == "FP2_CONJ_MUL_A1MI":                                # +-(a - b i) c (1 - i) = +-((a - b) c - (a + b) c i), - when k0 != 0
+        s = -1 if k[0] else 1
+        return [([(s, a - b, A[2])], []), ([(-s, a + b, A[2])], [])]
     if name in ("FP2_MUL", "FP2_MUL_INJ"):
         c, d = A[2], A[3]
         ia = [(k[0], A[4]), (k[2], P)] if name == "FP2_MUL_INJ" else []
@@ -252,18 +285,35 @@ def expected(name, vec):
     L = [o.l for o in vec.x]
     k = vec.k
     flag = lambda b: [int(b)] + [0] * (NL - 1)
-    if name in ("MUL", "SQR", "MUL2_ADD", "MUL2_SUB", "INJ", "INJ_CONST", "SQR_INJ_CONST", "INJ_LIT") or name[:3] == "RED":
+    if name in ("MUL", "SQR", "MUL2_ADD", "MUL2_SUB", "INJ", "INJ_CONST", "SQR_INJ_CONST", "INJ_LIT", "SQR2", "MUL_MSQR2") or name[:3] == "RED":
         return [reduce_form(products(name, A), injected(name, A, k))]
-    if name in ("FP2_MUL", "FP2_SQR", "FP2_MUL2_ADD", "FP2_MUL2_SUB", "FP2_MUL_INJ"):
+    if name in FP2_PRODUCTS:
         return [reduce_form(p_, i_) for p_, i_ in fp2_forms(name, A, k)]
-    if name == "NORM1":
-        r = [(L[0][i] & M28) + (L[0][i - 1] >> LB if i else 0) for i in range(NL - 1)] + [L[0][NL - 1] + (L[0][NL - 2] >> LB)]
-        assert val(r) == A[0]
-        return [r]
-    if name == "NORM1_DBL":
-        r = [((2 * L[0][i]) & M28) + (L[0][i - 1] >> (LB - 1) if i else 0) for i in range(NL - 1)] + [2 * L[0][NL - 1] + (L[0][NL - 2] >> (LB - 1))]
-        assert val(r) == 2 * A[0]
-        return [r]
+
+    def norm1(l):
+        r = [(l[i] & M28) + (l[i - 1] >> LB if i else 0) for i in range(NL - 1)] + [l[NL - 1] + (l[NL - 2] >> LB)]
+        assert val(r) == val(l)
+        return r
+
+    def norm1_dbl(l):
+        r = [((2 * l[i]) & M28) + (l[i - 1] >> (LB - 1) if i else 0) for i in range(NL - 1)] + [2 * l[NL - 1] + (l[NL - 2] >> (LB - 1))]
+        assert val(r) == 2 * val(l)
+        return r
+
+    if name == "NORM1": return [norm1(L[0])]
+    if name == "NORM1_DBL": return [norm1_dbl(L[0])]
+    if name == "FH2_NORM1": return [norm1(L[0]), norm1(L[1])]
+    if name == "FP2_NORM1_DBL": return [norm1_dbl(L[0]), norm1_dbl(L[1])]
+    if name == "FH2_ADD": return [[x + y for x, y in zip(L[0], L[2])], [x + y for x, y in zip(L[1], L[3])]]
+    if name == "FH2_SUB": return [[x - y for x, y in zip(L[0], L[2])], [x - y for x, y in zip(L[1], L[3])]]
+    if name == "FH2_NEG": return [[-x for x in L[0]], [-x for x in L[1]]]
+    if name == "FH2_DBL": return [[2 * x for x in L[0]], [2 * x for x in L[1]]]
+    if name == "FH2_MUL_SMALL": return [to_limbs(k[0] * A[0]), to_limbs(k[0] * A[1])]
+    if name == "FH2_SELECT": return [L[0], L[1]] if k[0] else [L[2], L[3]]
+    if name in ("FP2_CONJ", "FH2_CONJ"): return [L[0], [-x for x in L[1]]]
+    if name in ("FP2_CONJ_MUL_NEG_I", "FH2_CONJ_MUL_NEG_I"): return [[-x for x in L[1]], [-x for x in L[0]]]       # (a - b i)(-i) = -b - a i
+    if name == "FH2_IS_ZERO": return [flag(A[0] % P == 0 and A[1] % P == 0)] * 2                                 # the flag of each of the two lanes
+    if name == "FH2_ONE": return [to_limbs(RM % P), [0] * NL]
     if name == "MUL_SMALL": return [to_limbs(k[0] * A[0])]
     if name == "LINCOMB3P": return [to_limbs(k[0] * A[0] + k[1] * A[1] + k[2] * A[2] + k[3] * P)]
     if name in ("WEAK_REDUCE", "QUOT_TOP"): return [None]
@@ -278,7 +328,7 @@ def expected(name, vec):
     if name == "ADD": return [[x + y for x, y in zip(L[0], L[1])]]
     if name == "SUB": return [[x - y for x, y in zip(L[0], L[1])]]
     if name == "NEG": return [[-x for x in L[0]]]
-    if name == "FP2_MUL_IP": return [[x - y for x, y in zip(L[0], L[1])], [x + y for x, y in zip(L[0], L[1])]]
+    if name in ("FP2_MUL_IP", "FH2_MUL_IP"): return [[x - y for x, y in zip(L[0], L[1])], [x + y for x, y in zip(L[0], L[1])]]
     if name == "FP2_IS_ZERO": return [flag(A[0] % P == 0 and A[1] % P == 0)]
     if name == "FP2_SIGN":
         ca, cb = canon(A[0]), canon(A[1])
@@ -316,9 +366,12 @@ def check_outputs(name, vec, outs, bounds=None):
             assert abs(got[NL - 1]) <= lb
 
 
-PREDICATES = ("IS_ZERO", "EQUAL", "SIGN", "TO_WORDS", "FP2_IS_ZERO", "FP2_SIGN", "QUOT_TOP")
+PREDICATES = ("IS_ZERO", "EQUAL", "SIGN", "TO_WORDS", "FP2_IS_ZERO", "FP2_SIGN", "QUOT_TOP", "FH2_IS_ZERO")
+# Montgomery products of Fp2 elements, one reduce_form per coordinate (fp2_forms)
+FP2_PRODUCTS = ("FP2_MUL", "FP2_SQR", "FP2_MUL2_ADD", "FP2_MUL2_SUB", "FP2_MUL_INJ", "FP2_MUL_FP", "FP2_CONJ_MUL_CI", "FP2_CONJ_MUL_A1MI",
+                "FH2_MUL", "FH2_SQR", "FH2_MUL2_ADD", "FH2_MUL2_SUB", "FH2_MUL_FP", "FH2_CONJ_MUL_CI", "FH2_CONJ_MUL_A1MI")
 NORMALISED = ("MUL", "SQR", "MUL2_ADD", "MUL2_SUB", "RED1", "RED2", "RED3", "RED4", "REDS1", "REDS2", "REDS3", "REDS4", "INJ", "INJ_CONST", "SQR_INJ_CONST",
-              "INJ_LIT", "MUL_SMALL", "WEAK_REDUCE", "LINCOMB3P", "CANON", "INV", "FP2_MUL", "FP2_SQR", "FP2_MUL2_ADD", "FP2_MUL2_SUB", "FP2_MUL_INJ", "FP2_INV")
+              "INJ_LIT", "MUL_SMALL", "WEAK_REDUCE", "LINCOMB3P", "CANON", "INV", "FP2_INV", "SQR2", "MUL_MSQR2", "FH2_MUL_SMALL", "FH2_ONE") + FP2_PRODUCTS
 
 
 # ---------------------------------------------------------------- preconditions (real limbs, real values)
@@ -341,6 +394,19 @@ def forms_of(name, k):
     elif name == "FP2_MUL_INJ": forms = [([(1, 0, 2), (1, 1, 3)], [(k[0], 4), (k[2], None)]), ([(1, 0, 3), (1, 1, 2)], [(k[1], 5), (k[3], None)])]
     elif name in ("FP2_SQR", "FP2_INV"): forms = [([(1, 0, 0), (1, 1, 1)], []), ([(2, 0, 1)], [])]
     elif name in ("FP2_MUL2_ADD", "FP2_MUL2_SUB"): forms = [([(1, 0, 2), (1, 1, 3), (1, 4, 6), (1, 5, 7)], []), ([(1, 0, 3), (1, 1, 2), (1, 4, 7), (1, 5, 6)], [])]
+    elif name == "SQR2": forms = [([(2, 0, 0)], [])]                                              # fp_mul(a, 2a)
+    elif name == "MUL_MSQR2": forms = [([(1, 0, 1), (2, 2, 2)], [])]
+    elif name in ("FP2_MUL_FP", "FP2_CONJ_MUL_CI", "FH2_MUL_FP", "FH2_CONJ_MUL_CI"): forms = [([(1, 0, 2)], []), ([(1, 1, 2)], [])]
+    # the product operand y.a -+ y.b is a lazy sum: bounds LB(y.a) + LB(y.b) and VB(y.a) + VB(y.b), one product per coordinate
+    elif name in ("FP2_CONJ_MUL_A1MI", "FH2_CONJ_MUL_A1MI"): forms = [([(1, 0, 2), (1, 1, 2)], [])]
+    # the two-lane products, as fp2h.hpp forms them per lane (role: real / imaginary):
+    #   FH2_MUL     fp_mul2: own * U + partner * V with (U, V) = (y.a, -y.b) / (y.a, y.b): the operand pairs of FP2_MUL
+    #   FH2_MUL2_*  four such products in one static reduction: the operand pairs of FP2_MUL2_*
+    #   FH2_SQR     ONE product of two lazy sums: (a + b)(a - b), bound (LBa + LBb)^2 = LBa^2 + 2 LBa LBb + LBb^2, / (2a) b, whose left
+    #               factor is an fp_select of 2 partner and a + b and declares the larger: 2 LBa (LBa + LBb) and 2 LBb (LBa + LBb)
+    elif name == "FH2_MUL": forms = forms_of("FP2_MUL", k)
+    elif name in ("FH2_MUL2_ADD", "FH2_MUL2_SUB"): forms = forms_of("FP2_MUL2_ADD", k)
+    elif name == "FH2_SQR": forms = [([(1, 0, 0), (2, 0, 1), (1, 1, 1)], []), ([(2, 0, 0), (2, 0, 1)], []), ([(2, 1, 1), (2, 0, 1)], [])]
     else: forms = []
     return forms
 
@@ -384,8 +450,27 @@ def assert_precondition(name, vec):
     if name == "LINCOMB3P":
         assert (abs(k[0]) * A[0] + abs(k[1]) * A[1] + abs(k[2]) * A[2] + abs(k[3]) * P) // TOPW + 3 <= T31
         assert abs(k[0]) * D[0] + abs(k[1]) * D[1] + abs(k[2]) * D[2] + (abs(k[3]) << LB) < 1 << 62
-    if name in ("EQUAL", "ADD", "SUB", "FP2_MUL_IP"): assert D[0] + D[1] <= T31
-    if name in ("CANON", "IS_ZERO", "SIGN", "TO_WORDS", "INV", "FP2_IS_ZERO", "FP2_SIGN"): assert all(col_ok(d) for d in D)
+    if name in ("EQUAL", "ADD", "SUB", "FP2_MUL_IP", "FH2_MUL_IP", "FP2_CONJ_MUL_A1MI", "FH2_CONJ_MUL_A1MI"): assert D[0] + D[1] <= T31
+    if name in ("CANON", "IS_ZERO", "SIGN", "TO_WORDS", "INV", "FP2_IS_ZERO", "FP2_SIGN", "FH2_IS_ZERO"): assert all(col_ok(d) for d in D)
+    if name == "SQR2": assert 2 * D[0] <= T31
+    if name == "MUL_MSQR2": assert 4 * D[2] <= T31                                           # -4c is formed as raw limbs
+    if name in ("FH2_ADD", "FH2_SUB"): assert D[0] + D[2] <= T31 and D[1] + D[3] <= T31
+    if name in ("FH2_DBL", "FH2_SQR"): assert 2 * D[0] <= T31 and 2 * D[1] <= T31
+    if name == "FH2_SQR": assert D[0] + D[1] <= T31
+    if name == "FH2_NORM1": assert all(A[i] // TOPW + 4 + (D[i] >> LB) <= T31 for i in (0, 1))
+    if name == "FP2_NORM1_DBL": assert all(2 * (A[i] // TOPW) + 8 + (2 * D[i] >> LB) <= T31 and abs(vec.x[i].l[NL - 1]) < (1 << 30) - 16 for i in (0, 1))
+    if name == "FH2_MUL_SMALL": assert k[0] >= 0 and all(k[0] * A[i] // TOPW + 3 <= T31 for i in (0, 1))
+    if name in ("FH2_NEG", "FH2_CONJ", "FH2_CONJ_MUL_NEG_I", "FP2_CONJ", "FP2_CONJ_MUL_NEG_I"): assert all(x > -(1 << 31) for o in vec.x for x in o.l)
+    if name in ("FH2_MUL", "FH2_MUL2_ADD", "FH2_MUL2_SUB"):
+        # fp2h_lane_uv takes U and V by fp_select, which declares the larger bound of y's two halves for both: what the checker multiplies is
+        # (LBx.a + LBx.b) max(LBy.a, LBy.b) per product pair, and the same in value bounds — no weaker than the pairs really formed (above)
+        V = [o.vb for o in vec.x]
+        pairs = [(0, 1, 2, 3)] if name == "FH2_MUL" else [(0, 1, 2, 3), (4, 5, 6, 7)]
+        assert col_ok(sum((D[a] + D[b]) * max(D[c], D[d]) for a, b, c, d in pairs)), (name, "column, declared by fp_select")
+        assert sum((V[a] + V[b]) * max(V[c], V[d]) for a, b, c, d in pairs) <= CAP, (name, "value cap, declared by fp_select")
+    if name in ("FH2_SQR", "FH2_CONJ_MUL_A1MI", "FP2_CONJ_MUL_A1MI"):
+        V = [o.vb for o in vec.x]                                                             # the lazy sums' DECLARED value bounds are what is multiplied
+        assert (V[0] + V[1]) * (max(2 * V[0], 2 * V[1], V[0] + V[1]) if name == "FH2_SQR" else V[2]) <= CAP, (name, "value cap, declared")
 
 
 # ---------------------------------------------------------------- generators
@@ -402,10 +487,11 @@ def scale_top(top, T):
     return ("cap", max(1, isqrt(top[1] * top[1] // T)) if top[1] >= 45 else top[1], top[2])
 
 
-def product_vectors(name, T, pairs, rng, room=0, square=False, extra=None):
-    """pairs: operand index pairs (a_t, b_t) of the T products; extra(rng) -> (further operands, k)"""
+def product_vectors(name, T, pairs, rng, room=0, square=False, extra=None, amax=T31):
+    """pairs: operand index pairs (a_t, b_t) of the T products; extra(rng) -> (further operands, k); amax: the largest limb limit the first
+    operand of a pair may take (below 2^31 - 1 where the routine adds two such operands before it multiplies)"""
     L = limb_limit(T, room)
-    limits = [(L, L)] if square else [(L, L), (T31, L * L // T31), (min(L * L >> LB, T31 - 1), L * L // min(L * L >> LB, T31 - 1))]
+    limits = [(L, L)] if square else [(L, L), (amax, L * L // amax), (min(L * L >> LB, amax - 1), L * L // min(L * L >> LB, amax - 1))]
     out = []
     n_ops = ARITY[name]
 
@@ -544,6 +630,90 @@ def quot_top_vectors(rng):
     return [Vec([], [t]) for t in tops]
 
 
+# ---------------------------------------------------------------- Fp2 operands: the psi helpers and the two-lane ops
+def paired(name, shift=7):
+    """the vectors of a one-operand Fp op as Fp2 operands: each with the one `shift` places on among those of the same multipliers"""
+    groups = {}
+    for v in vectors(name):
+        groups.setdefault(tuple(v.k), []).append(v)
+    return [Vec([v.x[0], g[(j + shift) % len(g)].x[0]], v.k) for g in groups.values() for j, v in enumerate(g)]
+
+
+def neg_extra():
+    """no further operand; k0 = neg alternates"""
+    state = [0]
+
+    def f(rng):
+        state[0] += 1
+        return [], [state[0] & 1]
+    return f
+
+
+# limb-wise lazy operations: no product, the only limit is int32.  limits = the limb limit of each Fp2 operand (of both its halves)
+#   FH2_NEG, FH2_CONJ, *_CONJ_MUL_NEG_I, FP2_CONJ, FH2_SELECT   |limb| <= 2^31 - 1 (-2^31 has no negative)
+#   FH2_DBL                                                     2 LB <= 2^31 - 1:  LB = 2^30 - 1
+#   FH2_ADD, FH2_SUB                                            LBx + LBy <= 2^31 - 1: (2^30 - 1, 2^30), (2^31 - 1 - 2^28, 2^28) and the reverse
+def lazy_vectors(rng, limit_sets, ks=(0,)):
+    out = []
+    tops = [0, 1, -1, ("cap", 9000, 1), ("cap", 9000, -1)]
+    i = 0
+    for limits in limit_sets:
+        for pi, pa in enumerate(PATTERNS[:-1]):
+            for ta in tops:
+                x = [operand(PATTERNS[(pi + 3 * j) % 15] if fill_fits(PATTERNS[(pi + 3 * j) % 15], lim) else "pos", lim, fit_top(ta, lim), rng)
+                     for j, lim in enumerate(l for l in limits for _ in (0, 1))]
+                out.append(Vec(x, [ks[i % len(ks)]]))
+                i += 1
+        for _ in range(N_RANDOM // len(limit_sets)):
+            out.append(Vec([Operand([rng.randint(-lim, lim) for _ in range(NL)]) for lim in limits for _ in (0, 1)], [ks[i % len(ks)]]))
+            i += 1
+    return out
+
+
+def msqr2_vectors(rng):
+    """fp_mul_msqr2, a b - 2 c^2 in one reduction: 14 (LBa LBb + 2 LBc^2) + 14 2^56 + 2^40 < 2^63 and 4 LBc <= 2^31 - 1 (-4c is formed as raw
+    limbs).  At the inequality three ways: all three operands at L(3); a at 2^31 - 1 against a small b, c at L(3); c at its own cap 2^29 - 1
+    with a and b at what that leaves"""
+    L3, L1, C = limb_limit(3), limb_limit(1), (1 << 29) - 1
+    rest = isqrt(L1 * L1 - 2 * C * C)
+    while not col_ok(rest * rest + 2 * C * C):
+        rest -= 1
+    out = []
+    limits = [(L3, L3, L3), (T31, L3 * L3 // T31, L3), (rest, rest, C)]
+
+    def build(la, lb_, lc, pa, pb, pc, ta, tb):
+        fa, fb = fit_pair(scale_top(ta, 3), scale_top(tb, 3), la, lb_)
+        tc = ("cap", min(scale_top(ta, 3)[1], scale_top(tb, 3)[1]), ta[2]) if isinstance(ta, tuple) else ta      # 2 VBc^2 <= 2/3 of the target VBa VBb
+        return Vec([operand(pa, la, fa, rng), operand(pb, lb_, fb, rng), operand(pc, lc, fit_top(tc, lc), rng)])
+
+    for la, lb_, lc in limits:
+        for pa in PATTERNS[:-1]:
+            if not fill_fits(pa, la): continue
+            for pb, pc in (("pos", "pos"), ("neg", "alt"), ("alt", "neg"), (pa, pa)):
+                if not fill_fits(pb, lb_): pb = "pos"
+                if not fill_fits(pc, lc): pc = "pos"
+                for ta, tb in TOP_PAIRS:
+                    out.append(build(la, lb_, lc, pa, pb, pc, ta, tb))
+    for i in range(N_RANDOM):
+        la, lb_, lc = limits[i % 3]
+        out.append(build(la, lb_, lc, "random", "random", "random", *TOP_PAIRS[i % len(TOP_PAIRS)]))
+    return out
+
+
+def fh2_is_zero_vectors(rng):
+    """every combination of {0, k p (k != 0), e, k p + e} across the two halves, each in several representations"""
+    ks, es = [k for k in PRED_K if k], [e for e in PRED_E if e]
+    classes = [[0], [k * P for k in ks], es, [k * P + e for k in ks for e in es]]
+    out = []
+    for ca in classes:
+        for cb in classes:
+            for j in range(40):
+                out.append(Vec([moved(ca[(5 * j) % len(ca)], MOVES[j % 5], rng), moved(cb[(7 * j + 3) % len(cb)], MOVES[(j // 5 + j) % 5], rng)]))
+    kinds = {(v.x[0].v == 0, v.x[0].v % P == 0, v.x[1].v == 0, v.x[1].v % P == 0) for v in out}
+    assert len(kinds) == 9 and sum(1 for v in out if v.x[0].v % P == 0 and v.x[1].v % P == 0) == 4 * 40
+    return out
+
+
 _CACHE = {}
 
 
@@ -571,6 +741,36 @@ def vectors(name):
     elif name == "FP2_MUL_INJ": v = product_vectors(name, 2, [(0, 2), (1, 3)], rng, room=INJ_ROOM, extra=inj_extra(2, 4))
     elif name in ("FP2_SQR", "FP2_INV"): v = product_vectors(name, 2, [(0, 0), (1, 1)], rng, square=True)
     elif name in ("FP2_MUL2_ADD", "FP2_MUL2_SUB"): v = product_vectors(name, 4, [(0, 2), (1, 3), (4, 6), (5, 7)], rng)
+    # fp_sqr2 = fp_mul(a, 2a): 14 * 2 LBa^2 + ... < 2^63, LBa = L(2), and 2 VBa^2 <= 10^6
+    elif name == "SQR2": v = product_vectors(name, 2, [(0, 0)], rng, square=True)
+    elif name == "MUL_MSQR2": v = msqr2_vectors(rng)
+    # one Fp product per coordinate against the same Fp operand: LBx.a LBs, LBx.b LBs at L(1)^2
+    elif name in ("FP2_MUL_FP", "FP2_CONJ_MUL_CI"): v = product_vectors(name, 1, [(0, 2), (1, 2)], rng)
+    # the product operand y.a -+ y.b has limb bound 2 LB(y) and value bound 2 VB(y): 14 * 2 LB(y) LB(a) + ... < 2^63 is the inequality of TWO
+    # products, LB(y) LB(a) = L(2)^2, and y.a -+ y.b must fit int32: LB(y) <= 2^30 - 1.  k0 = neg alternates.
+    elif name == "FP2_CONJ_MUL_A1MI": v = product_vectors(name, 2, [(0, 2), (1, 2)], rng, extra=neg_extra(), amax=(1 << 30) - 1)
+    elif name == "FP2_NORM1_DBL": v = paired("NORM1_DBL")
+    elif name == "FP2_CONJ": v = lazy_vectors(rng, [(T31,)])
+    # the two-lane ops run the vectors of their whole-element counterparts wherever the preconditions agree (the product pairs of the lane
+    # routines are those of fp2_mul / fp2_mul2; the limits of both halves of an operand are equal in these sets, so fp_select's declared
+    # maximum changes nothing) ...
+    elif name in ("FH2_MUL", "FH2_MUL2_ADD", "FH2_MUL2_SUB", "FH2_MUL_IP", "FH2_MUL_FP", "FH2_CONJ_MUL_CI", "FH2_CONJ_MUL_A1MI", "FH2_CONJ"):
+        v = vectors("FP2_" + name[4:])
+    elif name in ("FP2_CONJ_MUL_NEG_I", "FH2_CONJ_MUL_NEG_I"): v = vectors("FP2_CONJ")
+    # ... and FH2_SQR does not: fp2_sqr sums a^2 and b^2 (2 LB^2, L(2)), fp2h_lane_sqr multiplies (a + b)(a - b) and (2b) a: both factors have
+    # limb bound 2 LB, so 14 * 4 LB^2 + 14 2^56 + 2^40 < 2^63: LB = L(4) = 382999548, the "2^28.5" of fp2h.hpp (2^28.5 = 379625062 is just
+    # below it), and value bound 2 VB each: 4 VB^2 <= 10^6, VB = 500
+    elif name == "FH2_SQR":
+        assert limb_limit(4) == 382999548 and 2 ** 57 <= limb_limit(4) ** 2 < 2 ** 57 * 1.02
+        v = product_vectors(name, 4, [(0, 0), (1, 1)], rng, square=True)
+    elif name == "FH2_NORM1": v = paired("NORM1")
+    elif name == "FH2_MUL_SMALL": v = paired("MUL_SMALL")
+    elif name == "FH2_NEG": v = lazy_vectors(rng, [(T31,)])
+    elif name == "FH2_SELECT": v = lazy_vectors(rng, [(T31, T31)], ks=(1, 0))
+    elif name == "FH2_DBL": v = lazy_vectors(rng, [((1 << 30) - 1,)])
+    elif name in ("FH2_ADD", "FH2_SUB"): v = lazy_vectors(rng, [((1 << 30) - 1, 1 << 30), (T31 - (1 << LB), 1 << LB), (1 << LB, T31 - (1 << LB))])
+    elif name == "FH2_IS_ZERO": v = fh2_is_zero_vectors(rng)
+    elif name == "FH2_ONE": v = [Vec([]) for _ in range(40)]                        # no operand: the lanes differ by their role alone
     elif name == "QUOT_TOP": v = quot_top_vectors(rng)
     elif name in ("NORM1", "NORM1_DBL", "MUL_SMALL", "WEAK_REDUCE", "LINCOMB3P", "FP2_MUL_IP"): v = carry_vectors(name, rng)
     else: v = predicate_vectors(name, rng)
@@ -665,4 +865,95 @@ def closure(run, steps, seed=20260):
         outs = run(name, [Vec([o]) for o in ops])
         for o, r in zip(outs, rs):
             assert o[0] == to_limbs(r * RINV % P)
+    return kinds
+
+
+def closure_fp2h(run, steps, seed=20261):
+    """The same for Fp2 through the two-lane ops, mixed as g2_add and g2_dbl mix them: from the worst-case outputs of FH2_MUL2_ADD (every
+    operand limb at +-L(4), every value at +-500 p: its column inequality and 4 * 500^2 = the cap), `steps` rounds of lazy add / sub / neg /
+    dbl / conj / mul_ip and mul_small, a carry round (FH2_NORM1) when a lazy result would pass L(1) or the next product's own limb limit, and
+    mul / sqr / mul2 (x y + y x and x x - y y; always when a lazy result would pass 500 p, which keeps every product under the value cap).
+    Every step's raw limbs are compared with the prediction, the canonical end values with the residues tracked in Fp2.
+    run(name, vecs) -> raw outputs per vector.  Returns the number of steps of each kind."""
+    rng = random.Random(seed)
+    L1, L4, VMAX = limb_limit(1), limb_limit(4), 500
+    start = [Vec([operand(p_, L4, ("cap", VMAX, s if j % 3 else -s), rng) for j, p_ in enumerate(pats)])
+             for pats in (("pos", "neg", "pos", "alt", "neg", "pos", "alt-", "neg"), ("alt", "alt-", "neg", "neg", "pos", "alt", "alt", "pos")) for s in (1, -1)
+             for pats in (pats, pats[::-1])]
+    assert len(start) == CLOSURE_LANES
+    for v in start:
+        assert_precondition("FH2_MUL2_ADD", v)
+        assert reach("FH2_MUL2_ADD", v)[1] >= 0.999999
+        for o in v.x:
+            assert all(abs(t) == L4 for t in o.l[:NL - 1]) and (VMAX - 1) * P < abs(o.v) <= VMAX * P
+
+    def step(name, vecs):
+        outs = run(name, vecs)
+        for v, o in zip(vecs, outs):
+            check_outputs(name, v, o)
+        return [(Operand(o[0]), Operand(o[1])) for o in outs]
+
+    def mulr(u, v):                       # Montgomery product of residues in Fp2
+        return ((u[0] * v[0] - u[1] * v[1]) * RINV % P, (u[0] * v[1] + u[1] * v[0]) * RINV % P)
+
+    x = step("FH2_MUL2_ADD", start)
+    y = [(v.x[0], v.x[1]) for v in start]
+    rx = [tuple(t % P for t in (v.x[0].v * v.x[2].v - v.x[1].v * v.x[3].v + v.x[4].v * v.x[6].v - v.x[5].v * v.x[7].v,
+                                v.x[0].v * v.x[3].v + v.x[1].v * v.x[2].v + v.x[4].v * v.x[7].v + v.x[5].v * v.x[6].v)) for v in start]
+    rx = [(a * RINV % P, b * RINV % P) for a, b in rx]
+    ry = [(a.v % P, b.v % P) for a, b in y]
+    lazy = {"FH2_ADD": 1, "FH2_SUB": 1, "FH2_NEG": 0, "FH2_CONJ": 0, "FH2_DBL": 0, "FH2_MUL_IP": 0, "FH2_MUL_SMALL": 0}
+    prods = ["FH2_MUL", "FH2_SQR", "FH2_MUL2_ADD", "FH2_MUL2_SUB"]
+    kinds = {}
+    for _ in range(steps):
+        want = rng.choice(["FH2_ADD", "FH2_ADD", "FH2_SUB", "FH2_SUB", "FH2_NEG", "FH2_CONJ", "FH2_DBL", "FH2_MUL_IP", "FH2_MUL_SMALL"] + prods)
+        kk = rng.choice([2, 3])
+        lbx, lby = (max(abs(t) for e in ops for o in e for t in o.l) for ops in (x, y))
+        vx, vy = (max(abs(o.v) for e in ops for o in e) for ops in (x, y))
+        if want in lazy:
+            # what the lazy result may reach: (limb, value)
+            lb_new, v_new = {"FH2_ADD": (lbx + lby, vx + vy), "FH2_SUB": (lbx + lby, vx + vy), "FH2_NEG": (lbx, vx), "FH2_CONJ": (lbx, vx), "FH2_DBL": (2 * lbx, 2 * vx),
+                             "FH2_MUL_IP": (2 * lbx, 2 * vx), "FH2_MUL_SMALL": (0, kk * vx)}[want]
+            if v_new > VMAX * P:
+                want = rng.choice(prods)
+            elif lb_new > L1:
+                want = "FH2_NORM1"
+                if lbx < lby:
+                    x, y, rx, ry, lbx, lby = y, x, ry, rx, lby, lbx
+        if want in prods:
+            # the product's own limb limit (forms_of): mul 2 LBx LBy, sqr 4 LBx^2, x y + y x 4 LBx LBy, x x - y y 2 LBx^2 + 2 LBy^2, all <= L(1)^2
+            need = {"FH2_MUL": 2 * lbx * lby, "FH2_SQR": 4 * lbx * lbx, "FH2_MUL2_ADD": 4 * lbx * lby, "FH2_MUL2_SUB": 2 * lbx * lbx + 2 * lby * lby}[want]
+            if not col_ok(need):
+                want = "FH2_NORM1"
+                if lbx < lby:
+                    x, y, rx, ry = y, x, ry, rx
+        kinds[want] = kinds.get(want, 0) + 1
+        if want in ("FH2_ADD", "FH2_SUB", "FH2_MUL"):
+            vecs = [Vec([a[0], a[1], b[0], b[1]]) for a, b in zip(x, y)]
+            rn = [tuple((s + t) % P for s, t in zip(a, b)) if want == "FH2_ADD" else tuple((s - t) % P for s, t in zip(a, b)) if want == "FH2_SUB" else mulr(a, b)
+                  for a, b in zip(rx, ry)]
+        elif want == "FH2_MUL2_ADD":
+            vecs = [Vec([*a, *b, *b, *a]) for a, b in zip(x, y)]
+            rn = [tuple(2 * t % P for t in mulr(a, b)) for a, b in zip(rx, ry)]
+        elif want == "FH2_MUL2_SUB":
+            vecs = [Vec([*a, *a, *b, *b]) for a, b in zip(x, y)]
+            rn = [tuple((s - t) % P for s, t in zip(mulr(a, a), mulr(b, b))) for a, b in zip(rx, ry)]
+        else:
+            vecs = [Vec([*a], [kk]) for a in x]
+            rn = [{"FH2_NEG": ((-a) % P, (-b) % P), "FH2_CONJ": (a, (-b) % P), "FH2_DBL": (2 * a % P, 2 * b % P), "FH2_MUL_IP": ((a - b) % P, (a + b) % P),
+                   "FH2_MUL_SMALL": (kk * a % P, kk * b % P), "FH2_SQR": mulr((a, b), (a, b)), "FH2_NORM1": (a, b)}[want] for a, b in rx]
+        for v in vecs:
+            assert_precondition(want, v)
+        new = step(want, vecs)
+        for o, r in zip(new, rn):
+            assert (o[0].v % P, o[1].v % P) == r, want
+        if want == "FH2_NORM1":
+            x, rx = new, rn
+        else:
+            x, y, rx, ry = new, x, rn, rx
+    for ops, rs in ((x, rx), (y, ry)):
+        for h in (0, 1):
+            outs = run("CANON", [Vec([e[h]]) for e in ops])
+            for o, r in zip(outs, rs):
+                assert o[0] == to_limbs(r[h] * RINV % P)
     return kinds

@@ -1,5 +1,5 @@
-// TEST HARNESS (CPU): the Fp / Fp2 leaf routines (fp.hpp, fp2.hpp) on RAW limbs under C12381_CHECK_BOUNDS, one op code per routine
-// (csrc/fp_raw_ops.hpp, shared with the device kernel fp_raw_kernel).  Operands come with their DECLARED bounds (lb = max |limb|,
+// TEST HARNESS (CPU): the Fp / Fp2 leaf routines (fp.hpp, fp2.hpp, and fp2h.hpp in its host form) on RAW limbs under C12381_CHECK_BOUNDS, one op
+// code per routine (csrc/fp_raw_ops.hpp, shared with the device kernels fp_raw_kernel and fp2h_raw_kernel).  Operands come with their DECLARED bounds (lb = max |limb|,
 // vb = |value| / p) and results go back with the bounds the routines declare.  bounds_fail aborts the process, so every precondition is
 // checked here first and a lane outside one is reported (return 1, *bad_lane) instead of run.  Not a product path.
 #include <cmath>
@@ -60,6 +60,34 @@ bool precondition(int op, const fp (&x)[FR_MAX_IN], const int32_t (&k)[FR_MAX_K]
         case FR2_IS_ZERO: case FR2_SIGN: return col(L(0)) && col(L(1));
         case FR2_INV: return col(L(0) * L(0) + L(1) * L(1)) && val(V(0) * V(0) + V(1) * V(1)) && 2 * L(0) < T31 && 2 * L(1) < T31
                              && col(L(0) * T28) && col(L(1) * T28) && val(V(0) * 1.001) && val(V(1) * 1.001);
+        case FR_SQR2: return col(2 * L(0) * L(0)) && val(2 * V(0) * V(0)) && 2 * L(0) < T31;                   // fp_mul(a, 2a)
+        case FR_MUL_MSQR2: return col(L(0) * L(1) + 2 * L(2) * L(2)) && val(V(0) * V(1) + 2 * V(2) * V(2)) && 4 * L(2) < T31;   // -4c is formed as raw limbs
+        case FR2_CONJ: case FR2_CONJ_MUL_NEG_I: case FH2_NEG: case FH2_SELECT: case FH2_CONJ: case FH2_CONJ_MUL_NEG_I: case FH2_ONE: return true;
+        case FR2_MUL_FP: case FR2_CONJ_MUL_CI: case FH2_MUL_FP: case FH2_CONJ_MUL_CI: return col(L(0) * L(2)) && col(L(1) * L(2)) && val(V(0) * V(2)) && val(V(1) * V(2));
+        // the product operand is y.a -+ y.b, limb bound LB(y.a) + LB(y.b)
+        case FR2_CONJ_MUL_A1MI: case FH2_CONJ_MUL_A1MI: return L(0) + L(1) <= T31 && col((L(0) + L(1)) * L(2)) && val((V(0) + V(1)) * V(2));
+        case FR2_NORM1_DBL:
+            for (int e = 0; e < 2; ++e)
+                if (!(2 * V(e) * TOP_PER_P + 6.0 + std::floor(2 * L(e) / T28) <= T31 && std::fabs((double)x[e].l[NL - 1]) < T31 / 2 - 16)) return false;
+            return true;
+        case FH2_ADD: case FH2_SUB: return L(0) + L(2) <= T31 && L(1) + L(3) <= T31;
+        case FH2_DBL: return 2 * L(0) <= T31 && 2 * L(1) <= T31;
+        case FH2_NORM1: return V(0) * TOP_PER_P + 4.0 + std::floor(L(0) / T28) <= T31 && V(1) * TOP_PER_P + 4.0 + std::floor(L(1) / T28) <= T31;
+        case FH2_MUL_SMALL: return k[0] >= 0 && topok(V(0) * k[0]) && topok(V(1) * k[0]);
+        case FH2_MUL_IP: return L(0) + L(1) <= T31;
+        case FH2_IS_ZERO: return col(L(0)) && col(L(1));
+        // fp2h_lane_uv takes U and V by fp_select, whose declared bounds are the larger of the two halves of y: own * U + partner * V is
+        // (LBx.a + LBx.b) max(LBy.a, LBy.b) on both lanes
+        case FH2_MUL: return col((L(0) + L(1)) * std::fmax(L(2), L(3))) && val((V(0) + V(1)) * std::fmax(V(2), V(3)));
+        // (a + b)(a - b) on the real lane, (2a) b on the imaginary lane, the left factor by fp_select: max(2 LB partner, LBa + LBb) (LBa + LBb)
+        case FH2_SQR: {
+            const double sl = L(0) + L(1), sv = V(0) + V(1);
+            return sl <= T31 && 2 * L(0) <= T31 && 2 * L(1) <= T31 && col(std::fmax(2 * L(0), sl) * sl) && col(std::fmax(2 * L(1), sl) * sl)
+                   && val(std::fmax(2 * V(0), sv) * sv) && val(std::fmax(2 * V(1), sv) * sv);
+        }
+        case FH2_MUL2_ADD: case FH2_MUL2_SUB:
+            return col((L(0) + L(1)) * std::fmax(L(2), L(3)) + (L(4) + L(5)) * std::fmax(L(6), L(7)))
+                   && val((V(0) + V(1)) * std::fmax(V(2), V(3)) + (V(4) + V(5)) * std::fmax(V(6), V(7)));
         default: return false;
     }
 }
@@ -72,7 +100,7 @@ extern "C" {
 // is run from that lane on); -1 for an unknown op.
 int sim_fp_raw_batch(int op, size_t n, const int32_t* in, const double* in_b, const int32_t* kk, int32_t* out, double* out_b, long long* bad_lane) {
     const int ar = fp_raw_arity(op), no = fp_raw_outputs(op);
-    if (op < 0 || op >= FR_OP_COUNT || (ar == 0 && op != FR_QUOT_TOP)) return -1;
+    if (!fp_raw_is_op(op)) return -1;
     for (size_t i = 0; i < n; ++i) {
         fp x[FR_MAX_IN], r[FR_MAX_OUT];
         int32_t k[FR_MAX_K];
@@ -83,7 +111,14 @@ int sim_fp_raw_batch(int op, size_t n, const int32_t* in, const double* in_b, co
         }
         std::memcpy(k, kk + i * FR_MAX_K, sizeof k);
         if (!precondition(op, x, k)) { *bad_lane = (long long)i; return 1; }
-        fp_raw_apply(op, x, k, r);
+        if (fp_raw_is_two_lane(op)) {            // the host form of fp2h: both halves in one object, the per-lane routines once per role
+            fp2h h; fp2 t;
+            fp2h_raw_apply(op, x, k, h);
+            fp2h_to(t, h);
+            r[0] = t.a; r[1] = t.b;
+        } else {
+            fp_raw_apply(op, x, k, r);
+        }
         for (int e = 0; e < no; ++e) {
             std::memcpy(out + (i * no + e) * NL, r[e].l, sizeof(int32_t) * NL);
             out_b[(i * no + e) * 2] = r[e].lb; out_b[(i * no + e) * 2 + 1] = r[e].vb;

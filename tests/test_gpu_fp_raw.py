@@ -4,7 +4,12 @@ it (child process, C12381_LIB).  The operands the product entries can reach are 
 negative limbs, limbs at +-L(T) and 2^31 - 1, values from -20000 p to 20000 p and non-zero multiples of p.  Every raw output limb is
 compared with the integer the mathematics predicts (fp_raw_vectors.py: the same vectors and expectations as on the host, so host ==
 device follows), in batches of 1, 63, 65 elements and the whole set; the closure run alternates lazy operations and products for a
-few thousand launches.  Vectors per op: fp_raw_vectors.COUNTS, all of them run."""
+few thousand launches.  Vectors per op: fp_raw_vectors.COUNTS, all of them run.
+
+The family "Fp2, two lanes" runs csrc/fp2h.hpp in its DEVICE form through fp2h_raw_kernel (the same entry, by op code): two adjacent lanes
+per element, each holding one half, the partner's half fetched by DPP and the role taken from the lane number — code the host simulation
+cannot execute.  Both halves of every result are compared, and the first 1, 31, 32, 33 elements are run again on their own (2, 62, 64, 66
+lanes: a lone pair, a pair that ends a wavefront, a wavefront plus one pair)."""
 import os
 import subprocess
 import sys
@@ -41,11 +46,12 @@ if mode == 'family':
             except AssertionError as e:
                 bad.append('lane %d: %s' % (i, e))
         assert not bad, '%s: %d of %d lanes differ\n%s' % (name, len(bad), len(vecs), '\n'.join(bad[:4]))
-        for n in (1, 63, 65):                                  # batch sizes off the wavefront / block size: same lanes, same limbs
+        # batch sizes off the wavefront / block size: same lanes, same limbs (two lanes per element in the two-lane family)
+        for n in ((1, 31, 32, 33) if name[:4] == 'FH2_' else (1, 63, 65)):
             assert run(name, vecs[:n]) == outs[:n], (name, n)
         print('%s: %d vectors' % (name, len(vecs)))
 else:
-    kinds = V.closure(run, 3000)
+    kinds = (V.closure if mode == 'closure' else V.closure_fp2h)(run, 3000)
     assert sum(kinds.values()) == 3000
     print('closure steps:', kinds)
 c.close()
@@ -63,13 +69,17 @@ def child(*args):
     assert r.returncode == 0 and "fp raw ok" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
 
 
-@pytest.mark.parametrize("family", ["product + reduction", "injected reductions", "exact carries", "canonical form and predicates", "Fp2"])
+@pytest.mark.parametrize("family", ["product + reduction", "injected reductions", "exact carries", "canonical form and predicates", "Fp2", "doubling and psi forms", "Fp2, two lanes"])
 def test_raw_limbs_at_the_bounds(family):
     child("family", family)
 
 
 def test_closure_lazy_ops_between_products():
     child("closure")
+
+
+def test_closure_two_lane_fp2_as_the_g2_formulas_mix_them():
+    child("closure_fp2h")
 
 
 def test_product_library_has_no_raw_entry():

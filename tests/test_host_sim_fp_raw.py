@@ -2,6 +2,7 @@
 under the bounds checker (tests/host_sim/fp_raw.cpp, C12381_CHECK_BOUNDS) with operands AT the documented limits (fp_raw_vectors.py),
 each raw result limb compared with plain integer mathematics, each promised post-condition asserted, the bounds the routines declare
 for their results checked against the data.  The device twin is test_gpu_fp_raw.py (same vectors, same expectations).
+The ops FH2_* run the two-lane Fp2 of csrc/fp2h.hpp in its host form (fp2h_from, the per-lane routine once per role, fp2h_to).
 Vectors per op: fp_raw_vectors.COUNTS (asserted at generation; every vector is run, none is skipped)."""
 import ctypes
 import os
@@ -83,6 +84,30 @@ def test_closure_lazy_ops_between_products(sim):
     kinds = V.closure(lambda name, vecs: run_host(sim, name, vecs)[0], 3000)
     print("closure steps:", kinds)
     assert sum(kinds.values()) == 3000 and all(kinds.get(k, 0) > 100 for k in ("ADD", "SUB", "NEG", "MUL", "SQR")) and kinds.get("NORM1", 0) > 0
+
+
+def test_harness_refuses_a_two_lane_square_one_limb_above_its_limit(sim):
+    """fp2h_lane_sqr multiplies (a + b)(a - b): both halves at L(4) = 382999548 sit at the column inequality and run; one more per limb is refused"""
+    L = V.limb_limit(4)
+    status = []
+    for lim in (L, L + 1):
+        o = V.Operand([lim] * 13 + [0])
+        limbs, bnd, k = V.pack("FH2_SQR", [V.Vec([o, o])])
+        out = ctypes.create_string_buffer(112)
+        ob = (ctypes.c_double * 4)()
+        bad = ctypes.c_longlong(-1)
+        status.append((sim.sim_fp_raw_batch(V.OPS["FH2_SQR"], sz(1), limbs, bnd, k, out, ob, ctypes.byref(bad)), bad.value))
+    assert status == [(0, -1), (1, 0)]
+    with pytest.raises(AssertionError):
+        V.assert_precondition("FH2_SQR", V.Vec([o, o]))
+
+
+def test_closure_two_lane_fp2_as_the_g2_formulas_mix_them(sim):
+    kinds = V.closure_fp2h(lambda name, vecs: run_host(sim, name, vecs)[0], 3000)
+    print("closure steps:", kinds)
+    assert sum(kinds.values()) == 3000 and kinds.get("FH2_NORM1", 0) > 0
+    assert all(kinds.get(k, 0) > 100 for k in ("FH2_ADD", "FH2_SUB", "FH2_NEG", "FH2_CONJ", "FH2_DBL", "FH2_MUL_IP", "FH2_MUL_SMALL", "FH2_MUL", "FH2_SQR", "FH2_MUL2_ADD",
+                                               "FH2_MUL2_SUB"))
 
 
 def test_raw_entry_is_exported_by_the_experiments_library_only():
