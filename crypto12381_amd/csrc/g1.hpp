@@ -7,9 +7,12 @@
 // the Renes–Costello–Batina COMPLETE formulas for a = 0 — no exceptional cases, hence no
 // data-dependent branch and no wavefront divergence (P+P, P+(-P), infinity operands and
 // zero digits all go through the same instruction stream) — for the MSM, the additions and the fallback; the batched scalar
-// multiplication runs Jacobian formulas over a co-Z affine table (g1_scalar_mul).  GLV: k = k0 + k1*x^2 with
-// [x^2](x,y) = (beta*x, -y), so both 128-bit halves share ONE table of 16 multiples of P (signed
-// 5-bit windows) that lives in HBM as one contiguous 2816-byte record per lane.
+// multiplication runs Jacobian formulas over a co-Z affine table (g1_scalar_mul_eis).  GLV: k = k0 + k1*x^2 with
+// psi = [x^2] : (x,y) -> (beta*x, -y).  psi^2 - psi + 1 = 0, so k0 + k1 psi is an Eisenstein integer: the single product expands it in
+// base 8 with digits unit x representative — 44 digits over a table of ELEVEN points, the six units psi^u applied for nothing (x -> beta^u x,
+// y -> (-1)^u y) — 129 doublings and 44 additions per scalar.  The k-term sums (g1_scalar_mul_sum) and the complete fallback treat the
+// halves as two 128-bit integers with signed 5-bit windows over ONE table of 16 multiples of P (125 doublings, 52 additions per term).
+// Either table lives in HBM as one contiguous 2816-byte record per lane.
 #pragma once
 #include "fp.hpp"
 
@@ -469,7 +472,7 @@ C12381_HDN void g1_glv_small_scalar_term(g1p& acc, const g1p& base) {
 }
 
 // [k]P for an AFFINE input point (x, y) or infinity with the complete formulas: no exceptional case.  `lane_tab` = this lane's table
-// record (G1_TAB_DWORDS).  Out of line: g1_scalar_mul falls back to it for the rare lanes its incomplete formulas cannot serve, and
+// record (G1_TAB_DWORDS).  Out of line: g1_scalar_mul_eis and g1_scalar_mul fall back to it for the rare lanes its incomplete formulas cannot serve, and
 // the main loop's register allocation does not pay for the second copy.
 C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, bool p_is_inf, const uint32_t (&kin)[8], int32_t* lane_tab) {
     uint32_t kb0[5], kb1[5];
@@ -528,7 +531,7 @@ C12381_HDN void g1_scalar_mul_complete(g1p& acc, const fp& px, const fp& py, boo
     }
 }
 
-// ------------------------------------------------------------------ co-Z affine table (the fast path)
+// ------------------------------------------------------------------ co-Z affine table of 16 multiples (the k-term sums: g1_scalar_mul_sum)
 // Record of entry j: x | y | beta x | 2 pad dwords (44 dwords, as the complete path's X | Y | Z).  The pads of entries 1..7 carry the
 // 14 limbs of Z_T, the shared Z of the table.  While the table is built, entry j holds (X_j, Y_j, h_j) instead: jP on its own Z and the
 // factor h_j that carries Z_j to Z_(j+1).
@@ -594,15 +597,19 @@ C12381_HD void g1j_dbl_window(g1j& a) { g1j_dbl(a); g1j_dbl(a); g1j_dbl(a); g1j_
 
 // acc += sign(d) T[|d|], or its image (beta x, -y) under the endomorphism, given the entry's x (beta x) and y.  d = 0 keeps acc (the
 // addition with entry 1 is computed and dropped); an accumulator at infinity (acc_inf) takes the looked-up point with Z = 1.
+C12381_HD void g1j_add_signed(g1j& acc, bool& acc_inf, const fp& x, const fp& y, bool neg, bool keep);
 C12381_HD void g1j_add_digit(g1j& acc, bool& acc_inf, const fp& x, const fp& y, int d, bool endo) {
+    g1j_add_signed(acc, acc_inf, x, y, (d < 0) != endo, d == 0);
+}
+// acc += (x, -y) if neg, else (x, y); `keep` keeps acc (the addition is computed and dropped)
+C12381_HD void g1j_add_signed(g1j& acc, bool& acc_inf, const fp& x, const fp& y, bool neg, bool keep) {
     fp ny, ys, one;
     fp_neg(ny, y);
-    fp_select(ys, (d < 0) != endo, ny, y);
+    fp_select(ys, neg, ny, y);
     g1j r;
     g1j_madd(r, acc, x, ys);
     fp_one(one);
     fp_select(r.x, acc_inf, x, r.x); fp_select(r.y, acc_inf, ys, r.y); fp_select(r.z, acc_inf, one, r.z);
-    const bool keep = d == 0;
     fp_select(acc.x, keep, acc.x, r.x); fp_select(acc.y, keep, acc.y, r.y); fp_select(acc.z, keep, acc.z, r.z);
     acc_inf = acc_inf && keep;
 }
@@ -622,6 +629,9 @@ C12381_HD bool g1_coz_finish(g1p& acc, const g1j& a, const fp& zc, bool inf) {
     return exc;
 }
 
+// The single product over the 16-entry table: g1_scalar_mul_sum<K>'s schedule for one term, in the form the sum grew from.  The kernels
+// multiply with g1_scalar_mul_eis below; this form stays as the plain statement of the 5-bit schedule, run lane by lane under the bounds
+// checker with its complete-path lanes predicted (tests/host_sim/g1_coz.cpp, tests/g1_torsion.py).
 // [k]P for an AFFINE input point (x, y) or infinity, result in homogeneous coordinates.  `lane_tab` = this lane's table record
 // (G1_TAB_DWORDS).  Returns true for a lane that took the complete path.
 // Jacobian doublings and mixed additions over an affine table: a table whose entries share one Jacobian Z = Z_T is affine on the
@@ -680,10 +690,268 @@ C12381_HD bool g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf
     if (exc) g1_scalar_mul_complete(acc, px, py, p_is_inf, kin, lane_tab);
     return exc;
 }
+// ------------------------------------------------------------------ base-8 Eisenstein digits (the single product: g1_scalar_mul_eis)
+// psi = [x^2] : (x, y) -> (beta x, -y) satisfies psi^2 - psi + 1 = 0 on all of E, so k0 + k1 psi is an Eisenstein integer a + b psi (a pair
+// (a, b) below; psi (a, b) = (-b, a + b)) and the six units psi^u act on an affine point for nothing: x -> beta^u x, y -> (-1)^u y.  Z[psi] / 8
+// has 64 classes; the 63 non-zero ones are unit x representative for ELEVEN representatives (ten orbits of six and the orbit of 4, of three),
+// so a table of eleven points serves every digit of the expansion k = sum_w d_w 8^w, d = rep(k mod 8), k <- (k - d) / 8: six bits of norm per
+// addition against five of the signed 5-bit windows, and a table of 10 co-Z steps against 15.
+// The representatives in chain order: each is the one before plus a unit, so the table is one co-Z chain with a unit image of P as addend.
+constexpr int G1E_TAB = 11;
+constexpr int G1E_DIGITS = 44;      // |k_n| <= |k| / 8^n + max|d| / 7 with |k|^2 < 3 * 2^256, max|d|^2 = 19: k_43 is 0 or a unit (tests/g1_eisenstein.py digit_bound)
+constexpr uint32_t G1E_NONE = 15;   // the entry field of the digit of class 0: no addition
+constexpr int EIS_REPS[G1E_TAB][2] = {{1, 0}, {2, -1}, {2, -2}, {2, -3}, {1, -3}, {0, -3}, {1, -4}, {2, -4}, {3, -5}, {3, -4}, {4, -4}};
+struct eis_z { int a, b; };
+constexpr eis_z eis_mul_unit(eis_z z, int u) {
+    for (int i = 0; i < u; ++i) z = eis_z{-z.b, z.a + z.b};
+    return z;
+}
+// u with REPS[i + 1] - REPS[i] = psi^u, or -1
+constexpr int eis_chain_unit(int i) {
+    for (int u = 0; u < 6; ++u) {
+        const eis_z w = eis_mul_unit(eis_z{1, 0}, u);
+        if (EIS_REPS[i + 1][0] - EIS_REPS[i][0] == w.a && EIS_REPS[i + 1][1] - EIS_REPS[i][1] == w.b) return u;
+    }
+    return -1;
+}
+// step i of the chain adds psi^(u_i) P; the running addend is carried from one step to the next through psi^(u_i - u_(i-1)) (u_(-1) = 0: P
+// itself).  Three bits per step.
+constexpr uint32_t eis_chain_deltas() {
+    uint32_t v = 0;
+    int prev = 0;
+    for (int i = 0; i + 1 < G1E_TAB; ++i) {
+        const int u = eis_chain_unit(i);
+        v |= (uint32_t)((u - prev + 6) % 6) << (3 * i);
+        prev = u;
+    }
+    return v;
+}
+constexpr bool eis_chain_ok() {
+    for (int i = 0; i + 1 < G1E_TAB; ++i) if (eis_chain_unit(i) < 0) return false;
+    return eis_chain_unit(G1E_TAB - 2) == 0;             // the addend ends as P itself: entry 0 on the table's Z
+}
+static_assert(eis_chain_ok(), "the representatives are not a chain of unit steps that ends on +P");
+constexpr uint32_t EIS_CHAIN_DELTAS = eis_chain_deltas();
+// class (a mod 8) + 8 (b mod 8) -> entry (bits 0..3, G1E_NONE for the class of 0) | unit (bits 4..6) | da < 0 (bit 7) | db < 0 (bit 8) of its
+// representative d = psi^unit REPS[entry].  The low seven bits are the digit as the loop reads it.  Both coefficients of every d lie in
+// [-5, 5], so (c - dc) / 8 = (c >> 3) + (dc < 0) for a coefficient c >= 0, which therefore stays >= 0: the recoder is unsigned.
+struct eis_classes { uint16_t v[64]; };
+constexpr eis_classes eis_make_classes() {
+    eis_classes t{};
+    for (int c = 0; c < 64; ++c) t.v[c] = 0xffff;
+    t.v[0] = (uint16_t)G1E_NONE;
+    for (int e = 0; e < G1E_TAB; ++e)
+        for (int u = 0; u < 6; ++u) {
+            const eis_z d = eis_mul_unit(eis_z{EIS_REPS[e][0], EIS_REPS[e][1]}, u);
+            const int c = (d.a & 7) + 8 * (d.b & 7);
+            if (t.v[c] == 0xffff && d.a >= -5 && d.a <= 5 && d.b >= -5 && d.b <= 5)
+                t.v[c] = (uint16_t)(e | (u << 4) | ((d.a < 0 ? 1 : 0) << 7) | ((d.b < 0 ? 1 : 0) << 8));
+        }
+    return t;
+}
+constexpr bool eis_classes_ok(const eis_classes& t) {
+    for (int c = 0; c < 64; ++c) if (t.v[c] == 0xffff) return false;
+    return true;
+}
+C12381_CONST eis_classes EIS_CLASSES = eis_make_classes();
+static_assert(eis_classes_ok(eis_make_classes()), "a class mod 8 without a representative");
+
+// c <- (c >> 3) + t
+C12381_HD void eis_next(uint32_t (&c)[4], uint32_t t) {
+    uint64_t s = t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { s += (c[i] >> 3) | (i < 3 ? c[i + 1] << 29 : 0u); c[i] = (uint32_t)s; s >>= 32; }
+}
+// k0 + k1 psi (k0, k1 < 2^128) -> its G1E_DIGITS digits of seven bits in ten dwords, the TOP digit lowest (digit w in bits 7 (43 - w) ...):
+// the loop reads the low seven bits and shifts.  A number that ends early is padded with digits of class 0.
+C12381_HD void eis_recode(uint32_t (&kd)[10], const uint32_t (&k0)[4], const uint32_t (&k1)[4]) {
+    uint32_t a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { a[i] = k0[i]; b[i] = k1[i]; }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) kd[i] = 0;
+#pragma unroll
+    for (int n = 0; n < G1E_DIGITS; ++n) {
+        const uint32_t e = EIS_CLASSES.v[(a[0] & 7u) | ((b[0] & 7u) << 3)];
+        const int pos = 7 * (G1E_DIGITS - 1 - n), word = pos >> 5, sh = pos & 31;
+        kd[word] |= (e & 127u) << sh;
+        if (sh > 25) kd[word + 1] |= (e & 127u) >> (32 - sh);
+        eis_next(a, (e >> 7) & 1u);
+        eis_next(b, (e >> 8) & 1u);
+    }
+}
+// scalar words (any value < 2^256) -> the digits of k mod r = k0 + k1 x^2
+C12381_HD void eis_scalar_digits(uint32_t (&kd)[10], const uint32_t (&kin)[8]) {
+    uint32_t k[8], k0[4], k1[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = kin[i];
+    scalar_mod_r(k);
+    scalar_glv_split(k0, k1, k);
+    eis_recode(kd, k0, k1);
+}
+// the next digit: the low seven bits, and the string moves down
+C12381_HD uint32_t eis_pop_digit(uint32_t (&kd)[10]) {
+    const uint32_t d = kd[0] & 127u;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) kd[i] = (kd[i] >> 7) | (i < 9 ? kd[i + 1] << 25 : 0u);
+    return d;
+}
+
+// Record of entry e (REPS[e] P on the table's Z_T): y | x | beta x | beta^2 x, each field 14 limbs padded to 16 dwords: 256 B, two 128-byte
+// lines, eleven entries = G1_TAB_DWORDS.  An addition reads y and ONE x field, aligned 16-byte accesses.  While the table is built, entry i
+// holds (Y_i, X_i, h_i) in its first three fields: the point on its own Z_i and the factor that carries Z_i to Z_(i+1).  Z_T lies in the
+// pads of the y fields of entries 0..6, written last.
+constexpr int G1E_FIELD = 16;
+constexpr int G1E_ENT_DWORDS = 4 * G1E_FIELD;
+static_assert(G1E_TAB * G1E_ENT_DWORDS == G1_TAB_DWORDS, "the Eisenstein table fills the lane's record of the 16-entry table");
+C12381_HD void eis_store_field(int32_t* ent, int f, const fp& a, double vb_cap) {
+    (void)vb_cap;
+    C12381_BOUNDS(if (a.vb > vb_cap) bounds_fail("eis_store_field value bound", a.vb, vb_cap);
+                  if (a.lb > G1_REC_LB) bounds_fail("eis_store_field limb bound", a.lb, G1_REC_LB);)
+    int32_t w[G1E_FIELD];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) w[i] = a.l[i];
+    w[14] = 0; w[15] = 0;
+    rec_store_q4<0, G1E_FIELD / 4>(reinterpret_cast<q4*>(ent + f * G1E_FIELD), w);
+}
+C12381_HD void eis_load_field(fp& a, const int32_t* ent, int f, double vb_cap) {
+    int32_t w[G1E_FIELD];
+    rec_load_q4<0, G1E_FIELD / 4>(w, reinterpret_cast<const q4*>(ent + f * G1E_FIELD));
+#pragma unroll
+    for (int i = 0; i < NL; ++i) a.l[i] = w[i];
+    (void)vb_cap;
+    C12381_BOUNDS(a.lb = G1_REC_LB; a.vb = vb_cap; check_actual(a, "eis_load_field");)
+}
+C12381_HD void eis_store_zt(int32_t* lane_tab, const fp& zt) {
+#pragma unroll
+    for (int j = 0; j < NL / 2; ++j) { d2 t; t.v[0] = zt.l[2 * j]; t.v[1] = zt.l[2 * j + 1]; *reinterpret_cast<d2*>(lane_tab + j * G1E_ENT_DWORDS + NL) = t; }
+}
+C12381_HD void eis_load_zt(fp& zt, const int32_t* lane_tab) {
+#pragma unroll
+    for (int j = 0; j < NL / 2; ++j) { const d2 t = *reinterpret_cast<const d2*>(lane_tab + j * G1E_ENT_DWORDS + NL); zt.l[2 * j] = t.v[0]; zt.l[2 * j + 1] = t.v[1]; }
+    C12381_BOUNDS(zt.lb = G1_REC_LB; zt.vb = 4.0; check_actual(zt, "eis_load_zt");)
+}
+// what the addition of digit `code` reads: y and beta^(unit mod 3) x of its entry (entry 0 for the digit of class 0, dropped afterwards),
+// requested here and not later (g1_sched_fence)
+C12381_HD void eis_fetch(fp& x, fp& y, const int32_t* lane_tab, uint32_t code) {
+    const uint32_t e = code & 15u, u = code >> 4;
+    const int32_t* ent = lane_tab + (e >= (uint32_t)G1E_TAB ? 0u : e) * G1E_ENT_DWORDS;
+    eis_load_field(y, ent, 0, 4.0);
+    eis_load_field(x, ent, 1 + (int)(u >= 3u ? u - 3u : u), 4.0);
+    g1_sched_fence();
+}
+// acc += psi^unit T[entry]: the sign of y is (-1)^unit
+C12381_HD void g1j_add_eis(g1j& acc, bool& acc_inf, const fp& x, const fp& y, uint32_t code) {
+    g1j_add_signed(acc, acc_inf, x, y, ((code >> 4) & 1u) != 0u, (code & 15u) == G1E_NONE);
+}
+
+// Forward co-Z pass: ten ZADDUs.  Step i adds the running addend psi^(u_i) P to entry i (entry 0 = P on Z_0 = 1) and gives entry i + 1 and the
+// addend on Z_(i+1) = Z_i h_i; between two steps the addend passes through a unit (one product by beta or beta^2 where u_i - u_(i-1) is no
+// multiple of 3, a sign on y).  Leaves entries 0..9 as (Y_i, X_i, h_i), entry 10 finished, and fields y, x, beta^2 x of entry 0 finished
+// from the last addend, which is P on Z_10 = Z_T = h_0 ... h_9; h_0 stays in entry 0 until the backward pass has run.
+C12381_HD void g1e_forward(int32_t* lane_tab, const fp& px, const fp& py, const fp& beta, const fp& beta2) {
+    fp x1 = px, y1 = py, xj = px, yj = py, xn, yn, h, hn, bx;
+#pragma unroll 1
+    for (int i = 0; i + 1 < G1E_TAB; ++i) {
+        const uint32_t dl = (EIS_CHAIN_DELTAS >> (3 * i)) & 7u, m = dl >= 3u ? dl - 3u : dl;       // wave-uniform
+        if (m != 0u) {
+            fp bm;
+            fp_select(bm, m == 2u, beta2, beta);
+            fp_mul(x1, x1, bm);
+        }
+        if (dl & 1u) fp_neg(y1, y1);
+        g1j_zaddu(xn, yn, x1, y1, h, xj, yj);
+        fp_norm1(hn, h);
+        int32_t* ent = lane_tab + i * G1E_ENT_DWORDS;
+        eis_store_field(ent, 0, yj, 32.0); eis_store_field(ent, 1, xj, 32.0); eis_store_field(ent, 2, hn, 32.0);
+        xj = xn; yj = yn;
+    }
+    int32_t* last = lane_tab + (G1E_TAB - 1) * G1E_ENT_DWORDS;
+    eis_store_field(last, 0, yj, 4.0); eis_store_field(last, 1, xj, 4.0);
+    fp_mul(bx, xj, beta); eis_store_field(last, 2, bx, 4.0);
+    fp_mul(bx, xj, beta2); eis_store_field(last, 3, bx, 4.0);
+    eis_store_field(lane_tab, 0, y1, 4.0); eis_store_field(lane_tab, 1, x1, 4.0);
+    fp_mul(bx, x1, beta2); eis_store_field(lane_tab, 3, bx, 4.0);
+}
+// One step of the backward pass: mu <- mu h_i (mu = h_i where the chain starts: `first`, wave-uniform), and entry i = (Y_i, X_i, h_i) becomes
+// the finished record of the point on Z_i mu.
+C12381_HD void g1e_backward(int32_t* ent, fp& mu, bool first, const fp& beta, const fp& beta2) {
+    fp m2, m3, x, y, h, bx;
+    eis_load_field(y, ent, 0, 32.0); eis_load_field(x, ent, 1, 32.0); eis_load_field(h, ent, 2, 32.0);
+    if (first) mu = h; else fp_mul(mu, mu, h);
+    fp_sqr(m2, mu);
+    fp_mul(m3, m2, mu);
+    fp_mul(x, x, m2);
+    fp_mul(y, y, m3);
+    eis_store_field(ent, 0, y, 4.0); eis_store_field(ent, 1, x, 4.0);
+    fp_mul(bx, x, beta); eis_store_field(ent, 2, bx, 4.0);
+    fp_mul(bx, x, beta2); eis_store_field(ent, 3, bx, 4.0);
+}
+
+// [k]P for an AFFINE input point (x, y) or infinity, result in homogeneous coordinates.  `lane_tab` = this lane's table record
+// (G1_TAB_DWORDS).  Returns true for a lane that took the complete path.
+// Jacobian doublings and mixed additions over an affine table: a table whose entries share one Jacobian Z = Z_T is affine on the
+// isomorphic curve E': y^2 = x^3 + 4 Z_T^6 ((x, y) -> (Z_T^2 x, Z_T^3 y)); the loop runs there (its formulas never read b), and
+// (X : Y : Z) on E' is (X : Y : Z Z_T) on E.  The endomorphism commutes with the map (beta Z^2 x = Z^2 beta x).  Co-Z additions
+// (Meloni) give the shared Z without an inversion: ten ZADDUs, and one backward pass that carries entry i from Z_i to Z_T.
+// Schedule: the top digit seeds the accumulator, then 43 windows of three doublings and one mixed addition: 129 doublings and 44 additions
+// per scalar (the 5-bit windows of the two halves, which g1_scalar_mul and g1_scalar_mul_sum run: 125 and 52, over a table of 15 steps).
+// The formulas are incomplete: an addition with acc = +-T, or a ZADDU whose operands coincide (points of small order: beta x = x on the
+// points of order 3), gives Z = 0, and Z = 0 survives every later step.  So one test at the end suffices: a lane whose final Z is 0 mod p
+// while the accumulator is not the point at infinity recomputes its product with g1_scalar_mul_complete.  No lane of a random subgroup
+// batch does.
+C12381_HD bool g1_scalar_mul_eis(g1p& acc, const fp& px, const fp& py, bool p_is_inf, const uint32_t (&kin)[8], int32_t* lane_tab) {
+    uint32_t kd[10];
+    eis_scalar_digits(kd, kin);
+
+    fp beta, beta2;
+    fp_set_const(beta, FP_BETA_A);
+    fp_set_const(beta2, FP_BETA_B);                             // beta^2, the other cube root of unity
+    g1e_forward(lane_tab, px, py, beta, beta2);
+    {   // backward pass: entry i times mu_i^2, mu_i^3 with mu_i = h_i ... h_9 = Z_T / Z_i; Z_T = h_0 mu_1
+        fp mu, zt, h0, x, bx;
+#pragma unroll 1
+        for (int i = G1E_TAB - 2; i >= 1; --i) g1e_backward(lane_tab + i * G1E_ENT_DWORDS, mu, i == G1E_TAB - 2, beta, beta2);
+        eis_load_field(h0, lane_tab, 2, 32.0);
+        eis_load_field(x, lane_tab, 1, 4.0);
+        fp_mul(zt, mu, h0);
+        fp_mul(bx, x, beta);
+        eis_store_field(lane_tab, 2, bx, 4.0);
+        eis_store_zt(lane_tab, zt);
+    }
+
+    // the top digit starts the accumulator with its point (Z = 1)
+    g1j a;
+    bool acc_inf;
+    {
+        const uint32_t code = eis_pop_digit(kd);
+        fp x, y, ny;
+        eis_fetch(x, y, lane_tab, code);
+        fp_neg(ny, y);
+        a.x = x;
+        fp_select(a.y, ((code >> 4) & 1u) != 0u, ny, y);
+        fp_one(a.z);
+        acc_inf = (code & 15u) == G1E_NONE;
+    }
+#pragma unroll 1
+    for (int w = G1E_DIGITS - 2; w >= 0; --w) {
+        const uint32_t code = eis_pop_digit(kd);
+        fp x, y;
+        eis_fetch(x, y, lane_tab, code);
+        g1j_dbl(a); g1j_dbl(a); g1j_dbl(a);
+        g1j_add_eis(a, acc_inf, x, y, code);
+    }
+
+    fp zt;
+    eis_load_zt(zt, lane_tab);
+    const bool exc = g1_coz_finish(acc, a, zt, acc_inf || p_is_inf);
+    if (exc) g1_scalar_mul_complete(acc, px, py, p_is_inf, kin, lane_tab);
+    return exc;
+}
 // ------------------------------------------------------------------ sum of K products under one doubling chain
 // sum_j [k_j]P_j per lane (the reference fuses g^x * h^y the same way: double_multiply -> ECP_mul2): K co-Z tables, ONE accumulator, per
-// window 5 doublings and 2K mixed additions.  `lane_tab` = K consecutive table records (K * G1_TAB_DWORDS); table j is built exactly as
-// g1_scalar_mul builds it, on its own Z_T,j.  The mixed additions need every entry affine on ONE curve y^2 = x^3 + 4 Z^6, so the
+// window 5 doublings and 2K mixed additions.  `lane_tab` = K consecutive table records (K * G1_TAB_DWORDS); table j is the 16-entry co-Z
+// table of signed 5-bit windows (g1_coz_forward: DBLU and fourteen ZADDUs), on its own Z_T,j.  The mixed additions need every entry affine on ONE curve y^2 = x^3 + 4 Z^6, so the
 // backward pass of table j starts its mu chain from f_j = prod_(l != j) Z_T,l instead of from 1: all tables land on Z = prod_j Z_T,j
 // without an inversion, and the end of the loop multiplies by that Z once.  Per table this costs 14 products for Z_T,j ahead of the
 // backward pass and 8 for entries 16 and 1, which the single table leaves as they are.
@@ -692,7 +960,7 @@ C12381_HD bool g1_scalar_mul(g1p& acc, const fp& px, const fp& py, bool p_is_inf
 // cancel to infinity), not only for torsion points.  Every such case leaves Jacobian Z = 0 (Z3 = Z1 H with H = 0; no point has order 2, so
 // a doubling never does), Z = 0 is absorbing, and a degenerate table has Z_T,j = 0: the one test at the end still suffices, and the lane
 // recomputes its K products with g1_scalar_mul_complete and adds them with the complete formulas.
-// The pads of entries 1..7 of each record carry Z_T,j as in the single table, those of entries 8..12 the ten biased digit words of the term
+// The pads of entries 1..7 of each record carry Z_T,j (tab_store_zt), those of entries 8..12 the ten biased digit words of the term
 // between the table passes (a loop over the terms, so the table code exists once per kernel; the main loop holds all 2K x 5 words in registers).
 C12381_HD void tab_store_kb(int32_t* lane_tab, const uint32_t (&kb0)[5], const uint32_t (&kb1)[5]) {
 #pragma unroll
@@ -755,7 +1023,7 @@ C12381_HD bool g1_scalar_mul_sum(g1p& acc, const In& in, int32_t* lane_tab) {
                 tab_store_rec<true>(ent, x, y, bx, 4.0);
             }
         }
-        // entry j times mu_j^2, mu_j^3 with mu_j = f_t h_j ... h_15; a single table (K = 1) has f_t = 1 and starts its chain as g1_scalar_mul does
+        // entry j times mu_j^2, mu_j^3 with mu_j = f_t h_j ... h_15; a single table (K = 1) has f_t = 1 and starts its chain from h_15
 #pragma unroll 1
         for (int j = G1_TAB - 1; j >= 2; --j) g1_coz_backward<true>(tab + (j - 1) * G1_ENT_DWORDS, mu, K == 1 && j == G1_TAB - 1, beta);
     }

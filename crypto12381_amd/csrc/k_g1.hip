@@ -1,6 +1,6 @@
 // Kernels of the Fp / G1 family (one element per lane):
 //   fp_op_kernel / fp_mulchain_kernel   Fp test + VALU-roofline hook
-//   g1_mul_kernel      bytes -> on-curve check -> GLV windowed [k]P -> projective SoA in HBM
+//   g1_mul_kernel      bytes -> on-curve check -> [k]P in base-8 Eisenstein digits of the GLV split (g1_scalar_mul_eis) -> projective SoA in HBM
 //   g1_add_kernel      complete addition of two affine inputs -> projective SoA
 //   g1_finish_kernel   Montgomery's simultaneous inversion over a strided chunk per lane,
 //                      affine conversion, canonical encoding (49 B / 96 B)
@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(BLOCK, G1_OCC) g1_mul_kernel(size_t n, const u
     load_raw32(raw, scalars + 32 * i);
     scalar_from_raw32(k, raw);
     g1p acc;
-    g1_scalar_mul(acc, px, py, inf || !ok, k, tab + i * (size_t)G1_TAB_DWORDS);
+    g1_scalar_mul_eis(acc, px, py, inf || !ok, k, tab + i * (size_t)G1_TAB_DWORDS);
     // the reference's [r]phi(P) term of scalars below x^2 (g1.hpp): no lane of a batch of random scalars, and then one that keeps its
     // wavefront for the length of a second scalar multiplication.  In a launch of several machine rounds that wavefront's workgroup
     // simply leaves later while others take the free slots; a separate fix-up launch behind the kernel (rounds 1-3) costs its full
