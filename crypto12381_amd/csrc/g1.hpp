@@ -10,7 +10,7 @@
 // multiplication runs Jacobian formulas over a co-Z affine table (g1_scalar_mul_eis).  GLV: k = k0 + k1*x^2 with
 // psi = [x^2] : (x,y) -> (beta*x, -y).  psi^2 - psi + 1 = 0, so k0 + k1 psi is an Eisenstein integer: the single product expands it in
 // base 8 with digits unit x representative — 44 digits over a table of ELEVEN points, the six units psi^u applied for nothing (x -> beta^u x,
-// y -> (-1)^u y) — 129 doublings and 44 additions per scalar.  The k-term sums (g1_scalar_mul_sum) and the complete fallback treat the
+// y -> (-1)^u y) — the top two digits as one seed, then 126 doublings and 42 additions per scalar.  The k-term sums (g1_scalar_mul_sum) and the complete fallback treat the
 // halves as two 128-bit integers with signed 5-bit windows over ONE table of 16 multiples of P (125 doublings, 52 additions per term).
 // Either table lives in HBM as one contiguous 2816-byte record per lane.
 #pragma once
@@ -755,6 +755,23 @@ constexpr bool eis_classes_ok(const eis_classes& t) {
 }
 C12381_CONST eis_classes EIS_CLASSES = eis_make_classes();
 static_assert(eis_classes_ok(eis_make_classes()), "a class mod 8 without a representative");
+// the seven-bit digit whose representative IS (a, b), not merely congruent to it mod 8; 0xff where the table's digit of that class is another
+constexpr uint32_t eis_exact_code(int a, int b) {
+    const uint32_t c = eis_make_classes().v[(a & 7) + 8 * (b & 7)] & 127u;
+    if ((c & 15u) >= (uint32_t)G1E_TAB) return 0xffu;
+    const eis_z d = eis_mul_unit(eis_z{EIS_REPS[c & 15u][0], EIS_REPS[c & 15u][1]}, (int)(c >> 4));
+    return d.a == a && d.b == b ? c : 0xffu;
+}
+// The top two digits.  What is left of k0 + k1 psi after 42 digits is t = 8 d_43 + d_42 with both coefficients in 0..3 (a coefficient c
+// becomes at most (c + 5) / 8 per digit: c_42 <= 2.6918 + 5/7).  Fourteen of those sixteen are nothing or a digit themselves (unit x
+// representative exactly), and then position 43 is empty.  The other two are a digit plus one: (3, 2) = (2, 2) + 1, recoded as
+// d_42 = (-5, 2) under d_43 = 1, and (3, 3) = (2, 3) + 1, recoded as d_42 = (3, -5) under d_43 = psi (tests/test_g1_eisenstein_seed.py).
+constexpr uint32_t EIS_TOP_ONE = eis_exact_code(1, 0), EIS_TOP_PSI = eis_exact_code(0, 1);
+constexpr uint32_t EIS_LOW_ONE = eis_exact_code(-5, 2), EIS_LOW_PSI = eis_exact_code(3, -5);
+constexpr uint32_t EIS_SEED_ONE = eis_exact_code(2, 2), EIS_SEED_PSI = eis_exact_code(2, 3);
+static_assert(EIS_TOP_ONE == 0u && EIS_TOP_PSI == 16u, "1 and psi are not entry 0 under the units 0 and 1");
+static_assert(EIS_LOW_ONE != 0xffu && EIS_LOW_PSI != 0xffu, "the digits under a non-empty top position are not (-5, 2) and (3, -5)");
+static_assert(EIS_SEED_ONE != 0xffu && EIS_SEED_PSI != 0xffu, "the table does not hold (2, 2) and (2, 3) themselves");
 
 // c <- (c >> 3) + t
 C12381_HD void eis_next(uint32_t (&c)[4], uint32_t t) {
@@ -887,6 +904,23 @@ C12381_HD void g1e_backward(int32_t* ent, fp& mu, bool first, const fp& beta, co
     fp_mul(bx, x, beta); eis_store_field(ent, 2, bx, 4.0);
     fp_mul(bx, x, beta2); eis_store_field(ent, 3, bx, 4.0);
 }
+// r = (x1, y1) + (x2, y2), both affine on the table's curve: g1j_madd with Z1 = 1, 4M + 2S in five reductions, Z3 = x2 - x1.  Exceptional
+// (Z3 = 0) when the operands are equal or opposite.
+C12381_HD void g1e_add_affine(g1j& r, const fp& x1, const fp& y1, const fp& x2, const fp& y2) {
+    fp h, s, hh, hhh, v, x3, y3, vx;
+    const int32_t cm1 = fp_opaque_const(-1), cm2 = fp_opaque_const(-2);
+    fp_sub(h, x2, x1);                                   // H = x2 - x1
+    fp_sub(s, y2, y1);                                   // s = y2 - y1
+    fp_sqr(hh, h);
+    fp_mul(hhh, h, hh);
+    fp_mul(v, x1, hh);                                   // V = x1 H^2
+    fp_sqr_inj(x3, s, [&](int i, int64_t& acc) { fp_inj(acc, hhh, i, cm1); fp_inj(acc, v, i, cm2); },
+               C12381_BV(hhh.vb + 2 * v.vb), C12381_BV(hhh.lb + 2 * v.lb));         // X3 = s^2 - H^3 - 2V
+    fp_sub(vx, v, x3);
+    fp_mul2<true>(y3, s, vx, y1, hhh);                   // Y3 = s (V - X3) - y1 H^3
+    r.x = x3; r.y = y3;
+    fp_norm1(r.z, h);
+}
 
 // [k]P for an AFFINE input point (x, y) or infinity, result in homogeneous coordinates.  `lane_tab` = this lane's table record
 // (G1_TAB_DWORDS).  Returns true for a lane that took the complete path.
@@ -894,8 +928,10 @@ C12381_HD void g1e_backward(int32_t* ent, fp& mu, bool first, const fp& beta, co
 // isomorphic curve E': y^2 = x^3 + 4 Z_T^6 ((x, y) -> (Z_T^2 x, Z_T^3 y)); the loop runs there (its formulas never read b), and
 // (X : Y : Z) on E' is (X : Y : Z Z_T) on E.  The endomorphism commutes with the map (beta Z^2 x = Z^2 beta x).  Co-Z additions
 // (Meloni) give the shared Z without an inversion: ten ZADDUs, and one backward pass that carries entry i from Z_i to Z_T.
-// Schedule: the top digit seeds the accumulator, then 43 windows of three doublings and one mixed addition: 129 doublings and 44 additions
+// Schedule: the top TWO digits seed the accumulator, then 42 windows of three doublings and one mixed addition: 126 doublings and 42 additions
 // per scalar (the 5-bit windows of the two halves, which g1_scalar_mul and g1_scalar_mul_sum run: 125 and 52, over a table of 15 steps).
+// The seed is [8 d_43 + d_42]P: the point of digit 42 where position 43 is empty, else T[(2, 2)] + P or T[(2, 3)] + P (EIS_SEED_ONE,
+// EIS_SEED_PSI above), one affine + affine addition that every lane computes and those lanes keep.
 // The formulas are incomplete: an addition with acc = +-T, or a ZADDU whose operands coincide (points of small order: beta x = x on the
 // points of order 3), gives Z = 0, and Z = 0 survives every later step.  So one test at the end suffices: a lane whose final Z is 0 mod p
 // while the accumulator is not the point at infinity recomputes its product with g1_scalar_mul_complete.  No lane of a random subgroup
@@ -920,21 +956,27 @@ C12381_HD bool g1_scalar_mul_eis(g1p& acc, const fp& px, const fp& py, bool p_is
         eis_store_zt(lane_tab, zt);
     }
 
-    // the top digit starts the accumulator with its point (Z = 1)
+    // the top two digits start the accumulator: the point of digit 42 (Z = 1), or a table point plus P where position 43 is not empty
     g1j a;
     bool acc_inf;
     {
-        const uint32_t code = eis_pop_digit(kd);
-        fp x, y, ny;
+        const uint32_t top = eis_pop_digit(kd), low = eis_pop_digit(kd);
+        const bool two = (top & 15u) != G1E_NONE;
+        C12381_BOUNDS(if (two && !(top == EIS_TOP_ONE && low == EIS_LOW_ONE) && !(top == EIS_TOP_PSI && low == EIS_LOW_PSI))
+                          bounds_fail("the top two digits are no pair the seed knows", top, low);)
+        const uint32_t code = two ? (top == EIS_TOP_ONE ? EIS_SEED_ONE : EIS_SEED_PSI) : low;
+        fp x, y, ny, ys, x0, y0, one;
+        eis_load_field(y0, lane_tab, 0, 4.0); eis_load_field(x0, lane_tab, 1, 4.0);
         eis_fetch(x, y, lane_tab, code);
         fp_neg(ny, y);
-        a.x = x;
-        fp_select(a.y, ((code >> 4) & 1u) != 0u, ny, y);
-        fp_one(a.z);
+        fp_select(ys, ((code >> 4) & 1u) != 0u, ny, y);
+        g1e_add_affine(a, x, ys, x0, y0);
+        fp_one(one);
+        fp_select(a.x, two, a.x, x); fp_select(a.y, two, a.y, ys); fp_select(a.z, two, a.z, one);
         acc_inf = (code & 15u) == G1E_NONE;
     }
 #pragma unroll 1
-    for (int w = G1E_DIGITS - 2; w >= 0; --w) {
+    for (int w = G1E_DIGITS - 3; w >= 0; --w) {
         const uint32_t code = eis_pop_digit(kd);
         fp x, y;
         eis_fetch(x, y, lane_tab, code);

@@ -1,6 +1,7 @@
 // Kernels of the Fp / G1 family (one element per lane):
 //   fp_op_kernel / fp_mulchain_kernel   Fp test + VALU-roofline hook
-//   g1_mul_kernel      bytes -> on-curve check -> [k]P in base-8 Eisenstein digits of the GLV split (g1_scalar_mul_eis) -> projective SoA in HBM
+//   g1_mul_kernel      bytes -> on-curve check -> [k]P in base-8 Eisenstein digits of the GLV split (g1_scalar_mul_eis: the top two digits seed
+//                      the accumulator, 42 windows follow) -> projective SoA in HBM
 //   g1_add_kernel      complete addition of two affine inputs -> projective SoA
 //   g1_finish_kernel   Montgomery's simultaneous inversion over a strided chunk per lane,
 //                      affine conversion, canonical encoding (49 B / 96 B)
