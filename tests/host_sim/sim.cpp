@@ -422,6 +422,13 @@ extern "C" int sim_gs_split(const uint8_t* scalar32, uint32_t* u8) {
     for (int i = 0; i < 4; ++i) { u8[2 * i] = u[i][0]; u8[2 * i + 1] = u[i][1]; }
     return 0;
 }
+// the width, the number of windows and the per-lane cap of a product of n terms (tests/msm_cases.py restates them)
+extern "C" int sim_msm_params(size_t n, int* c, int* W, uint32_t* cap) {
+    *c = msm_window_bits(n);
+    *W = msm_windows(*c);
+    *cap = msm_run_cap(n, *c);
+    return 0;
+}
 extern "C" int sim_g1_msm_pippenger(size_t n, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out, int fmt, int force_c) {
     const int c = force_c > 0 ? force_c : msm_window_bits(n);
     const int W = msm_windows(c);
