@@ -65,15 +65,19 @@ void* worker(void* arg) {
     }
     return nullptr;
 }
-}  // namespace
-
-extern "C" {
-
-// out[i] = conj(prod_{c < K} Miller(g1s[c*n + i], g2s[c])) with the lines of g2s[c] from miller_lines_precompute (raw records when
-// raw != 0, else normalised); G1 points as the prep kernel stores them (all-zero bytes = infinity, skipped).  step: iterations per
-// task (1 .. 64); single = c + 1: column c alone.
-int sim_fixedk_miller(size_t n, int K, const uint8_t* g1s, const uint8_t* g2s, int raw, int step, int single, uint8_t* out576) {
-    if (K < 1 || step < 1 || step > 64) return -1;
+bool on_curve(const fp& x, const fp& y) {            // kernels_common.hpp g1_on_curve
+    fp x2, x3, y2, four, rhs;
+    fp_sqr(x2, x); fp_mul(x3, x2, x);
+    fp_set_const(four, FP_FOUR);
+    fp_add(rhs, x3, four);
+    fp_sqr(y2, y);
+    return fp_equal(y2, rhs);
+}
+// tables, point records and mask word, then the three lanes.  prep: the records as pairk_prep_kernel writes them (see below); otherwise
+// all-zero bytes = infinity and nothing else is looked at.
+int run_fixedk(size_t n, int K, const uint8_t* g1s, const uint8_t* g2s, uint32_t neg_mask, bool prep, int raw, int step, int single,
+               uint8_t* out576, uint32_t* mask_out) {
+    if (K < 1 || K > 31 || step < 1 || step > 64) return -1;
     std::vector<int32_t> tabv((size_t)K * TAB_STRIDE + 4), ptsv((size_t)K * n * FQK_PT_DWORDS + 4);
     int32_t* tabs = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(tabv.data()) + 15) & ~(uintptr_t)15);
     int32_t* pts = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(ptsv.data()) + 15) & ~(uintptr_t)15);
@@ -91,7 +95,13 @@ int sim_fixedk_miller(size_t n, int K, const uint8_t* g1s, const uint8_t* g2s, i
             std::memcpy(rp, g1s + 96 * ((size_t)c * n + i), 96);
             fp x, y;
             fp_from_raw48(x, rp); fp_from_raw48(y, rp + 12);
-            if (raw_all_zero(rp, 24)) mask[i] |= 1u << c;
+            const bool inf = raw_all_zero(rp, 24);
+            if (prep) {
+                const bool ok = inf || on_curve(x, y);
+                if ((neg_mask >> c) & 1u) { fp ny; fp_neg(ny, y); fp_norm1(y, ny); }
+                if (!ok) mask[i] |= 0x80000000u;
+                if (!ok || inf) mask[i] |= 1u << c;
+            } else if (inf) mask[i] |= 1u << c;
             fqk_store_pt(pts + ((size_t)c * n + i) * FQK_PT_DWORDS, x, y);
         }
     }
@@ -104,7 +114,27 @@ int sim_fixedk_miller(size_t n, int K, const uint8_t* g1s, const uint8_t* g2s, i
     }
     for (int r = 0; r < 3; ++r) pthread_join(th[r], nullptr);
     pthread_barrier_destroy(&box.bar);
+    if (mask_out) std::memcpy(mask_out, mask.data(), n * sizeof(uint32_t));
     return 0;
+}
+}  // namespace
+
+extern "C" {
+
+// out[i] = conj(prod_{c < K} Miller(g1s[c*n + i], g2s[c])) with the lines of g2s[c] from miller_lines_precompute (raw records when
+// raw != 0, else normalised); G1 points as the prep kernel stores them (all-zero bytes = infinity, skipped).  step: iterations per
+// task (1 .. 64); single = c + 1: column c alone.
+int sim_fixedk_miller(size_t n, int K, const uint8_t* g1s, const uint8_t* g2s, int raw, int step, int single, uint8_t* out576) {
+    return run_fixedk(n, K, g1s, g2s, 0, false, raw, step, single, out576, nullptr);
+}
+
+// The same loop behind the records of pairk_prep_kernel (k_pairk.hip), restated for the host: every G1 argument parsed and tested against
+// the curve equation, py negated (pair_queue.hpp fp_negate) for the columns in neg_mask, mask_out[i] bit c = column c is at infinity or off
+// the curve, bit 31 = some column of element i is off the curve.  pair_out writes 0xff over such an element; here its value stays, so that a test
+// can see that the off-curve column was skipped (its record is not zero).
+int sim_fixedk_prep_miller(size_t n, int K, const uint8_t* g1s, const uint8_t* g2s, uint32_t neg_mask, int raw, int step, uint8_t* out576,
+                           uint32_t* mask_out) {
+    return run_fixedk(n, K, g1s, g2s, neg_mask, true, raw, step, 0, out576, mask_out);
 }
 
 }  // extern "C"
