@@ -149,6 +149,12 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz] + [vp] * 7
         for name in ("c12381_ac_bbs_pres_batch", "c12381_ac_bbs_pres_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz] + [vp] * 9
+        for name in ("c12381_ac_rbbs_verify_batch", "c12381_ac_rbbs_verify_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz] + [vp] * 7
+        for name in ("c12381_ac_rbbs_pres_batch", "c12381_ac_rbbs_pres_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 6
+        for name in ("c12381_ac_rbbs_redact_batch", "c12381_ac_rbbs_redact_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp] + [vp] * 6
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -692,6 +698,53 @@ class Context:
         arr, nI = self._idx(idx)
         self._ck(self.lib.c12381_ac_bbs_pres_batch_dev(self.h, n, nattr, nI, arr, msg_len, _p(pk_ptr), _p(Y_ptr), _p(attr_ptr), _p(sig_ptr), _p(msg_ptr),
                                                        _p(rnd_ptr), _p(pres_ptr), _p(u_ptr), _p(status_ptr)))
+
+    def ac_rbbs_verify(self, pk243: bytes, Y49: bytes, tY97: bytes, idx, pres341: bytes, attr48: bytes, msgs: bytes, msg_len: int,
+                       strict: bool = True) -> bytes:
+        """AC-rbbs verify from the wire formats (include/c12381_ac.h): pk.fixed_part (243 B), pk.Y (2 nattr x 49 B), pk.tilde_Y (nattr x 97 B),
+        the disclosure set idx, PresInfo (341 B each), the DISCLOSED attributes (nI x 48 B each, in the order of idx) and messages of msg_len
+        bytes each.  One byte per presentation: 1 / 0, or 0xff where the reference would throw.  A used key record that does not decode is
+        C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise."""
+        n, nattr = len(pres341) // 341, len(tY97) // 97
+        arr, nI = self._idx(idx)
+        out = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_rbbs_verify_batch(self.h, n, nattr, nI, arr, msg_len, _p(pk243), _p(Y49), _p(tY97), _p(pres341),
+                                                      _p(attr48) if nI else None, _p(msgs) if msg_len else None, _p(out)), allow_point=not strict)
+        return out.raw[:n]
+
+    def ac_rbbs_verify_dev(self, n, nattr, idx, msg_len, pk_ptr, Y_ptr, tY_ptr, pres_ptr, attr_ptr, msg_ptr, ok_ptr):
+        arr, nI = self._idx(idx)
+        self._ck(self.lib.c12381_ac_rbbs_verify_batch_dev(self.h, n, nattr, nI, arr, msg_len, _p(pk_ptr), _p(Y_ptr), _p(tY_ptr), _p(pres_ptr), _p(attr_ptr),
+                                                          _p(msg_ptr), _p(ok_ptr)))
+
+    def ac_rbbs_pres(self, sigs97: bytes, cache196: bytes, msgs: bytes, rnd: bytes, msg_len: int):
+        """AC-rbbs pres from the wire formats: signatures serialize(A, w) (97 B each), redact caches (196 B each), messages and the caller's
+        randomness (r, alpha, beta: 3 x 32 B per presentation) -> (n x 341-byte PresInfo, n status bytes: 0, or 0xff — and a record of 0xff —
+        where the reference would throw).  Not constant-time."""
+        n = len(sigs97) // 97
+        pres, st = ctypes.create_string_buffer(max(341 * n, 1)), ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_rbbs_pres_batch(self.h, n, msg_len, _p(sigs97), _p(cache196), _p(msgs) if msg_len else None, _p(rnd), _p(pres), _p(st)))
+        return pres.raw[:341 * n], st.raw[:n]
+
+    def ac_rbbs_pres_dev(self, n, msg_len, sig_ptr, cache_ptr, msg_ptr, rnd_ptr, pres_ptr, status_ptr):
+        self._ck(self.lib.c12381_ac_rbbs_pres_batch_dev(self.h, n, msg_len, _p(sig_ptr), _p(cache_ptr), _p(msg_ptr), _p(rnd_ptr), _p(pres_ptr), _p(status_ptr)))
+
+    def ac_rbbs_redact(self, pk243: bytes, Y49: bytes, idx, attr48: bytes, sigs97: bytes, strict: bool = True):
+        """AC-rbbs redact from the wire formats: pk.fixed_part, pk.Y (2 nattr x 49 B, nattr <= 16), the disclosure set idx, the holder's whole
+        attribute spans (nattr x 48 B each) and signatures (97 B each) -> (n x 196-byte RedactCache, n status bytes: 0, or 0xff — and a record
+        of 0xff — where the reference would throw).  A key that does not decode is C12381_E_POINT (every byte 0xff): raised when strict,
+        returned as bytes otherwise.  Not constant-time."""
+        n, nattr = len(sigs97) // 97, len(Y49) // 98
+        arr, nI = self._idx(idx)
+        cache, st = ctypes.create_string_buffer(max(196 * n, 1)), ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_rbbs_redact_batch(self.h, n, nattr, nI, arr, _p(pk243), _p(Y49), _p(attr48), _p(sigs97), _p(cache), _p(st)),
+                 allow_point=not strict)
+        return cache.raw[:196 * n], st.raw[:n]
+
+    def ac_rbbs_redact_dev(self, n, nattr, idx, pk_ptr, Y_ptr, attr_ptr, sig_ptr, cache_ptr, status_ptr):
+        arr, nI = self._idx(idx)
+        self._ck(self.lib.c12381_ac_rbbs_redact_batch_dev(self.h, n, nattr, nI, arr, _p(pk_ptr), _p(Y_ptr), _p(attr_ptr), _p(sig_ptr), _p(cache_ptr),
+                                                          _p(status_ptr)))
 
     # ---- device-pointer entry points (ints = device addresses, e.g. torch tensor.data_ptr())
     def bbs_plus_sign(self, g1, h0, h, gamma32, x, r, m) -> bytes:

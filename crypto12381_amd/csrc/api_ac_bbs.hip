@@ -37,8 +37,8 @@ static int ac_bbs_y_sum(c12381_ctx* c, size_t m, const ac_bbs_set& s, const ac_b
     if (nb == 0) { LAUNCH(c, ac_bbs_bcast96_kernel, m, m, addend, out96); return 0; }
     return g1_fixed_sum_range(c, m, s.nattr, first, nb, pub.y96, addend, sc, out96, 96);
 }
-// out[j] = a96[j] + b96[j]
-static int ac_bbs_add(c12381_ctx* c, size_t m, const uint8_t* a96, const uint8_t* b96, uint8_t* out, int fmt) {
+// out[j] = a96[j] + b96[j] (host.hpp: api_ac_rbbs.hip adds with it too)
+int c12381_host::ac_bbs_add(c12381_ctx* c, size_t m, const uint8_t* a96, const uint8_t* b96, uint8_t* out, int fmt) {
     proj_slab w;
     int rc;
     if ((rc = proj_ws(c, m, w))) return rc;

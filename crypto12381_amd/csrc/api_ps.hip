@@ -19,38 +19,48 @@ using namespace c12381_host;
 static int ps_verify_args(size_t nmsg, const void* g2, const void* X2, const void* Y2, const void* s1, const void* s2, const void* m, const void* ok) {
     return (!g2 || !X2 || !s1 || !s2 || !ok || (nmsg && (!Y2 || !m))) ? C12381_E_ARG : 0;
 }
-int c12381_ps_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
-                               const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok) {
-    int rc = bind(c) ?: ps_verify_args(nmsg, g2_192, X2_192, Y2_192, s1_96, s2_96, m_32, ok);
-    if (rc || n == 0) return rc;
-    const bool fast = nmsg + 2 <= (size_t)C12381_FIXED_G2_MAX;
-    const int k = (int)nmsg + 2;
+// The body, on checked arguments.  X2 may be absent (host.hpp ps_verify_core: the second pairing equation of AC-rbbs, api_ac_rbbs.hip): the
+// product then has the nmsg + 1 factors e(-s2, g2), e(m_i s1, Y2_i) over the tables of g2, Y2_0 .., and W is the plain sum (infinity for nmsg = 0).
+int c12381_host::ps_verify_core(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                                const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok) {
+    int rc;
+    const size_t fixed = X2_192 ? 2 : 1;              // factors of the product that take no message scalar
+    const bool fast = nmsg + fixed <= (size_t)C12381_FIXED_G2_MAX;
+    const int k = (int)(nmsg + fixed);
     const int32_t *gate_generic = nullptr, *gate_fast = nullptr;
     cached t = {};
     if (fast) {
-        if ((rc = lines_tables_k(c, k, g2_key_cols(g2_192, X2_192, Y2_192, nmsg), 1, t))) return rc;
+        g2_cols q = {};                               // without X2: g2, Y2_0 .. (up to FIXED_G2_MAX - 1 messages)
+        if (X2_192) q = g2_key_cols(g2_192, X2_192, Y2_192, nmsg);
+        else { q.p[0] = g2_192; for (size_t i = 0; i < nmsg; ++i) q.p[1 + i] = Y2_192 + 192 * i; }
+        if ((rc = lines_tables_k(c, k, q, 1, t))) return rc;
         gate_generic = t.gate;                // generic kernels: skip when every table is valid
         gate_fast = t.gate + GATE_OTHER;      // fast-route kernels with a skip pointer: skip when one is not
     }
     // generic route: W = X2 + sum_i m_i Y2_i (WS_BBS_Q), each product in WS_BBS_B
     if ((rc = ensure(c, c12381_ctx::WS_BBS_Q, 192 * n))) return rc;
     uint8_t* d_w = (uint8_t*)c->ws[c12381_ctx::WS_BBS_Q];
-    if (nmsg == 0) {
+    if (nmsg == 0 && !X2_192) {
+        HIPCK(c, hipMemsetAsync(d_w, 0, 192 * n, c->stream));
+    } else if (nmsg == 0) {
         LAUNCH(c, g2_bcast_kernel, 192 * n, n, X2_192, d_w, gate_generic);
     } else if (!fast && nmsg <= (size_t)C12381_G2_FIXED_SUM_MAX) {
-        if ((rc = c12381_g2_mul_fixed_sum_batch_dev(c, n, nmsg, Y2_192, X2_192, m_32, d_w, 192))) return rc;
+        if ((rc = g2_fixed_sum_range(c, n, nmsg, 0, nmsg, Y2_192, X2_192, m_32, d_w, 192))) return rc;
     } else {
         if ((rc = ensure(c, c12381_ctx::WS_BBS_B, 192 * n))) return rc;
         uint8_t* d_b = (uint8_t*)c->ws[c12381_ctx::WS_BBS_B];
         for (size_t i = 0; i < nmsg; ++i) {
-            if ((rc = g2_mul_dev_strided(c, n, Y2_192 + 192 * i, 0, m_32 + 32 * n * i, d_b, 192, gate_generic))) return rc;
+            const bool first_alone = i == 0 && !X2_192;       // no X2: the first product is W so far
+            if ((rc = g2_mul_dev_strided(c, n, Y2_192 + 192 * i, 0, m_32 + 32 * n * i, first_alone ? d_w : d_b, 192, gate_generic))) return rc;
+            if (first_alone) continue;
             LAUNCH(c, g2_add_kernel, n, n, i == 0 ? X2_192 : (const uint8_t*)d_w, (size_t)(i == 0 ? 0 : 192), (const uint8_t*)d_b, d_w, 192, c->d_flag, gate_generic);
         }
     }
     if (fast) {
         // fast route: the columns -s2 (against g2), s1 (X2), m_i s1 (Y2_i); m_i s1 by the generic G1 multiplication into WS_PROJ, then affine
         g1_cols cols = {};
-        cols.p[0] = s2_96; cols.p[1] = s1_96;
+        cols.p[0] = s2_96;
+        if (X2_192) cols.p[1] = s1_96;
         if (nmsg) {
             const size_t stride = round_up(nmsg * n, 64);
             for (size_t i = 0; i < nmsg; ++i)
@@ -58,13 +68,19 @@ int c12381_ps_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8
             if ((rc = ensure(c, c12381_ctx::WS_FQK_G1, 96 * nmsg * n))) return rc;
             uint8_t* d_m = (uint8_t*)c->ws[c12381_ctx::WS_FQK_G1];
             if ((rc = g1_finish(c, nmsg * n, (const int32_t*)c->ws[c12381_ctx::WS_PROJ], stride, d_m, 96))) return rc;
-            for (size_t i = 0; i < nmsg; ++i) cols.p[2 + i] = d_m + 96 * n * i;
+            for (size_t i = 0; i < nmsg; ++i) cols.p[fixed + i] = d_m + 96 * n * i;
         }
         timed tm(c, 4);
         if ((rc = launch_prodk(c, n, k, cols, 1u, t, ok, true, false, gate_fast))) return rc;
     }
     timed tm(c, 4);
     return launch_pair_eq(c, n, s1_96, d_w, s2_96, g2_192, (size_t)0, ok, gate_generic);
+}
+int c12381_ps_verify_batch_dev(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
+                               const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok) {
+    int rc = bind(c) ?: ps_verify_args(nmsg, g2_192, X2_192, Y2_192, s1_96, s2_96, m_32, ok);
+    if (rc || n == 0) return rc;
+    return ps_verify_core(c, n, nmsg, g2_192, X2_192, Y2_192, s1_96, s2_96, m_32, ok);
 }
 int c12381_ps_verify_batch(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192,
                            const uint8_t* s1_96, const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok) {

@@ -1054,6 +1054,10 @@ int g1_fixed_sum_range(c12381_ctx* c, size_t n, size_t total, size_t first, size
                        uint8_t* out, int fmt) {
     return fixed_sum_range<sum_g1>(c, n, total, first, nb, bases96, addend96, sc, out, fmt);
 }
+int g2_fixed_sum_range(c12381_ctx* c, size_t n, size_t total, size_t first, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc,
+                       uint8_t* out, int fmt) {
+    return fixed_sum_range<sum_g2>(c, n, total, first, nb, bases192, addend192, sc, out, fmt);
+}
 }  // namespace c12381_host
 template <class G>
 static int fixed_sum_host(c12381_ctx* c, size_t n, size_t nb, const uint8_t* bases, const uint8_t* addend, const uint8_t* sc, uint8_t* out, int fmt) {

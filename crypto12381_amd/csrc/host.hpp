@@ -1,4 +1,4 @@
-// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip): the context and its
+// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip, api_ac_rbbs.hip): the context and its
 // workspaces, and the idioms every entry point is written in — launch, slab (host_layouts.hpp), host form.  Everything in namespace c12381_host
 // has external linkage and hidden visibility: the units call each other's helpers, the library exports the C ABI alone.  The comment at each
 // declaration names the unit that defines it.
@@ -29,7 +29,7 @@ struct c12381_ctx {
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
            WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_FB_G1_4, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
-           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_PS, WS_AC_BBS, WS_COUNT };
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_PS, WS_AC_BBS, WS_AC_RBBS, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;
@@ -176,6 +176,17 @@ int g1_fixed_column(c12381_ctx* c, size_t m, const uint8_t* base, int slot, cons
 // Arguments are the caller's to check (1 <= nb, first + nb <= total <= C12381_G1_FIXED_SUM_MAX, n > 0).
 int g1_fixed_sum_range(c12381_ctx* c, size_t n, size_t total, size_t first, size_t nb, const uint8_t* bases96, const uint8_t* addend96, const uint8_t* sc,
                        uint8_t* out, int fmt);
+// the same over G2 bases and the tables of c12381_g2_mul_fixed_sum_batch_dev (1 <= nb, first + nb <= total <= C12381_G2_FIXED_SUM_MAX)
+int g2_fixed_sum_range(c12381_ctx* c, size_t n, size_t total, size_t first, size_t nb, const uint8_t* bases192, const uint8_t* addend192, const uint8_t* sc,
+                       uint8_t* out, int fmt);
+
+// ---------------------------------------------------------------- api_ps.hip, api_ac_bbs.hip: pieces the credential units share
+// The body of c12381_ps_verify_batch_dev on checked arguments (n > 0) with an X2 that may be ABSENT (null):
+// ok[j] = [ e(s1_j, sum_i m[i*n + j] Y2_i) == e(s2_j, g2) ], the product of the fast route then has nmsg + 1 factors.
+int ps_verify_core(c12381_ctx* c, size_t n, size_t nmsg, const uint8_t* g2_192, const uint8_t* X2_192, const uint8_t* Y2_192, const uint8_t* s1_96,
+                   const uint8_t* s2_96, const uint8_t* m_32, uint8_t* ok);
+// out[j] = a96[j] + b96[j], one complete addition per lane (api_ac_bbs.hip)
+int ac_bbs_add(c12381_ctx* c, size_t m, const uint8_t* a96, const uint8_t* b96, uint8_t* out, int fmt);
 
 // ---------------------------------------------------------------- api_pair.hip: line tables and the pairing launches the protocols share
 // Line tables of the k points q.p[j] (coefficients of a fixed G2 argument of the Miller loop, pairing3.hpp) and the gate over the k, in the

@@ -155,6 +155,53 @@ inline ac_bbs_pres_slab ac_bbs_pres_layout(void* base, size_t m, size_t nattr, s
     return s;
 }
 
+// ---------------------------------------------------------------- AC-rbbs (WS_AC_RBBS): the verify and redact slabs start behind the public block
+constexpr size_t AC_RBBS_PUB_BYTES = 18432;
+// the public block.  verify: the used records of pk.Y and pk.tilde_Y (in the order of idx) as they arrive (y49, ty97) and decoded (y96, ty192);
+// redact: all 2 nattr records of pk.Y decoded (y96) and the base list gathered from them (l96).  Both: g and tilde_g, tilde_X decoded straight
+// from pk.fixed_part, and the status bytes g, tilde_g, tilde_X, then the Y (and, behind them, the tilde_Y) that the entry decodes
+struct ac_rbbs_public {
+    uint8_t *y49, *ty97, *g96, *y96, *l96, *g2, *ty192, *st;  // 32 x 49 B; 32 x 97 B; 96 B; 32 x 96 B; 32 x 96 B; 2 x 192 B; 32 x 192 B; 3 + 64 B
+    explicit ac_rbbs_public(uint8_t* d)
+        : y49(d), ty97(d + 1792), g96(d + 5120), y96(d + 5376), l96(d + 8448), g2(d + 11520), ty192(d + 12032), st(d + 18176) {}
+};
+// verify, per presentation of a chunk: A_, B_, U, C_J_, D_ as they arrive (columns) and decoded, their statuses, the re-encoded five, the terms K, A_,
+// -B_ of the k = 3 product and its scalars s, t, c, the nI columns a_I and the nI columns q_I, the parse status, the transcript, C_J_ + B_, the
+// product compressed, both pairing verdicts: 1752 + 64 nI + msg_len bytes
+struct ac_rbbs_verify_slab { uint8_t *p49, *p96, *st_p, *e49, *q96, *sc3, *sca, *q32, *st, *tr, *s96, *r49, *ok1, *ok3; size_t bytes; };
+inline ac_rbbs_verify_slab ac_rbbs_verify_layout(void* base, size_t m, size_t nI, size_t msg_len) {
+    carver f(base, AC_RBBS_PUB_BYTES);
+    ac_rbbs_verify_slab s;
+    s.p49 = f.take(5 * 49 * m); s.p96 = f.take(5 * 96 * m); s.st_p = f.take(5 * m); s.e49 = f.take(5 * 49 * m); s.q96 = f.take(3 * 96 * m);
+    s.sc3 = f.take(3 * 32 * m); s.sca = f.take(32 * nI * m); s.q32 = f.take(32 * nI * m); s.st = f.take(m); s.tr = f.take((msg_len + 245) * m);
+    s.s96 = f.take(96 * m); s.r49 = f.take(49 * m); s.ok1 = f.take(m); s.ok3 = f.take(m);
+    s.bytes = f.bytes;
+    return s;
+}
+// pres (no key: the slab starts at the workspace), per presentation: C_I, A, B, C_J, D as they arrive and decoded, their statuses and the parse
+// status, r four times, alpha and beta, the terms C_I, A_ of the k = 2 product, the points A_, B_, C_J_, D_, U and their encodings, c, the
+// transcript: 2117 + msg_len bytes
+struct ac_rbbs_pres_slab { uint8_t *p49, *p96, *st_p, *st, *scr, *sc2, *t96, *o96, *e49, *c32, *tr; size_t bytes; };
+inline ac_rbbs_pres_slab ac_rbbs_pres_layout(void* base, size_t m, size_t msg_len) {
+    carver f(base);
+    ac_rbbs_pres_slab s;
+    s.p49 = f.take(5 * 49 * m); s.p96 = f.take(5 * 96 * m); s.st_p = f.take(5 * m); s.st = f.take(m); s.scr = f.take(4 * 32 * m); s.sc2 = f.take(2 * 32 * m);
+    s.t96 = f.take(2 * 96 * m); s.o96 = f.take(5 * 96 * m); s.e49 = f.take(5 * 49 * m); s.c32 = f.take(32 * m); s.tr = f.take((msg_len + 245) * m);
+    s.bytes = f.bytes;
+    return s;
+}
+// redact, per credential: A as it arrives and decoded, its status and the parse status, the nattr attribute columns, -w, the disclosed fields in
+// the order of idx, the nI columns q_I, the nD exponent columns of D, A^(-w), the points C_I, C_J, B, D: 659 + 32 nattr + 80 nI + 32 nD bytes
+struct ac_rbbs_redact_slab { uint8_t *a49, *a96, *st_a, *st, *sca, *scw, *aI48, *q32, *scd, *t96, *o96; size_t bytes; };
+inline ac_rbbs_redact_slab ac_rbbs_redact_layout(void* base, size_t m, size_t nattr, size_t nI, size_t nD) {
+    carver f(base, AC_RBBS_PUB_BYTES);
+    ac_rbbs_redact_slab s;
+    s.a49 = f.take(49 * m); s.a96 = f.take(96 * m); s.st_a = f.take(m); s.st = f.take(m); s.sca = f.take(32 * nattr * m); s.scw = f.take(32 * m);
+    s.aI48 = f.take(48 * nI * m); s.q32 = f.take(32 * nI * m); s.scd = f.take(32 * nD * m); s.t96 = f.take(96 * m); s.o96 = f.take(4 * 96 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+
 // ---------------------------------------------------------------- pairing work queue (WS_PAIR_ST; the GT power: WS_POW_ST)
 // The figures of the queue kernels (api_pair.hip asserts them against kernels.hpp): 21 pairings per wavefront group, 4 wavefronts per
 // workgroup, a grid that fills the machine at 2 wavefronts per SIMD, and a queued group's state block in the tagged / the fenced form.

@@ -10,6 +10,7 @@
 //   k_bbs04.hip  SHA3-512 (sha3.hpp) and the bbs04 group-signature stages around the scalar multiplications and the pairing product
 //   k_ps.hip     the PS signature stages (ps.hpp) around decompression, the fixed-base column, the bucket products and the pairing product
 //   k_ac_bbs.hip the AC-bbs credential stages (ac_bbs.hpp) around decompression, the fixed-base sums, the k-way products and PS verification
+//   k_ac_rbbs.hip the AC-rbbs credential stages (ac_rbbs.hpp): the same, with the q_i hashes, the exponents of redact and a second pairing equation
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -154,6 +155,17 @@ __global__ void __launch_bounds__(BLOCK, 2) ac_bbs_challenge_kernel(size_t n, si
 __global__ void __launch_bounds__(BLOCK, 2) ac_bbs_verify_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* r49, const uint8_t* u49, const uint8_t* okp, uint8_t* ok, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) ac_bbs_pres_prep_kernel(size_t n, size_t nattr, size_t nJ, ac_bbs_order ord, const uint8_t* attr48, const uint8_t* sig97, const uint8_t* rnd, uint8_t* a49, uint8_t* sca, uint8_t* scd, uint8_t* sc2, uint8_t* st);
 __global__ void __launch_bounds__(BLOCK, 2) ac_bbs_pres_finish_kernel(size_t n, size_t nattr, size_t nJ, ac_bbs_order ord, const uint8_t* attr48, const uint8_t* sig97, const uint8_t* rnd, const uint8_t* e49, const uint8_t* c32, const uint8_t* st, const uint8_t* st_a, const uint8_t* st_pub, uint8_t* pres243, uint8_t* u48, uint8_t* status, int* bad_flag);
+// k_ac_rbbs.hip: AC-rbbs credential redaction, presentation and verification (ac_rbbs.hpp; the index lists and the plan travel by value)
+struct ac_rbbs_plan;
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_gather_kernel(size_t count, size_t rec_bytes, ac_bbs_order ord, const uint8_t* in, uint8_t* out);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_verify_prep_kernel(size_t n, size_t nI, ac_bbs_order idx, const uint8_t* pres341, const uint8_t* attr48, uint8_t* p49, uint8_t* sc3, uint8_t* sca, uint8_t* q32, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_encode_kernel(size_t n, size_t count, const uint8_t* p96, uint8_t* e49);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_challenge_kernel(size_t n, size_t msg_len, const uint8_t* msgs, const uint8_t* e49, int u_col, uint8_t* tr, uint8_t* c32);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_verify_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* r49, const uint8_t* u49, const uint8_t* ok1, const uint8_t* ok3, uint8_t* ok, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_pres_prep_kernel(size_t n, const uint8_t* sig97, const uint8_t* cache196, const uint8_t* rnd, uint8_t* p49, uint8_t* scr, uint8_t* sc2, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_pres_finish_kernel(size_t n, const uint8_t* sig97, const uint8_t* rnd, const uint8_t* e49, const uint8_t* c32, const uint8_t* st, const uint8_t* st_p, uint8_t* pres341, uint8_t* status);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_redact_prep_kernel(size_t n, ac_rbbs_plan pl, const uint8_t* attr48, const uint8_t* sig97, uint8_t* a49, uint8_t* sca, uint8_t* scw, uint8_t* aI48, uint8_t* q32, uint8_t* scd, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_redact_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_a, const uint8_t* o96, uint8_t* cache196, uint8_t* status, int* bad_flag);
 // k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
 constexpr int TABLE_ARRAY_MAX = 32;
 struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };

@@ -90,6 +90,83 @@ int c12381_ac_bbs_pres_batch_dev(c12381_ctx* ctx, size_t n, size_t nattr, size_t
                                  const uint8_t* Y_49, const uint8_t* attr_48, const uint8_t* sig_97, const uint8_t* msgs, const uint8_t* rnd,
                                  uint8_t* pres_243, uint8_t* u_48, uint8_t* status);
 
+/* AC-rbbs credentials (examples/AC-rbbs/src/redact.cpp, pres.cpp, verify.cpp) from the WIRE formats ---------------------------------------- */
+/* The redactable family on top of AC-bbs: presentations of constant size (341 bytes whatever nJ), for a per-credential redact step and a second
+ * pairing equation over a hashed G2 combination.  Wire layouts (examples/AC-rbbs/include/AC-rbbs.hpp):
+ *   pk_243     pk.fixed_part = serialize(g, tilde_g, tilde_X)                49 + 97 + 97 = 243 bytes
+ *   Y_49       pk.Y, 2 nattr records of 49 bytes (Y[nattr] = g, keygen.cpp:31-38)
+ *   tY_97      pk.tilde_Y, nattr records of 97 bytes
+ *   sig_97     Signature = serialize(A, w)                                   49 + 48 = 97 bytes
+ *   cache_196  RedactCache = serialize(C_I, C_J, B, D)                       4 x 49 = 196 bytes
+ *   pres_341   PresInfo = serialize(A_, B_, C_J_, D_, U, s, t)               5 x 49 + 2 x 48 = 341 bytes
+ *   attributes serialize(Zp) fields of 48 bytes; messages msg_len raw bytes each (msg_len = 0 allowed, msgs may then be NULL)
+ * Everything said above for AC-bbs carries over unchanged: the library's decoding and parse<Zp>'s range check, bytewise reads, ONE disclosure set
+ * per batch with idx a HOST array in both forms, the C12381_E_ARG conditions (nattr = 0, nattr > C12381_G1_FIXED_SUM_MAX, nI > nattr, an index >=
+ * nattr, a repeated index, a null idx with nI > 0, any null pointer not allowed below) checked before the empty-batch rule, n = 0 returning C12381_OK
+ * and touching nothing, `^` = multiply exact for EVERY curve point (keys and records outside G1 / G2 and at infinity included; no verdict rests on
+ * a subgroup assumption the device has not checked), 0xff lanes where the reference would throw, and a key that does not decode: every lane 0xff
+ * and C12381_E_POINT (the _dev form reports it at the next c12381_sync), the context stays usable.  Batches run in chunks of up to 2^18.
+ * Hashes (set.hpp:327-392):
+ *   c   = SHA3-512(msg | A_ | B_ | C_J_ | D_ | U) mod r    no length prefix; the five points 49-byte compressed as hash() re-serialises the parsed
+ *                                                          points (a leading 0x00 hashes as 49 zeros, an x >= p as its residue): msg_len + 245 bytes
+ *   q_i = SHA3-512(a_I[0] | .. | a_I[nI-1] | i) mod r      the disclosed values as 48-byte fields in the order of idx, then the size_t i as 8
+ *                                                          little-endian bytes: 48 nI + 8 bytes.  Only i in I is ever used; those nI are computed,
+ *                                                          the whole blocks of the shared prefix absorbed once per lane.
+ *
+ * c12381_ac_rbbs_verify_batch: ok[j] = verify(m_j, attr_j, I, pres_j, pk) (verify.cpp:6-24); attr_48 holds the DISCLOSED values only, n x nI fields
+ * lane-major in the order of idx (NULL allowed when nI = 0).  With K = g * prod_I Y_i^a_i (one fixed-base sum with the addend g):
+ *   ok = [ e(A_, tilde_X) == e(C_J_ * B_, tilde_g) ]                            c12381_ps_verify_batch with no messages, s1 = A_, s2 = C_J_ + B_
+ *    and [ U * B_^c == K^s * A_^t ]                                             K^s A_^t (-B_)^c as ONE k = 3 product, compared with U
+ *    and [ e(C_J_, prod_I tilde_Y[nattr-1-i]^q_i) == e(D_, tilde_g) ]           the PS check with NO X2: g2 = tilde_g, Y2 = the used tilde_Y, m = q_i
+ * The third equation takes the routes of c12381_ps_verify_batch, picked on the device: e(-D_, tilde_g) * prod_I e(q_i C_J_, tilde_Y..) == 1 as one
+ * (nI + 1)-way product over line tables when tilde_g and the used tilde_Y are elements of G2 other than infinity and nI + 1 <= C12381_FIXED_G2_MAX;
+ * otherwise W = sum_I q_i tilde_Y.. (the G2 fixed-base sum for nI + 1 > C12381_FIXED_G2_MAX, column by column below; nI = 0: infinity) and pair_eq.
+ * The reference parses pk.Y and pk.tilde_Y lazily: only Y_i and tilde_Y[nattr-1-i] for i in I are read and decoded, an undecodable record that
+ * verify never touches does not fail the call.  nattr up to C12381_G1_FIXED_SUM_MAX.
+ * Status: ok[j] = 1 / 0; 0xff: one of the five points does not decode, or s, t or a disclosed a_i is >= r.  Key failure: g, tilde_g, tilde_X or a
+ * USED record of Y / tilde_Y does not decode.
+ * Workspace (c12381_trim releases it): per presentation of a chunk 1752 + 64 nI + msg_len bytes, besides the workspaces of the entries used.
+ * Both pairing equations share the line-table array of c12381_ps_verify_batch: its second table alternates between tilde_X and the first used
+ * tilde_Y, so each chunk rebuilds that one table twice. */
+int c12381_ac_rbbs_verify_batch(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, size_t msg_len, const uint8_t* pk_243,
+                                const uint8_t* Y_49, const uint8_t* tY_97, const uint8_t* pres_341, const uint8_t* attr_48, const uint8_t* msgs,
+                                uint8_t* ok);
+int c12381_ac_rbbs_verify_batch_dev(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, size_t msg_len, const uint8_t* pk_243,
+                                    const uint8_t* Y_49, const uint8_t* tY_97, const uint8_t* pres_341, const uint8_t* attr_48, const uint8_t* msgs,
+                                    uint8_t* ok);
+/* c12381_ac_rbbs_pres_batch: pres(m_j, sig_j, cache_j) (pres.cpp:6-27) with the caller's randomness; no key and no index set.
+ *   rnd      per presentation r, alpha, beta, 32 big-endian bytes each; any value below 2^256, reduced mod r first
+ * Per presentation, negation being the reference's Zp negation (the scalar r - w; -0 = 0):
+ *   A_, B_, C_J_, D_ = A^r, B^r, C_J^r, D^r      one generic G1 column of 4 n lanes
+ *   U = C_I^alpha * A_^beta                       one k = 2 product;  c as above;  s = alpha + r c,  t = beta + (-w) c
+ * Outputs: pres_341 (n x 341 bytes), status (n bytes): 0, or 0xff — and a record of 0xff bytes — where the reference would throw: A or a cache
+ * point does not decode, or w >= r; the other lanes are unaffected and the call returns C12381_OK.
+ * NOT constant-time: the scalar multiplications take data-dependent paths and addresses.  The secrets the call is given (w, r, alpha, beta) and
+ * values derived from them stay in the context's device workspaces (and, for the host form, its staging buffer) until a later call overwrites
+ * them or c12381_trim frees them; nothing is wiped.
+ * Workspace: per presentation of a chunk 2117 + msg_len bytes, besides the workspaces of the entries used. */
+int c12381_ac_rbbs_pres_batch(c12381_ctx* ctx, size_t n, size_t msg_len, const uint8_t* sig_97, const uint8_t* cache_196, const uint8_t* msgs,
+                              const uint8_t* rnd, uint8_t* pres_341, uint8_t* status);
+int c12381_ac_rbbs_pres_batch_dev(c12381_ctx* ctx, size_t n, size_t msg_len, const uint8_t* sig_97, const uint8_t* cache_196, const uint8_t* msgs,
+                                  const uint8_t* rnd, uint8_t* pres_341, uint8_t* status);
+/* c12381_ac_rbbs_redact_batch: redact(attr_j, sig_j, I, pk) (redact.cpp:7-44).  attr_48: the holder's WHOLE span, n x nattr fields lane-major in
+ * attribute order, every field range-checked.  With J the indices outside I and q_i as above, per credential:
+ *   C_I = g * prod_I Y_i^a_i      C_J = prod_J Y_j^a_j      B = C_I * A^(-w)
+ *   D = prod_(k in K_D) Y[k]^e_k,  e_k = sum_(i in I, k-nattr+i in J) q_i a_(k-nattr+i) mod r,  K_D = { nattr - i + j : i in I, j in J }
+ * exactly the k the reference's filter keeps; the empty product is infinity.  The three Y-sums are ranges of ONE base list of at most 2 nattr - 1
+ * records of pk.Y, evaluated through the tables of c12381_g1_mul_fixed_sum_batch (its workspace, its routes), so a second call with the same key
+ * and set builds no table.  That is why redact accepts nattr <= C12381_G1_FIXED_SUM_MAX / 2 = 16 ONLY and returns C12381_E_ARG above it (verify
+ * and pres take credentials of up to 32 attributes).
+ * Outputs: cache_196 (n x 196 bytes), status (n bytes): 0, or 0xff — and a record of 0xff bytes — where the reference would throw: A does not
+ * decode, or w or an attribute is >= r.  The reference materialises all of pk.Y here: g, tilde_g, tilde_X or ANY of the 2 nattr records of Y_49
+ * not decoding is a key failure.
+ * NOT constant-time, and nothing is wiped, as for pres: the attributes, w and the values derived from them stay in the workspaces.
+ * Workspace: per credential of a chunk 659 + 32 nattr + 80 nI + 32 |K_D| bytes, besides the workspaces of the entries used. */
+int c12381_ac_rbbs_redact_batch(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* pk_243, const uint8_t* Y_49,
+                                const uint8_t* attr_48, const uint8_t* sig_97, uint8_t* cache_196, uint8_t* status);
+int c12381_ac_rbbs_redact_batch_dev(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* pk_243, const uint8_t* Y_49,
+                                    const uint8_t* attr_48, const uint8_t* sig_97, uint8_t* cache_196, uint8_t* status);
+
 #ifdef __cplusplus
 }
 #endif
