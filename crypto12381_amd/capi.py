@@ -155,6 +155,12 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 6
         for name in ("c12381_ac_rbbs_redact_batch", "c12381_ac_rbbs_redact_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp] + [vp] * 6
+        for name in ("c12381_ac_rps_verify_batch", "c12381_ac_rps_verify_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp] + [vp] * 6
+        for name in ("c12381_ac_rps_pres_batch", "c12381_ac_rps_pres_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp] + [vp] * 9
+        for name in ("c12381_ac_rps_redact_batch", "c12381_ac_rps_redact_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp] + [vp] * 5
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -745,6 +751,66 @@ class Context:
         arr, nI = self._idx(idx)
         self._ck(self.lib.c12381_ac_rbbs_redact_batch_dev(self.h, n, nattr, nI, arr, _p(pk_ptr), _p(Y_ptr), _p(attr_ptr), _p(sig_ptr), _p(cache_ptr),
                                                           _p(status_ptr)))
+
+    def ac_rps_verify(self, pk243: bytes, Y49: bytes, tY97: bytes, idx, pres389: bytes, attr48: bytes, strict: bool = True, dev: bool = False) -> bytes:
+        """AC-rps verify from the wire formats (include/c12381_ac.h): pk.fixed_part (243 B), pk.Y ((2 nattr + 1) x 49 B), pk.tilde_Y
+        ((nattr + 1) x 97 B), the disclosure set idx, PresInfo (389 B each) and the DISCLOSED attributes (nI x 48 B each, in the order of idx);
+        there is no message.  One byte per presentation: 1 / 0, or 0xff where the reference would throw.  A used key record that does not
+        decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise.  dev: through the _dev form on device
+        copies of the buffers."""
+        n, nattr = len(pres389) // 389, len(tY97) // 97 - 1
+        arr, nI = self._idx(idx)
+        if dev:
+            return self._rps_dev(lambda p, o: self.lib.c12381_ac_rps_verify_batch_dev(self.h, n, nattr, nI, arr, *p, *o),
+                                 [pk243, Y49, tY97, pres389, attr48 if nI else None], [n], strict)[0]
+        out = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_rps_verify_batch(self.h, n, nattr, nI, arr, _p(pk243), _p(Y49), _p(tY97), _p(pres389), _p(attr48) if nI else None,
+                                                     _p(out)), allow_point=not strict)
+        return out.raw[:n]
+
+    def ac_rps_pres(self, pk243: bytes, Y49: bytes, idx, attr48: bytes, sigs195: bytes, cache97: bytes, usk48: bytes, rnd: bytes, strict: bool = True,
+                    dev: bool = False):
+        """AC-rps pres from the wire formats: pk.fixed_part, pk.Y, the disclosure set idx, the holder's whole attribute spans (nattr x 48 B each),
+        signatures serialize(h, sigma, tilde_M) (195 B each), redact caches (97 B each), user secret keys (48 B each) and the caller's randomness
+        (r, t, rho: 3 x 32 B per presentation) -> (n x 389-byte PresInfo, n status bytes: 0, or 0xff — and a record of 0xff — where the reference
+        would throw).  A key that does not decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes otherwise.  Not
+        constant-time."""
+        n, nattr = len(sigs195) // 195, (len(Y49) // 49 - 1) // 2
+        arr, nI = self._idx(idx)
+        if dev:
+            return tuple(self._rps_dev(lambda p, o: self.lib.c12381_ac_rps_pres_batch_dev(self.h, n, nattr, nI, arr, *p, *o),
+                                       [pk243, Y49, attr48, sigs195, cache97, usk48, rnd], [389 * n, n], strict))
+        pres, st = ctypes.create_string_buffer(max(389 * n, 1)), ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_rps_pres_batch(self.h, n, nattr, nI, arr, _p(pk243), _p(Y49), _p(attr48), _p(sigs195), _p(cache97), _p(usk48), _p(rnd),
+                                                   _p(pres), _p(st)), allow_point=not strict)
+        return pres.raw[:389 * n], st.raw[:n]
+
+    def ac_rps_redact(self, tY97: bytes, idx, attr48: bytes, sigs195: bytes, strict: bool = True, dev: bool = False):
+        """AC-rps redact from the wire formats: pk.tilde_Y ((nattr + 1) x 97 B), the disclosure set idx, the holder's whole attribute spans and
+        signatures (195 B each) -> (n x 97-byte RedactCache, n status bytes: 0, or 0xff — and a record of 0xff — where the reference would
+        throw).  A used record of pk.tilde_Y that does not decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as bytes
+        otherwise.  Not constant-time."""
+        n, nattr = len(sigs195) // 195, len(tY97) // 97 - 1
+        arr, nI = self._idx(idx)
+        if dev:
+            return tuple(self._rps_dev(lambda p, o: self.lib.c12381_ac_rps_redact_batch_dev(self.h, n, nattr, nI, arr, *p, *o), [tY97, attr48, sigs195],
+                                       [97 * n, n], strict))
+        cache, st = ctypes.create_string_buffer(max(97 * n, 1)), ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_ac_rps_redact_batch(self.h, n, nattr, nI, arr, _p(tY97), _p(attr48), _p(sigs195), _p(cache), _p(st)), allow_point=not strict)
+        return cache.raw[:97 * n], st.raw[:n]
+
+    def _rps_dev(self, call, ins, out_sizes, strict):
+        """the _dev form of an AC-rps entry on device copies of `ins` (bytes, or None for a null pointer): call(input pointers, output pointers), sync,
+        the outputs as bytes.  The outputs start as 0x07 bytes, so a byte the entry does not write shows."""
+        import torch
+        dev = [None if b is None else torch.frombuffer(bytearray(b) or bytearray(1), dtype=torch.uint8).to("cuda") for b in ins]
+        outs = [torch.full((max(k, 1),), 7, dtype=torch.uint8, device="cuda") for k in out_sizes]
+        torch.cuda.synchronize()
+        self._ck(call([None if t is None else _p(t.data_ptr()) for t in dev], [_p(t.data_ptr()) for t in outs]))
+        rc = self.lib.c12381_sync(self.h)
+        got = [bytes(t.cpu().numpy().tobytes())[:k] for t, k in zip(outs, out_sizes)]
+        self._ck(rc, allow_point=not strict)
+        return got
 
     # ---- device-pointer entry points (ints = device addresses, e.g. torch tensor.data_ptr())
     def bbs_plus_sign(self, g1, h0, h, gamma32, x, r, m) -> bytes:

@@ -202,6 +202,60 @@ inline ac_rbbs_redact_slab ac_rbbs_redact_layout(void* base, size_t m, size_t na
     return s;
 }
 
+// ---------------------------------------------------------------- AC-rps (WS_AC_RPS): every slab starts behind the public block
+constexpr size_t AC_RPS_PUB_BYTES = 22016;
+// the public block.  verify: the nI + 1 used records of pk.Y (the base list) and of pk.tilde_Y (the disclosed ones in the order of idx, then
+// tilde_Y[nattr]) as they arrive (y49, ty97) and decoded (l96, ty192); redact: the nI used records of pk.tilde_Y likewise; pres: all 2 nattr + 1
+// records of pk.Y decoded (y96) and the base list gathered from them (l96).  verify and pres: g and tilde_g, tilde_X decoded straight from
+// pk.fixed_part.  st: the status bytes of what the entry decodes — g, tilde_g, tilde_X, then the Y (and, behind them, the tilde_Y); redact: the tilde_Y
+struct ac_rps_public {
+    uint8_t *y49, *ty97, *g96, *y96, *l96, *g2, *ty192, *st;  // 32 x 49 B; 33 x 97 B; 96 B; 65 x 96 B; 32 x 96 B; 2 x 192 B; 32 x 192 B; 3 + 65 B
+    explicit ac_rps_public(uint8_t* d)
+        : y49(d), ty97(d + 1792), g96(d + 5120), y96(d + 5376), l96(d + 11776), g2(d + 14848), ty192(d + 15360), st(d + 21504) {}
+};
+// verify, per presentation of a chunk: sigma1_, C, sigma3_, sigma2_ (columns, in that order) and tilde_sigma_ as they arrive; S and the four decoded
+// (S in front: S | sigma1_ and sigma1_ | C and sigma3_ | sigma2_ are each the point columns of one launch); tilde_sigma_ decoded and W behind it; the
+// G2 sum; the five decoding statuses, the parse statuses of c0, s0 and of the disclosed values; the scalars s0, c0; the nI columns a_I; the hashed
+// prefix; the nI + 1 columns q; the encodings sigma1_, C, C0, sigma2_; the Schnorr transcript and its hash; five Miller values, e(C, tilde_Y[nattr])'s,
+// two conjugates; both verdicts: 6632 + 120 nI bytes
+struct ac_rps_verify_slab { uint8_t *p49, *p97, *a96, *q192, *w192, *st_p, *st, *st_a, *sc2, *sca, *pre, *q32, *e49, *tr, *c32, *gt, *ge, *gh, *okp; size_t bytes; };
+inline ac_rps_verify_slab ac_rps_verify_layout(void* base, size_t m, size_t nI) {
+    carver f(base, AC_RPS_PUB_BYTES);
+    ac_rps_verify_slab s;
+    s.p49 = f.take(4 * 49 * m); s.p97 = f.take(97 * m); s.a96 = f.take(5 * 96 * m); s.q192 = f.take(2 * 192 * m); s.w192 = f.take(192 * m);
+    s.st_p = f.take(5 * m); s.st = f.take(m); s.st_a = f.take(m); s.sc2 = f.take(2 * 32 * m); s.sca = f.take(32 * nI * m);
+    s.pre = f.take((195 + 56 * nI) * m + 4); s.q32 = f.take(32 * (nI + 1) * m); s.e49 = f.take(4 * 49 * m); s.tr = f.take(147 * m + 4); s.c32 = f.take(32 * m);
+    s.gt = f.take(5 * 576 * m); s.ge = f.take(576 * m); s.gh = f.take(2 * 576 * m); s.okp = f.take(2 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+// pres, per presentation: h, sigma and tilde_M, tilde_H as they arrive; h, sigma decoded and sigma1_ behind them; sigma1_ twice; tilde_M, tilde_H
+// decoded; tilde_g^t; the four decoding statuses and the parse status; the scalars r | r, t | z, rho | t; the hashed prefix; the nI + 1 columns q;
+// the `total` columns of sigma3_'s sum; the encodings sigma2_, sigma1_, C, C0 and sigma3_, tilde_sigma_; the Schnorr transcript and its hash:
+// 2293 + 88 nI + 32 total bytes
+struct ac_rps_pres_slab { uint8_t *p49, *p97, *a96, *b96, *m192, *t192, *st_p, *st, *scr, *sc2, *scz, *sct, *pre, *q32, *sc3, *e49, *s3_49, *ts97, *tr, *c32; size_t bytes; };
+inline ac_rps_pres_slab ac_rps_pres_layout(void* base, size_t m, size_t nI, size_t total) {
+    carver f(base, AC_RPS_PUB_BYTES);
+    ac_rps_pres_slab s;
+    s.p49 = f.take(2 * 49 * m); s.p97 = f.take(2 * 97 * m); s.a96 = f.take(3 * 96 * m); s.b96 = f.take(2 * 96 * m); s.m192 = f.take(2 * 192 * m);
+    s.t192 = f.take(192 * m); s.st_p = f.take(4 * m); s.st = f.take(m); s.scr = f.take(32 * m); s.sc2 = f.take(2 * 32 * m); s.scz = f.take(2 * 32 * m);
+    s.sct = f.take(32 * m); s.pre = f.take((195 + 56 * nI) * m + 4); s.q32 = f.take(32 * (nI + 1) * m); s.sc3 = f.take(32 * total * m);
+    s.e49 = f.take(4 * 49 * m); s.s3_49 = f.take(49 * m); s.ts97 = f.take(97 * m); s.tr = f.take(147 * m + 4); s.c32 = f.take(32 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+// redact, per credential: h, sigma and tilde_M as they arrive; h, sigma decoded (for their statuses alone) and tilde_M decoded; the three decoding
+// statuses and the parse status; the nI columns a_I; the G2 sum; tilde_H encoded: 872 + 32 nI bytes
+struct ac_rps_redact_slab { uint8_t *p49, *p97, *a96, *m192, *st_p, *st, *sca, *w192, *h97; size_t bytes; };
+inline ac_rps_redact_slab ac_rps_redact_layout(void* base, size_t m, size_t nI) {
+    carver f(base, AC_RPS_PUB_BYTES);
+    ac_rps_redact_slab s;
+    s.p49 = f.take(2 * 49 * m); s.p97 = f.take(97 * m); s.a96 = f.take(2 * 96 * m); s.m192 = f.take(192 * m); s.st_p = f.take(3 * m); s.st = f.take(m);
+    s.sca = f.take(32 * nI * m); s.w192 = f.take(192 * m); s.h97 = f.take(97 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+
 // ---------------------------------------------------------------- pairing work queue (WS_PAIR_ST; the GT power: WS_POW_ST)
 // The figures of the queue kernels (api_pair.hip asserts them against kernels.hpp): 21 pairings per wavefront group, 4 wavefronts per
 // workgroup, a grid that fills the machine at 2 wavefronts per SIMD, and a queued group's state block in the tagged / the fenced form.

@@ -11,6 +11,7 @@
 //   k_ps.hip     the PS signature stages (ps.hpp) around decompression, the fixed-base column, the bucket products and the pairing product
 //   k_ac_bbs.hip the AC-bbs credential stages (ac_bbs.hpp) around decompression, the fixed-base sums, the k-way products and PS verification
 //   k_ac_rbbs.hip the AC-rbbs credential stages (ac_rbbs.hpp): the same, with the q_i hashes, the exponents of redact and a second pairing equation
+//   k_ac_rps.hip the AC-rps credential stages (ac_rps.hpp): the q_k hashes over points and indices, the exponents of pres, G2 subtraction
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -166,6 +167,17 @@ __global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_pres_prep_kernel(size_t n, c
 __global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_pres_finish_kernel(size_t n, const uint8_t* sig97, const uint8_t* rnd, const uint8_t* e49, const uint8_t* c32, const uint8_t* st, const uint8_t* st_p, uint8_t* pres341, uint8_t* status);
 __global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_redact_prep_kernel(size_t n, ac_rbbs_plan pl, const uint8_t* attr48, const uint8_t* sig97, uint8_t* a49, uint8_t* sca, uint8_t* scw, uint8_t* aI48, uint8_t* q32, uint8_t* scd, uint8_t* st);
 __global__ void __launch_bounds__(BLOCK, 2) ac_rbbs_redact_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_a, const uint8_t* o96, uint8_t* cache196, uint8_t* status, int* bad_flag);
+// k_ac_rps.hip: AC-rps credential redaction, presentation and verification (ac_rps.hpp; the index list and the plan travel by value)
+struct ac_rps_plan;
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_verify_prep_kernel(size_t n, size_t nI, const uint8_t* pres389, const uint8_t* attr48, uint8_t* p49, uint8_t* p97, uint8_t* sc2, uint8_t* sca, uint8_t* st, uint8_t* st_a);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_verify_q_kernel(size_t n, ac_rps_plan pl, const uint8_t* s1_49, const uint8_t* s2_49, const uint8_t* ts192, const uint8_t* attr48, uint8_t* pre, uint8_t* q32);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_verify_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_a, const uint8_t* st_p, const uint8_t* c32, const uint8_t* sc2, const uint8_t* okp, uint8_t* ok, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_pres_prep_kernel(size_t n, size_t nattr, const uint8_t* attr48, const uint8_t* sig195, const uint8_t* cache97, const uint8_t* usk48, const uint8_t* rnd, uint8_t* p49, uint8_t* p97, uint8_t* scr, uint8_t* sc2, uint8_t* scz, uint8_t* sct, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_pres_scalars_kernel(size_t n, ac_rps_plan pl, const uint8_t* s1_49, const uint8_t* s2_49, const uint8_t* ts97, const uint8_t* attr48, const uint8_t* rnd, uint8_t* pre, uint8_t* q32, uint8_t* sc3);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_pres_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* e49, const uint8_t* s3_49, const uint8_t* ts97, const uint8_t* c32, const uint8_t* usk48, const uint8_t* rnd, uint8_t* pres389, uint8_t* status, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_redact_prep_kernel(size_t n, size_t nattr, size_t nI, ac_bbs_order idx, const uint8_t* attr48, const uint8_t* sig195, uint8_t* p49, uint8_t* p97, uint8_t* sca, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_g2_sub_kernel(size_t n, const uint8_t* a192, const uint8_t* b192, uint8_t* out, int fmt, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_rps_redact_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* h97, uint8_t* cache97, uint8_t* status, int* bad_flag);
 // k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
 constexpr int TABLE_ARRAY_MAX = 32;
 struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };

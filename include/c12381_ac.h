@@ -167,6 +167,99 @@ int c12381_ac_rbbs_redact_batch(c12381_ctx* ctx, size_t n, size_t nattr, size_t 
 int c12381_ac_rbbs_redact_batch_dev(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* pk_243, const uint8_t* Y_49,
                                     const uint8_t* attr_48, const uint8_t* sig_97, uint8_t* cache_196, uint8_t* status);
 
+/* AC-rps credentials (examples/AC-rps/src/redact.cpp, pres.cpp, verify.cpp) from the WIRE formats ------------------------------------------ */
+/* The redactable PS family: a user key z, presentations of constant size (389 bytes), two pairing equations whose G2 argument differs per
+ * presentation.  Wire layouts (examples/AC-rps/include/AC-rps.hpp), n = nattr:
+ *   pk_243     pk.fixed_part = serialize(g, tilde_g, tilde_X)                49 + 97 + 97 = 243 bytes
+ *   Y_49       pk.Y, 2 nattr + 1 records of 49 bytes, Y[k] = g^(y^(k+1)) (keygen.cpp:26-37)
+ *   tY_97      pk.tilde_Y, nattr + 1 records of 97 bytes
+ *   sig_195    Signature = serialize(h, sigma, tilde_M)                      49 + 49 + 97 = 195 bytes
+ *   cache_97   RedactCache = serialize(tilde_H)                              97 bytes
+ *   pres_389   PresInfo = serialize(sigma1_, sigma2_, sigma3_, C, tilde_sigma_, c0, s0)   4 x 49 + 97 + 2 x 48 = 389 bytes
+ *   usk_48     UserSecretKey = serialize(z)                                  48 bytes
+ *   attributes serialize(Zp) fields of 48 bytes
+ * The reference's pres and verify take a message m and never read it (pres.cpp:8, verify.cpp:6): these entries have NO message parameter.
+ * Everything said above for AC-bbs / AC-rbbs carries over unchanged: the library's decoding (a leading 0x00 is infinity, x taken mod p, no subgroup
+ * check) and parse<Zp>'s range check, bytewise reads, ONE disclosure set per batch with idx a HOST array in both forms, the C12381_E_ARG conditions
+ * (nattr = 0, nattr > C12381_G1_FIXED_SUM_MAX, nI > nattr, an index >= nattr, a repeated index, a null idx with nI > 0, any null pointer not allowed
+ * below, and what each entry adds) checked before the empty-batch rule, n = 0 returning C12381_OK and touching nothing, `^` = multiply exact for
+ * EVERY curve point (keys and records outside G1 / G2 and at infinity included; no verdict rests on a subgroup assumption the device has not
+ * checked), 0xff lanes where the reference would throw, and a key that does not decode: every lane 0xff and C12381_E_POINT (the _dev form reports
+ * it at the next c12381_sync), the context stays usable.  Batches run in chunks of up to 2^18.
+ * Parsing (set.hpp:114-160): a tuple parse — Signature, PresInfo, pk.fixed_part — decodes EVERY field, used or not; a range parse — pk.Y,
+ * pk.tilde_Y, the attributes — is lazy unless `| materialize` follows: only the elements an entry indexes are decoded or range-checked.
+ * Hashes (set.hpp:327-392), Ip = idx followed by nattr:
+ *   q_k = SHA3-512(sigma1_ | sigma2_ | tilde_sigma_ | idx[0] .. idx[nI-1] | a_I[0] .. a_I[nI-1] | Ip[k]) mod r, k <= nI
+ *         the points 49 / 49 / 97-byte compressed as hash() re-serialises the parsed points (a leading 0x00 hashes as zeros, an x >= p as its
+ *         residue), every index as the 8 little-endian bytes of a size_t, the disclosed values as 48-byte fields in the order of idx:
+ *         203 + 56 nI bytes.  The whole blocks of the shared 195 + 56 nI-byte prefix are absorbed once per lane.
+ *   c0  = SHA3-512(sigma1_ | C | C0) mod r                                    147 bytes
+ *
+ * c12381_ac_rps_verify_batch: ok[j] = verify(m_j, attr_j, I, pres_j, pk) (verify.cpp:6-38); attr_48 holds the DISCLOSED values only, n x nI fields
+ * lane-major in the order of idx (NULL allowed when nI = 0).  Per presentation, in the reference's order:
+ *   C0 = sigma1_^s0 * C^c0                                                      ONE k = 2 product (c12381_g1_mul_sum_batch)
+ *   c0 != hash(sigma1_, C, C0)  ->  ok = 0, WHATEVER the disclosed values hold: the reference returns before it reads them
+ *   S  = prod_(k <= nI) Y[nattr - Ip[k]]^q_k                                     the G1 fixed-base sum over nI + 1 bases, no addend
+ *   W  = tilde_X * tilde_sigma_ * prod_I tilde_Y[i]^a_i                          the G2 fixed-base sum with the addend tilde_X, one G2 addition per lane
+ *   ok = [ e(sigma1_, W) * e(C, tilde_Y[nattr]) == e(sigma2_, tilde_g) ] and [ e(sigma3_, tilde_g) == e(S, tilde_sigma_) ]
+ * Each equation is evaluated as the reference's header does (liner_pair.hpp:291-350): Miller values, conjugate of the right side, multiply, one
+ * final exponentiation, is_unity.  W and tilde_sigma_ are per-lane G2 points nobody has checked for subgroup membership, so no equation is split
+ * bilinearly over them and no conjugate is replaced by a negated point: (sigma1_, W) and (S, tilde_sigma_) run the running-point Miller loop
+ * (c12381_miller_batch), (C, tilde_Y[nattr]), (sigma2_, tilde_g) and (sigma3_, tilde_g) the line tables (c12381_pair_product_fixed_g2_batch with
+ * C12381_F_MILLER_ONLY, the same bytes for every Q), and the GT entries join them, both equations as one column of 2 n lanes.
+ * Key records: Y[nattr - idx[k]], Y[0], tilde_Y[idx[k]] and tilde_Y[nattr] alone are read and decoded; an undecodable record that verify never
+ * touches has no effect.  C12381_E_ARG also for nI + 1 > C12381_G1_FIXED_SUM_MAX.
+ * Status: ok[j] = 1 / 0; 0xff: one of the five points does not decode, c0 or s0 is >= r, or — behind a matching c0 — a disclosed a_i is >= r.  Key
+ * failure: g, tilde_g, tilde_X or a USED record of Y / tilde_Y does not decode.
+ * Workspace (c12381_trim releases it): per presentation of a chunk 6632 + 120 nI bytes, besides the workspaces of the entries used.  The two
+ * line-table products share one table position, which alternates between tilde_Y[nattr] and tilde_g: each chunk rebuilds that table twice. */
+int c12381_ac_rps_verify_batch(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* pk_243, const uint8_t* Y_49,
+                               const uint8_t* tY_97, const uint8_t* pres_389, const uint8_t* attr_48, uint8_t* ok);
+int c12381_ac_rps_verify_batch_dev(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* pk_243, const uint8_t* Y_49,
+                                   const uint8_t* tY_97, const uint8_t* pres_389, const uint8_t* attr_48, uint8_t* ok);
+/* c12381_ac_rps_pres_batch: pres(m_j, attr_j, sig_j, I, cache_j, usk_j, pk) (pres.cpp:8-62) with the caller's randomness.
+ *   attr_48  the holder's WHOLE span, n x nattr fields lane-major in attribute order; every field is range-checked, as materialize does
+ *   rnd      per presentation r, t, rho in the order the reference draws them, 32 big-endian bytes each; any value below 2^256, reduced mod r first
+ * Per presentation, negation being the reference's Zp negation (-0 = 0), J the indices outside I:
+ *   sigma1_ = h^r                    sigma2_ = sigma^r * sigma1_^t              ONE k = 2 product
+ *   C = sigma1_^z                    C0 = sigma1_^rho                           one generic G1 column of 2 n lanes
+ *   tilde_sigma_ = tilde_g^t * tilde_H                                          c12381_g2_mul_fixed_batch and one G2 addition per lane
+ *   sigma3_ = prod_(k <= nI) Y[nattr - Ip[k]]^(t q_k) * prod_(k in K) Y[k]^e_k,  q_k as above from the encodings just made,
+ *             e_k = sum over the ii <= nI with j = k + Ip[ii] - nattr - 1 in J of q_ii a_j mod r,  K = the k of [0, 2 nattr] with at least one such ii
+ *   c0 as above,  s0 = rho + (-c0) z
+ * sigma3_ is ONE sum over one base list through the tables of c12381_g1_mul_fixed_sum_batch (its workspace, its routes): the nI + 1 fixed positions
+ * in the order of Ip — verify's list, so the two entries share those tables — then K ascending.  The list holds exactly the reference's terms: a
+ * record that appears in both parts takes two positions and no zero scalar is put anywhere, because multiply(P, 0) and k1 P + k2 P differ from the
+ * merged forms for points outside G1.  That is why pres returns C12381_E_ARG when nI + 1 + |K| > C12381_G1_FIXED_SUM_MAX = 32: every set fits for
+ * nattr <= 12, larger credentials only with sets whose K is small enough — (16, {0, 3}) fills the list exactly, (13, {1 .. 11}) is the smallest shape
+ * refused — (verify and redact take up to 32 attributes).  With J empty sigma3_ is the
+ * fixed part alone.
+ * Outputs: pres_389 (n x 389 bytes), status (n bytes): 0, or 0xff — and a record of 0xff bytes — where the reference would throw: h, sigma, tilde_M
+ * (decoded though unused) or tilde_H does not decode, or z or ANY attribute is >= r; the other lanes are unaffected and the call returns C12381_OK.
+ * The reference materialises pk.Y here: g, tilde_g, tilde_X or ANY of the 2 nattr + 1 records of Y_49 not decoding is a key failure.
+ * NOT constant-time: the scalar multiplications and the table look-ups take data-dependent paths and addresses.  The secrets the call is given (the
+ * attributes, z, r, t, rho) and values derived from them stay in the context's device workspaces (and, for the host form, its staging buffer)
+ * until a later call overwrites them or c12381_trim frees them; nothing is wiped.
+ * Workspace: per presentation of a chunk 2293 + 88 nI + 32 (nI + 1 + |K|) bytes, besides the workspaces of the entries used. */
+int c12381_ac_rps_pres_batch(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* pk_243, const uint8_t* Y_49,
+                             const uint8_t* attr_48, const uint8_t* sig_195, const uint8_t* cache_97, const uint8_t* usk_48, const uint8_t* rnd,
+                             uint8_t* pres_389, uint8_t* status);
+int c12381_ac_rps_pres_batch_dev(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* pk_243, const uint8_t* Y_49,
+                                 const uint8_t* attr_48, const uint8_t* sig_195, const uint8_t* cache_97, const uint8_t* usk_48, const uint8_t* rnd,
+                                 uint8_t* pres_389, uint8_t* status);
+/* c12381_ac_rps_redact_batch: redact(attr_j, sig_j, I, pk) (redact.cpp:6-16): tilde_H = tilde_M / prod_I tilde_Y[i]^a_i, evaluated as the G2 fixed-base
+ * sum over the used tilde_Y with no addend (the positions of verify's sum: shared tables), negated and added to tilde_M — miracl_core::sub is
+ * add-the-negative.  nI = 0: tilde_M re-encoded.  There is no pk_243: redact never parses pk.fixed_part.  attr_48 is the holder's WHOLE span, n x
+ * nattr fields lane-major, but only the disclosed fields are read and range-checked.
+ * Outputs: cache_97 (n x 97 bytes), status (n bytes): 0, or 0xff — and a record of 0xff bytes — where the reference would throw: h, sigma (decoded
+ * though unused) or tilde_M does not decode, or a disclosed a_i is >= r.  Key failure: a USED record tilde_Y[idx[k]] does not decode.
+ * NOT constant-time, and nothing is wiped, as for pres: the disclosed attributes and the values derived from them stay in the workspaces.
+ * Workspace: per credential of a chunk 872 + 32 nI bytes, besides the workspaces of the entries used. */
+int c12381_ac_rps_redact_batch(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* tY_97, const uint8_t* attr_48,
+                               const uint8_t* sig_195, uint8_t* cache_97, uint8_t* status);
+int c12381_ac_rps_redact_batch_dev(c12381_ctx* ctx, size_t n, size_t nattr, size_t nI, const uint32_t* idx, const uint8_t* tY_97, const uint8_t* attr_48,
+                                   const uint8_t* sig_195, uint8_t* cache_97, uint8_t* status);
+
 #ifdef __cplusplus
 }
 #endif
