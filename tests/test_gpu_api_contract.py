@@ -372,45 +372,63 @@ def test_device_pointer_entry_points_report_through_sync(ctx):
     assert res[:49] == b"\xff" * 49 and res[49:] == cat(g["mul49"])[49:]
 
 
-def test_stream_ordering_through_events():
-    """include/c12381_hip.h "Stream ordering": inputs filled on ANOTHER stream behind a long-running kernel, outputs consumed on a third one —
-    c12381_wait_event / c12381_record_event are the only edges (no host-side wait anywhere between the fill and the read-back).  The input
-    buffers hold a different valid batch beforehand, so a library that did not wait would return that batch's (wrong) results, not an error."""
-    import torch
-    from crypto12381_amd import Context
-    dev = torch.device("cuda", 0)
-    g = golden("g1")
-    pts, sc = cat(g["points"]), cat(g["scalars"])
-    n = len(sc) // 32
-    c = Context(0)                                                                 # its own stream, unknown to torch
-    try:
+def _event_case(c, entry, orc):
+    """(arguments, the same with another valid batch in every input, expected outputs) of one entry of test_stream_ordering_through_events"""
+    if entry == "g1_mul_batch_dev":                                                # the golden batch; the stale one is made by the library
+        g = golden("g1")
+        pts, sc = cat(g["points"]), cat(g["scalars"])
+        n = len(sc) // 32
         stale_p = c.g1_mul(pts, scalars(77, n), 96)                                # another valid batch
         stale_s = scalars(78, n)
         want, stale_want = cat(g["mul96"]), c.g1_mul(stale_p, stale_s, 96)
         assert want != stale_want
-        src_p = torch.frombuffer(bytearray(pts), dtype=torch.uint8).pin_memory()
-        src_s = torch.frombuffer(bytearray(sc), dtype=torch.uint8).pin_memory()
-        dp = torch.frombuffer(bytearray(stale_p), dtype=torch.uint8).to(dev)
-        ds = torch.frombuffer(bytearray(stale_s), dtype=torch.uint8).to(dev)
-        out = torch.zeros(96 * n, dtype=torch.uint8, device=dev)
-        host = torch.zeros(96 * n, dtype=torch.uint8).pin_memory()
+        return [n, In(pts), In(sc), Out(96 * n), Fmt(96)], [n, In(stale_p), In(stale_s), Out(96 * n), Fmt(96)], [want]
+    import stream_cases                                                            # entries with side-stream work: batches A and B of their rows
+    row = stream_cases.BY_ID[{"bbs_plus_verify_wire_batch_dev": "bbs_plus_verify_wire", "g1_msm_dev[2^15]": "g1_msm[2^15]"}[entry]]
+    a, want, _ = stream_cases.case(orc, row, v=0)
+    b, stale_want, _ = stream_cases.case(orc, row, v=1)
+    assert want != stale_want
+    return a, b, want
+
+
+@pytest.mark.parametrize("entry", ["g1_mul_batch_dev", "bbs_plus_verify_wire_batch_dev", "g1_msm_dev[2^15]"])
+def test_stream_ordering_through_events(entry, oracle_port):
+    """include/c12381_hip.h "Stream ordering": inputs filled on ANOTHER stream behind a long-running kernel, outputs consumed on a third one —
+    c12381_wait_event / c12381_record_event are the only edges (no host-side wait anywhere between the fill and the read-back).  The input
+    buffers hold a different valid batch beforehand, so a library that did not wait would return that batch's (wrong) results, not an error.
+    g1_mul_batch_dev never leaves the context's stream; the wire verification forks the side stream per chunk and the bucket product of 2^15
+    terms sorts its window segments on two streams: c12381_record_event covers that work too ("which is joined first")."""
+    import torch
+    from crypto12381_amd import Context
+    dev = torch.device("cuda", 0)
+    c = Context(0)                                                                 # its own stream, unknown to torch
+    try:
+        args, stale, want = _event_case(c, entry, oracle_port)
+        ins = [i for i, a in enumerate(args) if isinstance(a, In)]
+        outs = [i for i, a in enumerate(args) if isinstance(a, Out)]
+        src = {i: torch.frombuffer(bytearray(bytes(args[i])), dtype=torch.uint8).pin_memory() for i in ins}
+        d = {i: torch.frombuffer(bytearray(bytes(stale[i])), dtype=torch.uint8).to(dev) for i in ins}
+        d.update({i: torch.zeros(int(args[i]), dtype=torch.uint8, device=dev) for i in outs})
+        host = {i: torch.zeros(int(args[i]), dtype=torch.uint8).pin_memory() for i in outs}
         torch.cuda.synchronize(dev)
         prod, cons = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
         ready, done = torch.cuda.Event(), torch.cuda.Event()
         with torch.cuda.stream(prod):
             torch.cuda._sleep(400_000_000)                                         # ~0.2 s of spinning in front of the fill
-            dp.copy_(src_p, non_blocking=True)
-            ds.copy_(src_s, non_blocking=True)
+            for i in ins:
+                d[i].copy_(src[i], non_blocking=True)
             ready.record(prod)
         c.wait_event(ready.cuda_event)
-        c.g1_mul_dev(n, dp.data_ptr(), ds.data_ptr(), out.data_ptr(), 96)
+        rc = getattr(c.lib, "c12381_" + entry.split("[")[0])(c.h, *[_arg(d[i].data_ptr() if i in d else a) for i, a in enumerate(args)])
+        assert rc == 0
         done.record(cons)                                                          # creates the handle; re-recorded on the library's stream below
         c.record_event(done.cuda_event)
         with torch.cuda.stream(cons):
             cons.wait_event(done)
-            host.copy_(out, non_blocking=True)
+            for i in outs:
+                host[i].copy_(d[i], non_blocking=True)
         cons.synchronize()                                                         # the first host-side wait
-        assert bytes(host.numpy()) == want
+        assert [bytes(host[i].numpy()) for i in outs] == want
         assert c.sync() == 0
         assert c.lib.c12381_wait_event(c.h, None) == E_ARG and c.lib.c12381_record_event(c.h, None) == E_ARG
     finally:
@@ -431,10 +449,14 @@ def test_trim_releases_the_workspaces_and_the_next_call_rebuilds_them():
         k = len(gp["gt_pow_exp"])
         pw = c.gt_op("pow", cat(gp["gt"])[:576 * k], cat(gp["gt_pow_exp"]))
         assert pw == cat(gp["gt_pow"])
+        lanes = 1 << 14                                                           # a table slab of 2816 B per lane (c12381_hip.hip, G1_CHUNK): 46 MB
+        reps = lanes // (len(sc) // 32) + 1
+        big = c.g1_mul((pts * reps)[:96 * lanes], (sc * reps)[:32 * lanes], 49)
+        assert big[:len(cat(g["mul49"]))] == cat(g["mul49"])
         torch.cuda.synchronize()
         free_before = torch.cuda.mem_get_info(0)[0]
         c.trim()
-        assert torch.cuda.mem_get_info(0)[0] >= free_before                      # nothing is held back
+        assert torch.cuda.mem_get_info(0)[0] >= free_before + 2816 * lanes       # at least that batch's table slab came back
         assert c.g1_mul_fixed(gen, sc, 49) == fixed
         assert c.g1_mul(pts, sc, 49) == cat(g["mul49"])
         assert c.gt_op("pow", cat(gp["gt"])[:576 * k], cat(gp["gt_pow_exp"])) == pw
