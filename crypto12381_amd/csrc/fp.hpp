@@ -612,6 +612,19 @@ C12381_HD void fp_mul_msqr2(fp& r, const fp& a, const fp& b, const fp& c) {
     r = t;
 }
 
+// r = (a^2 + c*d) / R with ONE reduction: a square's 105 column products beside the 196 of a general one (the X3 of the Eisenstein loop's
+// mixed addition, s^2 - H^2 (U2 + X1), with c = -H^2).  The square's cross terms run against the raw limb multiple 2a.
+// Needs 14*(LBa^2 + LBc*LBd) + 14*2^56 + 2^40 < 2^63: a lazy difference of two reduction outputs (2^29), c a reduction output and d a lazy
+// sum of two give 14 * 6 * 2^56 = 2^62.4.  Counted by its pieces: 2 x 27 columns, 1 reduction.
+C12381_HD void fp_sqr_madd(fp& r, const fp& a, const fp& c, const fp& d) {
+    fp t, a2;
+    fp_raw_dbl(a2, a);
+    fp_reduce_cols(t, [&](int k, int64_t& acc) { fp_col_sqr_acc(acc, a, a2, a, k); fp_col_acc(acc, c, d, k); });
+    C12381_BOUNDS({ check_actual(a, "fp_sqr_madd"); check_actual(c, "fp_sqr_madd"); check_actual(d, "fp_sqr_madd");
+                    set_lazy_bounds(t, a.lb * a.lb + c.lb * d.lb, a.vb * a.vb + c.vb * d.vb, "fp_sqr_madd"); })
+    r = t;
+}
+
 // ------------------------------------------------------------------ canonical form, tests
 // Leaves Montgomery form and fully reduces: r = a / R mod p as canonical limbs in [0, p).
 // (FP_redc fp_BLS12381.cpp:234 + FP_reduce :549).  Cost: one fp_mul + compare/subtract.

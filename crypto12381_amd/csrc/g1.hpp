@@ -857,15 +857,48 @@ C12381_HD void eis_fetch(fp& x, fp& y, const int32_t* lane_tab, uint32_t code) {
     eis_load_field(x, ent, 1 + (int)(u >= 3u ? u - 3u : u), 4.0);
     g1_sched_fence();
 }
-// acc += psi^unit T[entry]: the sign of y is (-1)^unit
+// g1j_madd in NINE reductions, for this loop alone (the k-term sums keep g1j_madd: there this form spills).  H^3 and V = X1 H^2 are not
+// formed: X3 = s^2 - H^2 (U2 + X1) is a square and a product under one reduction (H^3 + 2V = H^2 (H + 2 X1)), and
+// Y3 = s (V - X3) - Y1 H^3 = H^2 (s X1 - Y1 H) - s X3 is two reductions of two products each.  3S + 9M.  The same values mod p, on the same
+// Z3 = Z1 H: Z = 0 stays absorbing, and the lanes with H = 0 are the ones g1j_madd finds.
+// Signs: with n = -s = Y1 - S2 (a difference either way round) every product but those by H^2 enters with a plus, and -H^2, negated once,
+// serves both: X3 = n^2 + (-H^2)(U2 + X1), W = n X1 + Y1 H = -(s X1 - Y1 H), Y3 = (-H^2) W + n X3.
+C12381_HD void g1j_madd_eis(g1j& r, const g1j& p, const fp& x2, const fp& y2) {
+    fp zz, zzz, u2, s2, h, n, t, hh, nhh, w, x3, y3, z3;
+    fp_sqr(zz, p.z);
+    fp_mul(u2, x2, zz);                                  // U2 = x2 Z1^2
+    fp_mul(zzz, p.z, zz);
+    fp_mul(s2, y2, zzz);                                 // S2 = y2 Z1^3
+    fp_sub(h, u2, p.x);                                  // H = U2 - X1
+    fp_sub(n, p.y, s2);                                  // n = Y1 - S2 = -s
+    fp_add(t, u2, p.x);                                  // U2 + X1
+    fp_mul(z3, p.z, h);                                  // Z3 = Z1 H
+    fp_sqr(hh, h);
+    fp_raw_neg(nhh, hh);
+    fp_sqr_madd(x3, n, nhh, t);                          // X3 = s^2 - H^2 (U2 + X1)
+    fp_mul2<false>(w, n, p.x, p.y, h);                   // W = -(s X1 - Y1 H)
+    fp_mul2<false>(y3, nhh, w, n, x3);                   // Y3 = H^2 (s X1 - Y1 H) - s X3
+    r.x = x3; r.y = y3; r.z = z3;
+}
+// acc += psi^unit T[entry]: the sign of y is (-1)^unit.  g1j_add_signed's steps over g1j_madd_eis.
 C12381_HD void g1j_add_eis(g1j& acc, bool& acc_inf, const fp& x, const fp& y, uint32_t code) {
-    g1j_add_signed(acc, acc_inf, x, y, ((code >> 4) & 1u) != 0u, (code & 15u) == G1E_NONE);
+    const bool neg = ((code >> 4) & 1u) != 0u, keep = (code & 15u) == G1E_NONE;
+    fp ny, ys, one;
+    fp_neg(ny, y);
+    fp_select(ys, neg, ny, y);
+    g1j r;
+    g1j_madd_eis(r, acc, x, ys);
+    fp_one(one);
+    fp_select(r.x, acc_inf, x, r.x); fp_select(r.y, acc_inf, ys, r.y); fp_select(r.z, acc_inf, one, r.z);
+    fp_select(acc.x, keep, acc.x, r.x); fp_select(acc.y, keep, acc.y, r.y); fp_select(acc.z, keep, acc.z, r.z);
+    acc_inf = acc_inf && keep;
 }
 
 // Forward co-Z pass: ten ZADDUs.  Step i adds the running addend psi^(u_i) P to entry i (entry 0 = P on Z_0 = 1) and gives entry i + 1 and the
 // addend on Z_(i+1) = Z_i h_i; between two steps the addend passes through a unit (one product by beta or beta^2 where u_i - u_(i-1) is no
-// multiple of 3, a sign on y).  Leaves entries 0..9 as (Y_i, X_i, h_i), entry 10 finished, and fields y, x, beta^2 x of entry 0 finished
-// from the last addend, which is P on Z_10 = Z_T = h_0 ... h_9; h_0 stays in entry 0 until the backward pass has run.
+// multiple of 3, a sign on y).  Leaves entries 0..9 as (Y_i, X_i, h_i), entry 10 finished, and fields y, x of entry 0 finished
+// from the last addend, which is P on Z_10 = Z_T = h_0 ... h_9; h_0 stays in entry 0 until the backward pass has run, and beta x, beta^2 x
+// of entry 0 follow it there.
 C12381_HD void g1e_forward(int32_t* lane_tab, const fp& px, const fp& py, const fp& beta, const fp& beta2) {
     fp x1 = px, y1 = py, xj = px, yj = py, xn, yn, h, hn, bx;
 #pragma unroll 1
@@ -887,13 +920,21 @@ C12381_HD void g1e_forward(int32_t* lane_tab, const fp& px, const fp& py, const 
     eis_store_field(last, 0, yj, 4.0); eis_store_field(last, 1, xj, 4.0);
     fp_mul(bx, xj, beta); eis_store_field(last, 2, bx, 4.0);
     fp_mul(bx, xj, beta2); eis_store_field(last, 3, bx, 4.0);
-    eis_store_field(lane_tab, 0, y1, 4.0); eis_store_field(lane_tab, 1, x1, 4.0);
-    fp_mul(bx, x1, beta2); eis_store_field(lane_tab, 3, bx, 4.0);
+    eis_store_field(lane_tab, 0, y1, 4.0); eis_store_field(lane_tab, 1, x1, 2.0);   // x1 is a product: g1_scalar_mul_eis adds beta x1 to it
+}
+// beta^2 x = -(x + beta x) (1 + beta + beta^2 = 0): a negated lazy sum and one carry round where a product by beta^2 stood.  x and beta x
+// are products here (value bounds at most 2 and 1 and a little, so the field's cap of 4 holds; the x of entry 10 is a ZADDU's X3, value
+// bound 3, and keeps its product).
+C12381_HD void g1e_beta2x(fp& r, const fp& x, const fp& bx) {
+    fp t;
+    fp_add(t, x, bx);
+    fp_neg(t, t);
+    fp_norm1(r, t);
 }
 // One step of the backward pass: mu <- mu h_i (mu = h_i where the chain starts: `first`, wave-uniform), and entry i = (Y_i, X_i, h_i) becomes
 // the finished record of the point on Z_i mu.
-C12381_HD void g1e_backward(int32_t* ent, fp& mu, bool first, const fp& beta, const fp& beta2) {
-    fp m2, m3, x, y, h, bx;
+C12381_HD void g1e_backward(int32_t* ent, fp& mu, bool first, const fp& beta) {
+    fp m2, m3, x, y, h, bx, b2x;
     eis_load_field(y, ent, 0, 32.0); eis_load_field(x, ent, 1, 32.0); eis_load_field(h, ent, 2, 32.0);
     if (first) mu = h; else fp_mul(mu, mu, h);
     fp_sqr(m2, mu);
@@ -902,7 +943,26 @@ C12381_HD void g1e_backward(int32_t* ent, fp& mu, bool first, const fp& beta, co
     fp_mul(y, y, m3);
     eis_store_field(ent, 0, y, 4.0); eis_store_field(ent, 1, x, 4.0);
     fp_mul(bx, x, beta); eis_store_field(ent, 2, bx, 4.0);
-    fp_mul(bx, x, beta2); eis_store_field(ent, 3, bx, 4.0);
+    g1e_beta2x(b2x, x, bx); eis_store_field(ent, 3, b2x, 4.0);
+}
+// The lane's table of P = (px, py): the forward pass, then the backward pass: entry i times mu_i^2, mu_i^3 with mu_i = h_i ... h_9 =
+// Z_T / Z_i; Z_T = h_0 mu_1, and entry 0's beta x, beta^2 x once h_0 has been read.
+C12381_HD void g1e_table(int32_t* lane_tab, const fp& px, const fp& py) {
+    fp beta, beta2;
+    fp_set_const(beta, FP_BETA_A);
+    fp_set_const(beta2, FP_BETA_B);                             // beta^2, the other cube root of unity
+    g1e_forward(lane_tab, px, py, beta, beta2);
+    fp mu, zt, h0, x, bx, b2x;
+#pragma unroll 1
+    for (int i = G1E_TAB - 2; i >= 1; --i) g1e_backward(lane_tab + i * G1E_ENT_DWORDS, mu, i == G1E_TAB - 2, beta);
+    eis_load_field(h0, lane_tab, 2, 32.0);
+    eis_load_field(x, lane_tab, 1, 2.0);
+    fp_mul(zt, mu, h0);
+    fp_mul(bx, x, beta);
+    eis_store_field(lane_tab, 2, bx, 4.0);
+    g1e_beta2x(b2x, x, bx);
+    eis_store_field(lane_tab, 3, b2x, 4.0);
+    eis_store_zt(lane_tab, zt);
 }
 // r = (x1, y1) + (x2, y2), both affine on the table's curve: g1j_madd with Z1 = 1, 4M + 2S in five reductions, Z3 = x2 - x1.  Exceptional
 // (Z3 = 0) when the operands are equal or opposite.
@@ -940,21 +1000,7 @@ C12381_HD bool g1_scalar_mul_eis(g1p& acc, const fp& px, const fp& py, bool p_is
     uint32_t kd[10];
     eis_scalar_digits(kd, kin);
 
-    fp beta, beta2;
-    fp_set_const(beta, FP_BETA_A);
-    fp_set_const(beta2, FP_BETA_B);                             // beta^2, the other cube root of unity
-    g1e_forward(lane_tab, px, py, beta, beta2);
-    {   // backward pass: entry i times mu_i^2, mu_i^3 with mu_i = h_i ... h_9 = Z_T / Z_i; Z_T = h_0 mu_1
-        fp mu, zt, h0, x, bx;
-#pragma unroll 1
-        for (int i = G1E_TAB - 2; i >= 1; --i) g1e_backward(lane_tab + i * G1E_ENT_DWORDS, mu, i == G1E_TAB - 2, beta, beta2);
-        eis_load_field(h0, lane_tab, 2, 32.0);
-        eis_load_field(x, lane_tab, 1, 4.0);
-        fp_mul(zt, mu, h0);
-        fp_mul(bx, x, beta);
-        eis_store_field(lane_tab, 2, bx, 4.0);
-        eis_store_zt(lane_tab, zt);
-    }
+    g1e_table(lane_tab, px, py);
 
     // the top two digits start the accumulator: the point of digit 42 (Z = 1), or a table point plus P where position 43 is not empty
     g1j a;
