@@ -161,6 +161,10 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp] + [vp] * 9
         for name in ("c12381_ac_rps_redact_batch", "c12381_ac_rps_redact_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp] + [vp] * 5
+        for name in ("c12381_mhac_bbs_verify_batch", "c12381_mhac_bbs_verify_batch_dev"):      # include/c12381_mhac.h
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz, vp] + [vp] * 9
+        for name in ("c12381_mhac_bbs_pres_batch", "c12381_mhac_bbs_pres_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, sz, vp, sz, vp] + [vp] * 15
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -798,6 +802,41 @@ class Context:
         cache, st = ctypes.create_string_buffer(max(97 * n, 1)), ctypes.create_string_buffer(max(n, 1))
         self._ck(self.lib.c12381_ac_rps_redact_batch(self.h, n, nattr, nI, arr, _p(tY97), _p(attr48), _p(sigs195), _p(cache), _p(st)), allow_point=not strict)
         return cache.raw[:97 * n], st.raw[:n]
+
+    def mhac_bbs_verify(self, pp146: bytes, h49: bytes, pk97: bytes, prv, rev, crev49: bytes, fixed242: bytes, z48: bytes, zhp48: bytes, pub48: bytes,
+                        strict: bool = True, dev: bool = False) -> bytes:
+        """MHAC-bbs verify_pres from the wire formats (include/c12381_mhac.h): pp.g1_g2 (146 B), pp.h (m x 49 B), pk (97 B), the index sets prv (in
+        the caller's order) and rev, then per presentation PresType.C_rev (49 B), Pres.fixed_part (242 B), Pres.z (nPrv x 48 B), Pres.z_hid_pub
+        (nHidPub x 48 B) and the REVEALED public values (nRevPub x 48 B, ascending Pub position).  One byte per presentation: 1 / 0, or 0xff where
+        the reference would throw.  A pp / used h / pk that does not decode is C12381_E_POINT (every byte 0xff): raised when strict, returned as
+        bytes otherwise.  dev: through the _dev form on device copies of the buffers."""
+        n, m = len(fixed242) // 242, len(h49) // 49
+        (pa, nP), (ra, nR) = self._idx(prv), self._idx(rev)
+        ins = [pp146, h49, pk97, crev49, fixed242, z48 or None, zhp48 or None, pub48 or None]
+        if dev:
+            return self._rps_dev(lambda p, o: self.lib.c12381_mhac_bbs_verify_batch_dev(self.h, n, m, nP, pa, nR, ra, *p, *o), ins, [n], strict)[0]
+        out = ctypes.create_string_buffer(max(n, 1))
+        self._ck(self.lib.c12381_mhac_bbs_verify_batch(self.h, n, m, nP, pa, nR, ra, *(_p(b) for b in ins), _p(out)), allow_point=not strict)
+        return out.raw[:n]
+
+    def mhac_bbs_pres(self, pp146: bytes, h49: bytes, prv, rev, t: int, A49: bytes, D49: bytes, lam48: bytes, eshare48: bytes, ashare48: bytes,
+                      crev49: bytes, cpub49: bytes, pub48: bytes, rnd: bytes, strict: bool = True, dev: bool = False):
+        """MHAC-bbs cred_pres from the wire formats for t parties: per presentation creds.A and group.D (49 B each), group.lambda and the parties'
+        e_share (t x 48 B each), their a_share rows (t x nPrv x 48 B, party-major), PresType.C_rev / C_pub (49 B each), the WHOLE public span
+        (nPub x 48 B) and the caller's randomness (r, alpha, beta_share, beta_share_j, gamma_share: (2 + (t - 1) nPrv + nHid + t) x 32 B) ->
+        (n x 242-byte Pres.fixed_part, n x nPrv x 48-byte Pres.z, n x nHidPub x 48-byte Pres.z_hid_pub, n status bytes: 0, or 0xff — and records
+        of 0xff — where the reference would throw).  A pp / used h that does not decode is C12381_E_POINT (every byte 0xff): raised when strict,
+        returned as bytes otherwise.  Not constant-time."""
+        n, m = len(A49) // 49, len(h49) // 49
+        (pa, nP), (ra, nR) = self._idx(prv), self._idx(rev)
+        nhp = max(m - nP - nR, 0)
+        ins = [pp146, h49, A49, D49, lam48, eshare48, ashare48 or None, crev49, cpub49, pub48 or None, rnd]
+        sizes = [242 * n, 48 * nP * n, 48 * nhp * n, n]
+        if dev:
+            return tuple(self._rps_dev(lambda p, o: self.lib.c12381_mhac_bbs_pres_batch_dev(self.h, n, m, t, nP, pa, nR, ra, *p, *o), ins, sizes, strict))
+        outs = [ctypes.create_string_buffer(max(k, 1)) for k in sizes]
+        self._ck(self.lib.c12381_mhac_bbs_pres_batch(self.h, n, m, t, nP, pa, nR, ra, *(_p(b) for b in ins), *(_p(o) for o in outs)), allow_point=not strict)
+        return tuple(o.raw[:k] for o, k in zip(outs, sizes))
 
     def _rps_dev(self, call, ins, out_sizes, strict):
         """the _dev form of an AC-rps entry on device copies of `ins` (bytes, or None for a null pointer): call(input pointers, output pointers), sync,

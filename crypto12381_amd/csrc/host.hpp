@@ -1,4 +1,4 @@
-// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip, api_ac_rbbs.hip, api_ac_rps.hip): the context and its
+// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip, api_ac_rbbs.hip, api_ac_rps.hip, api_mhac_bbs.hip): the context and its
 // workspaces, and the idioms every entry point is written in — launch, slab (host_layouts.hpp), host form.  Everything in namespace c12381_host
 // has external linkage and hidden visibility: the units call each other's helpers, the library exports the C ABI alone.  The comment at each
 // declaration names the unit that defines it.
@@ -29,7 +29,7 @@ struct c12381_ctx {
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
            WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_FB_G1_4, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
-           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_PS, WS_AC_BBS, WS_AC_RBBS, WS_AC_RPS, WS_COUNT };
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_PS, WS_AC_BBS, WS_AC_RBBS, WS_AC_RPS, WS_MHAC_BBS, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;
@@ -97,12 +97,12 @@ struct timed {
 
 // Host form.  The caller's inputs and outputs, (host pointer, bytes) each, laid out in WS_STAGE at 256-byte-aligned offsets.  stage() copies
 // every non-empty input in and hands back the device pointers (a null host pointer stays null); unstage() copies the outputs back after
-// the _dev call and ends with read_flag.  Up to 12 inputs and 3 outputs.  host_form: stage, the entry's _dev form on s.in[] / s.out[], unstage.
+// the _dev call and ends with read_flag.  Up to 12 inputs and 4 outputs.  host_form: stage, the entry's _dev form on s.in[] / s.out[], unstage.
 struct host_buf { const void* p; size_t bytes; };
 struct staging {
     const uint8_t* in[12] = {};
-    uint8_t* out[3] = {};
-    host_buf host_out[3] = {};
+    uint8_t* out[4] = {};
+    host_buf host_out[4] = {};
     size_t nout = 0;
 };
 int stage(c12381_ctx* c, staging& s, std::initializer_list<host_buf> ins, std::initializer_list<host_buf> outs);       // c12381_hip.hip

@@ -256,6 +256,38 @@ inline ac_rps_redact_slab ac_rps_redact_layout(void* base, size_t m, size_t nI) 
     return s;
 }
 
+// ---------------------------------------------------------------- MHAC-bbs (WS_MHAC_BBS): both slabs start behind the public block
+// The public block is ac_bbs_public's, read as: y49 / y96 the used h records gathered into the entry's base list (up to 32 positions) as they arrive
+// and decoded, g96 = g1 of pp (decoded, not used), g2 = g2 of pp and w of pk (pres: g2 alone), st = the statuses g1, g2, w (pres: 1), then the list's
+constexpr size_t MHAC_BBS_PUB_BYTES = AC_BBS_PUB_BYTES;
+// verify, per presentation of a chunk: B_, C_rev, A_ as they arrive (columns) and decoded — the terms of the k = 3 product —, their statuses, its
+// scalars -ch, zr, ze, the nb columns z .., zhp .. of the verify list, ch, the parse status, the product, the sum over the list, U compressed, the
+// pairing verdict, the transcript of nrp revealed values: 956 + 32 nb + 48 nrp bytes
+struct mhac_bbs_verify_slab { uint8_t *p49, *p96, *st_p, *sc3, *sca, *c32, *st, *r96, *s96, *u49, *okp, *tr; size_t bytes; };
+inline mhac_bbs_verify_slab mhac_bbs_verify_layout(void* base, size_t m, size_t nb, size_t nrp) {
+    carver f(base, MHAC_BBS_PUB_BYTES);
+    mhac_bbs_verify_slab s;
+    s.p49 = f.take(3 * 49 * m); s.p96 = f.take(3 * 96 * m); s.st_p = f.take(3 * m); s.sc3 = f.take(3 * 32 * m); s.sca = f.take(32 * nb * m);
+    s.c32 = f.take(32 * m); s.st = f.take(m); s.r96 = f.take(96 * m); s.s96 = f.take(96 * m); s.u49 = f.take(49 * m); s.okp = f.take(m);
+    s.tr = f.take((147 + 48 * nrp) * m + 4);
+    s.bytes = f.bytes;
+    return s;
+}
+// pres, per presentation of a chunk: C_pub, D, A, C_rev as they arrive (columns) and decoded (C_pub * D replaces D: C_pub * D | A is the 2 m-lane G1
+// column), their statuses and the parse status, r twice, the t + 1 columns alpha, gamma .., the `total` exponent columns of the pres list, the
+// column's output B_ | A_, the five term columns C_rev, A_ x 4 of the k-way products, the running U and one further point, the transcript:
+// 1692 + 32 (t + total) + 48 nrp bytes
+struct mhac_bbs_pres_slab { uint8_t *p49, *p96, *st_p, *st, *scr, *scu, *sch, *o96, *q96, *u96, *v96, *tr; size_t bytes; };
+inline mhac_bbs_pres_slab mhac_bbs_pres_layout(void* base, size_t m, size_t t, size_t total, size_t nrp) {
+    carver f(base, MHAC_BBS_PUB_BYTES);
+    mhac_bbs_pres_slab s;
+    s.p49 = f.take(4 * 49 * m); s.p96 = f.take(4 * 96 * m); s.st_p = f.take(4 * m); s.st = f.take(m); s.scr = f.take(2 * 32 * m);
+    s.scu = f.take(32 * (t + 1) * m); s.sch = f.take(32 * total * m); s.o96 = f.take(2 * 96 * m); s.q96 = f.take(5 * 96 * m); s.u96 = f.take(96 * m);
+    s.v96 = f.take(96 * m); s.tr = f.take((147 + 48 * nrp) * m + 4);
+    s.bytes = f.bytes;
+    return s;
+}
+
 // ---------------------------------------------------------------- pairing work queue (WS_PAIR_ST; the GT power: WS_POW_ST)
 // The figures of the queue kernels (api_pair.hip asserts them against kernels.hpp): 21 pairings per wavefront group, 4 wavefronts per
 // workgroup, a grid that fills the machine at 2 wavefronts per SIMD, and a queued group's state block in the tagged / the fenced form.

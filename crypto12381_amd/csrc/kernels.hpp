@@ -12,6 +12,7 @@
 //   k_ac_bbs.hip the AC-bbs credential stages (ac_bbs.hpp) around decompression, the fixed-base sums, the k-way products and PS verification
 //   k_ac_rbbs.hip the AC-rbbs credential stages (ac_rbbs.hpp): the same, with the q_i hashes, the exponents of redact and a second pairing equation
 //   k_ac_rps.hip the AC-rps credential stages (ac_rps.hpp): the q_k hashes over points and indices, the exponents of pres, G2 subtraction
+//   k_mhac_bbs.hip the MHAC-bbs credential stages (mhac_bbs.hpp): the index sets, the transcript over revealed values, the threshold responses
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -178,6 +179,12 @@ __global__ void __launch_bounds__(BLOCK, 2) ac_rps_pres_finish_kernel(size_t n, 
 __global__ void __launch_bounds__(BLOCK, 2) ac_rps_redact_prep_kernel(size_t n, size_t nattr, size_t nI, ac_bbs_order idx, const uint8_t* attr48, const uint8_t* sig195, uint8_t* p49, uint8_t* p97, uint8_t* sca, uint8_t* st);
 __global__ void __launch_bounds__(BLOCK, 2) ac_rps_g2_sub_kernel(size_t n, const uint8_t* a192, const uint8_t* b192, uint8_t* out, int fmt, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) ac_rps_redact_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* h97, uint8_t* cache97, uint8_t* status, int* bad_flag);
+// k_mhac_bbs.hip: MHAC-bbs credential presentation and verification (mhac_bbs.hpp; the index sets travel by value)
+struct mhac_bbs_sets;
+__global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_verify_prep_kernel(size_t n, size_t nz, size_t nhp, size_t nrp, const uint8_t* crev49, const uint8_t* fixed242, const uint8_t* z48, const uint8_t* zhp48, const uint8_t* pub48, uint8_t* p49, uint8_t* sc3, uint8_t* sca, uint8_t* c32, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_verify_finish_kernel(size_t n, size_t nrp, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* p96, const uint8_t* u49, const uint8_t* pub48, const uint8_t* c32, const uint8_t* okp, uint8_t* tr, uint8_t* ok, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_pres_prep_kernel(size_t n, size_t t, mhac_bbs_sets s, const uint8_t* A49, const uint8_t* D49, const uint8_t* crev49, const uint8_t* cpub49, const uint8_t* lam48, const uint8_t* eshare48, const uint8_t* ashare48, const uint8_t* pub48, const uint8_t* rnd, uint8_t* p49, uint8_t* scr, uint8_t* scu, uint8_t* sch, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_pres_finish_kernel(size_t n, size_t t, mhac_bbs_sets s, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* o96, const uint8_t* u96, const uint8_t* lam48, const uint8_t* eshare48, const uint8_t* ashare48, const uint8_t* pub48, const uint8_t* rnd, uint8_t* tr, uint8_t* fixed242, uint8_t* z48, uint8_t* zhp48, uint8_t* status, int* bad_flag);
 // k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
 constexpr int TABLE_ARRAY_MAX = 32;
 struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };
