@@ -165,6 +165,14 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz, vp] + [vp] * 9
         for name in ("c12381_mhac_bbs_pres_batch", "c12381_mhac_bbs_pres_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz, sz, sz, vp, sz, vp] + [vp] * 15
+        for name in ("c12381_mhac_bbs_attr_batch", "c12381_mhac_bbs_attr_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, sz, sz, vp] + [vp] * 6
+        for name in ("c12381_mhac_bbs_iss_batch", "c12381_mhac_bbs_iss_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, sz, sz, vp] + [vp] * 10
+        for name in ("c12381_mhac_bbs_group_batch", "c12381_mhac_bbs_group_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz] + [vp] * 8
+        for name in ("c12381_mhac_bbs_type_batch", "c12381_mhac_bbs_type_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz, vp] + [vp] * 6
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -837,6 +845,60 @@ class Context:
         outs = [ctypes.create_string_buffer(max(k, 1)) for k in sizes]
         self._ck(self.lib.c12381_mhac_bbs_pres_batch(self.h, n, m, t, nP, pa, nR, ra, *(_p(b) for b in ins), *(_p(o) for o in outs)), allow_point=not strict)
         return tuple(o.raw[:k] for o, k in zip(outs, sizes))
+
+    def _mhac_call(self, name, head, ins, sizes, strict, dev, null_out=()):
+        """one MHAC-bbs issuance entry in its host or its _dev form: head = the scalar arguments and index arrays, ins = the input buffers (None: a
+        null pointer), sizes = the byte counts of the outputs; null_out: the positions of outputs passed as NULL (returned as b"")"""
+        if dev:
+            fn = getattr(self.lib, name + "_dev")
+            got = self._rps_dev(lambda p, o: fn(self.h, *head, *p, *(None if i in null_out else x for i, x in enumerate(o))), ins, sizes, strict)
+            return tuple(b"" if i in null_out else g for i, g in enumerate(got))
+        outs = [ctypes.create_string_buffer(max(k, 1)) for k in sizes]
+        self._ck(getattr(self.lib, name)(self.h, *head, *(_p(b) for b in ins), *(None if i in null_out else _p(o) for i, o in enumerate(outs))),
+                 allow_point=not strict)
+        return tuple(b"" if i in null_out else o.raw[:k] for i, (o, k) in enumerate(zip(outs, sizes)))
+
+    def mhac_bbs_attr(self, pp146: bytes, h49: bytes, prv, t: int, nparties: int, rnd: bytes, strict: bool = True, dev: bool = False):
+        """MHAC-bbs generate_attributes from the caller's randomness (include/c12381_mhac.h): per credential m + nPrv (t - 1) scalars of 32 B (the
+        attributes, then the polynomial coefficients) -> (n x nPub x 48-byte public attributes, n x nparties x nPrv x 48-byte shares party-major,
+        n x nparties x 49-byte commitments).  A pp / used h that does not decode is C12381_E_POINT (every byte 0xff): raised when strict."""
+        m = len(h49) // 49
+        pa, nP = self._idx(prv)
+        n = len(rnd) // (32 * (m + nP * (t - 1)))
+        return self._mhac_call("c12381_mhac_bbs_attr_batch", (n, m, t, nparties, nP, pa), [pp146, h49, rnd],
+                               [48 * (m - nP) * n, 48 * nP * nparties * n, 49 * nparties * n], strict, dev)
+
+    def mhac_bbs_iss(self, pp146: bytes, h49: bytes, sk48: bytes, pub_idx, t: int, nparties: int, C49: bytes, pub48: bytes, rnd: bytes,
+                     strict: bool = True, dev: bool = False):
+        """MHAC-bbs cred_iss from the wire formats: the issuer's key (48 B), public_indexes in the caller's order, per credential the nparties
+        commitments (49 B each), the nPub public values (48 B each) and the randomness (e, then t - 1 coefficients: t x 32 B) -> (n x 49-byte A,
+        n x nparties x 48-byte e_share, n x nparties x 49-byte D, n status bytes: 0, or 0xff — and records of 0xff — where the reference would
+        throw).  sk >= r is C12381_E_ARG (every byte 0xff), a pp / used h that does not decode C12381_E_POINT.  Not constant-time."""
+        m, n = len(h49) // 49, len(rnd) // (32 * t)
+        ia, nPub = self._idx(pub_idx)
+        return self._mhac_call("c12381_mhac_bbs_iss_batch", (n, m, t, nparties, nPub, ia), [pp146, h49, sk48, C49, pub48 or None, rnd],
+                               [49 * n, 48 * nparties * n, 49 * nparties * n, n], strict, dev)
+
+    def mhac_bbs_group(self, S, nparties: int, nPrv: int, D49: bytes, eshare48: bytes | None, ashare48: bytes | None, strict: bool = True,
+                       dev: bool = False):
+        """MHAC-bbs make_pres_group for the parties S (in the caller's order), with the gather of their rows: per credential the nparties D records,
+        and optionally the nparties e_share fields and the nparties x nPrv a_share fields -> (n x t x 48-byte lambda, n x 49-byte D, the rows of S
+        of e_share (n x t x 48 B) and of a_share (n x t x nPrv x 48 B) — b"" where the input was None —, n status bytes: 0, or 0xff where a D
+        record of S does not decode)."""
+        n = len(D49) // (49 * nparties)
+        sa, t = self._idx(S)
+        null = tuple(i for i, b in ((2, eshare48), (3, ashare48 if nPrv else None)) if b is None)
+        return self._mhac_call("c12381_mhac_bbs_group_batch", (n, nparties, t, sa, nPrv), [D49, eshare48, ashare48 if nPrv else None],
+                               [48 * t * n, 49 * n, 48 * t * n, 48 * t * nPrv * n, n], strict, dev, null)
+
+    def mhac_bbs_type(self, pp146: bytes, h49: bytes, prv, rev, pub48: bytes, n: int | None = None, strict: bool = True, dev: bool = False):
+        """MHAC-bbs make_pres_type from the wire formats: the index sets of verify and pres and per presentation the WHOLE public span (nPub x 48 B)
+        -> (n x 49-byte C_rev, n x 49-byte C_pub, n status bytes: 0, or 0xff — and records of 0xff — where a public value is >= r).  n: the
+        number of presentations, taken from pub48 when not given (nPub = 0 needs it)."""
+        m = len(h49) // 49
+        (pa, nP), (ra, nR) = self._idx(prv), self._idx(rev)
+        n = len(pub48) // (48 * (m - nP)) if n is None else n
+        return self._mhac_call("c12381_mhac_bbs_type_batch", (n, m, nP, pa, nR, ra), [pp146, h49, pub48 or None], [49 * n, 49 * n, n], strict, dev)
 
     def _rps_dev(self, call, ins, out_sizes, strict):
         """the _dev form of an AC-rps entry on device copies of `ins` (bytes, or None for a null pointer): call(input pointers, output pointers), sync,

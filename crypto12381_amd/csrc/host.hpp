@@ -1,4 +1,4 @@
-// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip, api_ac_rbbs.hip, api_ac_rps.hip, api_mhac_bbs.hip): the context and its
+// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip, api_ac_rbbs.hip, api_ac_rps.hip, api_mhac_bbs.hip, api_mhac_iss.hip): the context and its
 // workspaces, and the idioms every entry point is written in — launch, slab (host_layouts.hpp), host form.  Everything in namespace c12381_host
 // has external linkage and hidden visibility: the units call each other's helpers, the library exports the C ABI alone.  The comment at each
 // declaration names the unit that defines it.
@@ -97,12 +97,12 @@ struct timed {
 
 // Host form.  The caller's inputs and outputs, (host pointer, bytes) each, laid out in WS_STAGE at 256-byte-aligned offsets.  stage() copies
 // every non-empty input in and hands back the device pointers (a null host pointer stays null); unstage() copies the outputs back after
-// the _dev call and ends with read_flag.  Up to 12 inputs and 4 outputs.  host_form: stage, the entry's _dev form on s.in[] / s.out[], unstage.
+// the _dev call and ends with read_flag.  Up to 12 inputs and 5 outputs.  host_form: stage, the entry's _dev form on s.in[] / s.out[], unstage.
 struct host_buf { const void* p; size_t bytes; };
 struct staging {
     const uint8_t* in[12] = {};
-    uint8_t* out[4] = {};
-    host_buf host_out[4] = {};
+    uint8_t* out[5] = {};
+    host_buf host_out[5] = {};
     size_t nout = 0;
 };
 int stage(c12381_ctx* c, staging& s, std::initializer_list<host_buf> ins, std::initializer_list<host_buf> outs);       // c12381_hip.hip

@@ -287,6 +287,53 @@ inline mhac_bbs_pres_slab mhac_bbs_pres_layout(void* base, size_t m, size_t t, s
     s.bytes = f.bytes;
     return s;
 }
+// The issuance entries (api_mhac_iss.hip).  attr and iss run k credentials of a chunk as k x nparties lanes (credential-major, the layout of
+// their per-party outputs); a chunk holds mhac_iss_chunk(nparties) credentials, so no launch exceeds 2^18 lanes.
+inline size_t mhac_iss_chunk(size_t nparties) { const size_t k = ((size_t)1 << 18) / nparties; return k ? k : 1; }
+// attr, per credential: the nPrv share columns of its nparties lanes: 32 nPrv nparties bytes
+struct mhac_iss_attr_slab { uint8_t* sc; size_t bytes; };
+inline mhac_iss_attr_slab mhac_iss_attr_layout(void* base, size_t k, size_t nparties, size_t nPrv) {
+    carver f(base, MHAC_BBS_PUB_BYTES);
+    mhac_iss_attr_slab s;
+    s.sc = f.take(32 * nPrv * nparties * k);
+    s.bytes = f.bytes;
+    return s;
+}
+// iss: gamma as 32 bytes and its range status in front (64 bytes for the chunk); per credential the nparties records of C decoded and their
+// statuses, the parse status, e, inverse(gamma + e), the t columns lambda, the nPub public columns, the nparties scalars -e_share, the t term columns
+// C[0] .. C[t-1] of the products, the product (then C_a), the public sum, A, A once per party, and A^(-e_share) (then D):
+// 353 + 321 nparties + 128 t + 32 nPub bytes
+struct mhac_iss_iss_slab { uint8_t *gam, *c96, *st_c, *st, *e32, *inv, *scl, *scp, *nes, *q96, *u96, *v96, *a96, *r96, *w96; size_t bytes; };
+inline mhac_iss_iss_slab mhac_iss_iss_layout(void* base, size_t k, size_t nparties, size_t t, size_t nPub) {
+    const size_t L = k * nparties;
+    carver f(base, MHAC_BBS_PUB_BYTES);
+    mhac_iss_iss_slab s;
+    s.gam = f.take(64); s.c96 = f.take(96 * L); s.st_c = f.take(L); s.st = f.take(k); s.e32 = f.take(32 * k); s.inv = f.take(32 * k);
+    s.scl = f.take(32 * t * k); s.scp = f.take(32 * nPub * k); s.nes = f.take(32 * L); s.q96 = f.take(96 * t * k); s.u96 = f.take(96 * k);
+    s.v96 = f.take(96 * k); s.a96 = f.take(96 * k); s.r96 = f.take(96 * L); s.w96 = f.take(96 * L);
+    s.bytes = f.bytes;
+    return s;
+}
+// group (no key: the slab starts at the workspace), per presentation: the t records of S as they arrive (columns) and decoded, their statuses, the t
+// columns lambda, the running product and one further point: 192 + 178 t bytes
+struct mhac_iss_group_slab { uint8_t *p49, *p96, *st_p, *sc, *u96, *v96; size_t bytes; };
+inline mhac_iss_group_slab mhac_iss_group_layout(void* base, size_t m, size_t t) {
+    carver f(base);
+    mhac_iss_group_slab s;
+    s.p49 = f.take(49 * t * m); s.p96 = f.take(96 * t * m); s.st_p = f.take(t * m); s.sc = f.take(32 * t * m); s.u96 = f.take(96 * m); s.v96 = f.take(96 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+// type, per presentation: the parse status, the nPub columns of the type list, C_rev, the sum over the hidden public positions, C_pub:
+// 289 + 32 nPub bytes
+struct mhac_iss_type_slab { uint8_t *st, *sca, *r96, *v96, *p96; size_t bytes; };
+inline mhac_iss_type_slab mhac_iss_type_layout(void* base, size_t m, size_t nPub) {
+    carver f(base, MHAC_BBS_PUB_BYTES);
+    mhac_iss_type_slab s;
+    s.st = f.take(m); s.sca = f.take(32 * nPub * m); s.r96 = f.take(96 * m); s.v96 = f.take(96 * m); s.p96 = f.take(96 * m);
+    s.bytes = f.bytes;
+    return s;
+}
 
 // ---------------------------------------------------------------- pairing work queue (WS_PAIR_ST; the GT power: WS_POW_ST)
 // The figures of the queue kernels (api_pair.hip asserts them against kernels.hpp): 21 pairings per wavefront group, 4 wavefronts per

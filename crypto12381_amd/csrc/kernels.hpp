@@ -13,6 +13,7 @@
 //   k_ac_rbbs.hip the AC-rbbs credential stages (ac_rbbs.hpp): the same, with the q_i hashes, the exponents of redact and a second pairing equation
 //   k_ac_rps.hip the AC-rps credential stages (ac_rps.hpp): the q_k hashes over points and indices, the exponents of pres, G2 subtraction
 //   k_mhac_bbs.hip the MHAC-bbs credential stages (mhac_bbs.hpp): the index sets, the transcript over revealed values, the threshold responses
+//   k_mhac_iss.hip the MHAC-bbs issuance stages (mhac_iss.hpp): the polynomial shares, the Lagrange columns, the row gather, the records and statuses
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -185,6 +186,20 @@ __global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_verify_prep_kernel(size_t n
 __global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_verify_finish_kernel(size_t n, size_t nrp, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* p96, const uint8_t* u49, const uint8_t* pub48, const uint8_t* c32, const uint8_t* okp, uint8_t* tr, uint8_t* ok, int* bad_flag);
 __global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_pres_prep_kernel(size_t n, size_t t, mhac_bbs_sets s, const uint8_t* A49, const uint8_t* D49, const uint8_t* crev49, const uint8_t* cpub49, const uint8_t* lam48, const uint8_t* eshare48, const uint8_t* ashare48, const uint8_t* pub48, const uint8_t* rnd, uint8_t* p49, uint8_t* scr, uint8_t* scu, uint8_t* sch, uint8_t* st);
 __global__ void __launch_bounds__(BLOCK, 2) mhac_bbs_pres_finish_kernel(size_t n, size_t t, mhac_bbs_sets s, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* st_p, const uint8_t* o96, const uint8_t* u96, const uint8_t* lam48, const uint8_t* eshare48, const uint8_t* ashare48, const uint8_t* pub48, const uint8_t* rnd, uint8_t* tr, uint8_t* fixed242, uint8_t* z48, uint8_t* zhp48, uint8_t* status, int* bad_flag);
+// k_mhac_iss.hip: MHAC-bbs attribute generation, issuance, group and type (mhac_iss.hpp; the sets, S, lambda and the type plan travel by value)
+struct mhac_iss_lambda;
+struct mhac_iss_parties_set;
+struct mhac_iss_type_plan;
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_attr_kernel(size_t k, size_t np, size_t t, mhac_bbs_sets s, const uint8_t* rnd, uint8_t* pub48, uint8_t* ashare48, uint8_t* sc);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_attr_finish_kernel(size_t L, size_t np, size_t nPrv, size_t nPub, size_t npub, const uint8_t* st_pub, uint8_t* pub48, uint8_t* ashare48, uint8_t* C49, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_iss_prep_kernel(size_t k, size_t np, size_t t, size_t nPub, mhac_iss_lambda lam, const uint8_t* sk48, const uint8_t* pub48, const uint8_t* rnd, uint8_t* gam, uint8_t* st, uint8_t* e32, uint8_t* scl, uint8_t* scp, uint8_t* nes, uint8_t* eshare48, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_cols_kernel(size_t k, size_t np, size_t t, const uint8_t* c96, uint8_t* q96);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_rep_kernel(size_t L, size_t np, const uint8_t* a96, uint8_t* r96);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_iss_finish_kernel(size_t L, size_t np, size_t npub, const uint8_t* st_pub, const uint8_t* gam, const uint8_t* st, const uint8_t* st_c, const uint8_t* a96, const uint8_t* w96, uint8_t* A49, uint8_t* eshare48, uint8_t* D49, uint8_t* status, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_group_prep_kernel(size_t n, size_t np, size_t t, size_t nPrv, mhac_iss_parties_set S, mhac_iss_lambda lam, const uint8_t* D49, const uint8_t* eshare48, const uint8_t* ashare48, uint8_t* p49, uint8_t* sc, uint8_t* lam48, uint8_t* eS48, uint8_t* aS48);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_group_finish_kernel(size_t n, size_t t, size_t nPrv, const uint8_t* st_p, const uint8_t* u96, uint8_t* Dg49, uint8_t* lam48, uint8_t* eS48, uint8_t* aS48, uint8_t* status);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_type_prep_kernel(size_t n, size_t nPub, mhac_iss_type_plan plan, const uint8_t* pub48, uint8_t* sca, uint8_t* st);
+__global__ void __launch_bounds__(BLOCK, 2) mhac_iss_type_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* r96, const uint8_t* p96, uint8_t* crev49, uint8_t* cpub49, uint8_t* status, int* bad_flag);
 // k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
 constexpr int TABLE_ARRAY_MAX = 32;
 struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };

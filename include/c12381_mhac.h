@@ -111,6 +111,94 @@ int c12381_mhac_bbs_pres_batch_dev(c12381_ctx* ctx, size_t n, size_t m, size_t t
                                    const uint8_t* eshare_48, const uint8_t* ashare_48, const uint8_t* crev_49, const uint8_t* cpub_49, const uint8_t* pub_48,
                                    const uint8_t* rnd, uint8_t* fixed_242, uint8_t* z_48, uint8_t* zhp_48, uint8_t* status);
 
+/* MHAC-bbs issuance: generate_attributes, cred_iss, make_pres_group, make_pres_type --------------------------------------------------------- */
+/* Everything that produces the inputs of c12381_mhac_bbs_pres_batch, so that a caller goes from the issuer's key to a verified presentation
+ * through this library alone: setup -> attr -> iss -> group -> type -> pres -> verify, device-resident in the _dev forms.  Every convention above
+ * and of c12381_ac.h holds: decoding (leading 0x00 = infinity, x taken mod p, no subgroup check), parse<Zp> (48 big-endian bytes below r), `^` =
+ * PAIR_G1mul, exact for every curve point; index sets (prv, rev, pub_idx, S) are HOST arrays in both forms, read before anything is launched;
+ * argument errors are checked before the empty-batch rule; a pp or used h record that does not decode makes every output byte 0xff and returns
+ * C12381_E_POINT (the _dev form reports it at the next c12381_sync); the caller's randomness is 32-byte values below 2^256, reduced mod r first, in
+ * the order the reference draws them.  NOT constant-time, and nothing is wiped, as c12381_mhac_bbs_pres_batch states.
+ *
+ * Parties: a credential is shared among nparties parties, any t of which present.  polynomial(x, a0, a) = a0 + sum_i a[i] x^(i + 1) is evaluated
+ * at x = 1 .. nparties.  nparties <= C12381_MHAC_PARTIES_MAX = 64: with t <= C12381_MHAC_T_MAX = 8 every power x^i the entries form is at most
+ * 64^7 = 2^42 < 2^53, so the reference's `(type)std::pow(x, i)` (zp_number.hpp:1100) is the exact integer power for every accepted shape; above 2^53
+ * the reference's own value is a rounded double and nothing could be exact against it.
+ * C12381_E_ARG, all four entries: t = 0, t > C12381_MHAC_T_MAX, t > nparties, nparties = 0 or > C12381_MHAC_PARTIES_MAX, m = 0 or
+ * m > C12381_G1_FIXED_SUM_MAX, an index out of range or repeated, a null pointer that is not explicitly allowed.
+ * Per-party arrays are credential-major: record i of credential j is at position j nparties + i.  attr and iss run a chunk of max(1, 2^18 /
+ * nparties) credentials at a time, so that no launch exceeds 2^18 lanes; group and type run chunks of 2^18 presentations.
+ *
+ * c12381_mhac_bbs_attr_batch: generate_attributes(pp, t, nparties, Prv, random) (generate_attributes.cpp:6-37).
+ *   rnd        per credential m + nPrv (t - 1) scalars: attr[0 .. m), then a; a[ii (t - 1) .. (ii + 1)(t - 1)) belongs to private attribute ii
+ *   share[k][ii] = polynomial(k + 1, attr[Prv[ii]], a[ii (t - 1) .. (ii + 1)(t - 1)))         k < nparties
+ *   C[k]       = prod_ii h[Prv[ii]]^share[k][ii]                                              nPrv = 0: infinity
+ * Outputs: pub_48 (n x nPub fields, attr at Pub, Pub the ascending complement of Prv; NULL allowed when nPub = 0), ashare_48 (n x nparties x nPrv
+ * fields, party-major: the layout pres reads its rows in; NULL allowed when nPrv = 0), C_49 (n x nparties records).  prv may be NULL when nPrv = 0.
+ * Only the Prv records of h are decoded.  The commitments are ONE fixed-base sum of n nparties lanes over nPrv bases (c12381_g1_mul_fixed_sum_batch:
+ * its tables, its generic route for a base outside G1).  No per-lane input can fail: there is no status output.
+ * Workspace: 32 nPrv nparties bytes per credential of a chunk, besides the workspaces of the entries used.
+ *
+ * c12381_mhac_bbs_iss_batch: cred_iss(pp, sk, t, commitment, public_indexes, public_attributes, random) (cred_iss.cpp:43-85).
+ *   pub_idx    the reference's public_indexes in the caller's order, nPub <= m distinct indices below m: pub_a[ii] belongs to h[pub_idx[ii]]
+ *              (NULL allowed when nPub = 0, and pub_48 with it)
+ *   sk_48      the issuer's gamma, ONE field for the batch;  C_49 n x nparties records;  pub_48 n x nPub fields
+ *   rnd        per credential t scalars: e, then the t - 1 coefficients a
+ *   C_a        = g1 * prod_(i < t) C[i]^lambda_i * prod_ii h[pub_idx[ii]]^pub_a[ii]          lambda_i = prod_(j != i) (-x_j / (x_i - x_j)), x = 1 .. t
+ *   A          = C_a^inverse(gamma + e)                                                      inverse(0) = 0: A is then infinity
+ *   e_share[i] = polynomial(i + 1, e, a)                                                     i < nparties
+ *   D[i]       = C[i] * A^(-e_share[i])                                                      the Zp negation, -0 = 0
+ * Each C[i] is an unchecked per-lane point, so each C[i]^lambda_i is a multiply of its own (products of at most C12381_G1_MUL_SUM_MAX terms joined
+ * by additions, as in pres); the public terms are one fixed-base sum with addend g1; inverse(gamma + e) is the simultaneous inversion of
+ * c12381_zp_op_batch; the D column is one generic G1 column of n nparties lanes.
+ * Outputs: A_49 (n records), eshare_48 (n x nparties fields), D_49 (n x nparties records), status (n bytes).
+ * Status: status[j] = 0, or 0xff where the reference would throw: one of the credential's nparties C records does not decode, or a public value is
+ * >= r.  That credential's A, e_share and D bytes are then all 0xff and the other credentials are untouched.  sk_48 >= r: every output byte is 0xff
+ * and the call returns C12381_E_ARG (the _dev form at the next c12381_sync) — the rule of c12381_bbs04_open_batch for gmsk.
+ * Workspace: 353 + 321 nparties + 128 t + 32 nPub bytes per credential of a chunk, besides the workspaces of the entries used.
+ *
+ * c12381_mhac_bbs_group_batch: make_pres_group(creds, S) (make_pres_group.cpp:6-21), and the selection of the rows of S that pres leaves to the caller.
+ *   S          t distinct party indices below nparties, in the caller's order; x[k] = S[k] + 1
+ *   lambda[k]  = prod_(y != k) (-x[y] / (x[k] - x[y]))                                        the same for every presentation of the batch
+ *   D          = prod_k D_share[S[k]]^lambda[k]                                               per-term multiplies, as above
+ * Inputs: D_49 (n x nparties records, of which only the rows of S are read), eshare_48 (n x nparties fields), ashare_48 (n x nparties x nPrv fields).
+ * Outputs: lam_48 (n x t fields — per presentation, because that is what pres takes), Dg_49 (n records), eS_48 (n x t fields), aS_48 (n x t x nPrv
+ * fields), status (n bytes).  eS_48 and aS_48 are the rows of S gathered in the order of S, copied verbatim with no range check (pres checks them);
+ * each may be NULL together with its input (one of the pair NULL and the other not: C12381_E_ARG); with nPrv = 0 ashare_48 and aS_48 are not looked
+ * at.  nPrv > C12381_G1_FIXED_SUM_MAX: C12381_E_ARG.
+ * Status: 0, or 0xff where a D record of S does not decode; that presentation's D, lambda and gathered rows are then 0xff bytes.  There is no pp:
+ * the entry never returns C12381_E_POINT.
+ * Workspace: 192 + 178 t bytes per presentation of a chunk, besides the workspaces of the entries used.
+ *
+ * c12381_mhac_bbs_type_batch: make_pres_type(pp, Rev, Prv, public_attributes) (make_pres_type.cpp:6-38).  The sets are those of verify and pres.
+ *   C_rev      = g1 * prod_(ii in RevPub) h[Pub[ii]]^pub_a[ii]
+ *   C_pub      = C_rev * prod_(ii in PubHid) h[Pub[ii]]^pub_a[ii]                              PubHid: the positions of Pub whose attribute is in Hid
+ * pub_48: the WHOLE public span, n x nPub fields in Pub order, every field range-checked (NULL allowed when nPub = 0).  Only the Pub records of h are
+ * decoded; they form ONE base list, the revealed positions in front, and the two sums run over its two ranges; an empty range leaves its addend.
+ * Outputs: crev_49, cpub_49 (n records each), status (n bytes): 0, or 0xff — and both records 0xff bytes — where a public value is >= r.
+ * Workspace: 289 + 32 nPub bytes per presentation of a chunk, besides the workspaces of the entries used. */
+#define C12381_MHAC_PARTIES_MAX 64
+int c12381_mhac_bbs_attr_batch(c12381_ctx* ctx, size_t n, size_t m, size_t t, size_t nparties, size_t nPrv, const uint32_t* prv, const uint8_t* pp_146,
+                               const uint8_t* h_49, const uint8_t* rnd, uint8_t* pub_48, uint8_t* ashare_48, uint8_t* C_49);
+int c12381_mhac_bbs_attr_batch_dev(c12381_ctx* ctx, size_t n, size_t m, size_t t, size_t nparties, size_t nPrv, const uint32_t* prv, const uint8_t* pp_146,
+                                   const uint8_t* h_49, const uint8_t* rnd, uint8_t* pub_48, uint8_t* ashare_48, uint8_t* C_49);
+int c12381_mhac_bbs_iss_batch(c12381_ctx* ctx, size_t n, size_t m, size_t t, size_t nparties, size_t nPub, const uint32_t* pub_idx, const uint8_t* pp_146,
+                              const uint8_t* h_49, const uint8_t* sk_48, const uint8_t* C_49, const uint8_t* pub_48, const uint8_t* rnd, uint8_t* A_49,
+                              uint8_t* eshare_48, uint8_t* D_49, uint8_t* status);
+int c12381_mhac_bbs_iss_batch_dev(c12381_ctx* ctx, size_t n, size_t m, size_t t, size_t nparties, size_t nPub, const uint32_t* pub_idx, const uint8_t* pp_146,
+                                  const uint8_t* h_49, const uint8_t* sk_48, const uint8_t* C_49, const uint8_t* pub_48, const uint8_t* rnd, uint8_t* A_49,
+                                  uint8_t* eshare_48, uint8_t* D_49, uint8_t* status);
+int c12381_mhac_bbs_group_batch(c12381_ctx* ctx, size_t n, size_t nparties, size_t t, const uint32_t* S, size_t nPrv, const uint8_t* D_49,
+                                const uint8_t* eshare_48, const uint8_t* ashare_48, uint8_t* lam_48, uint8_t* Dg_49, uint8_t* eS_48, uint8_t* aS_48,
+                                uint8_t* status);
+int c12381_mhac_bbs_group_batch_dev(c12381_ctx* ctx, size_t n, size_t nparties, size_t t, const uint32_t* S, size_t nPrv, const uint8_t* D_49,
+                                    const uint8_t* eshare_48, const uint8_t* ashare_48, uint8_t* lam_48, uint8_t* Dg_49, uint8_t* eS_48, uint8_t* aS_48,
+                                    uint8_t* status);
+int c12381_mhac_bbs_type_batch(c12381_ctx* ctx, size_t n, size_t m, size_t nPrv, const uint32_t* prv, size_t nRev, const uint32_t* rev, const uint8_t* pp_146,
+                               const uint8_t* h_49, const uint8_t* pub_48, uint8_t* crev_49, uint8_t* cpub_49, uint8_t* status);
+int c12381_mhac_bbs_type_batch_dev(c12381_ctx* ctx, size_t n, size_t m, size_t nPrv, const uint32_t* prv, size_t nRev, const uint32_t* rev,
+                                   const uint8_t* pp_146, const uint8_t* h_49, const uint8_t* pub_48, uint8_t* crev_49, uint8_t* cpub_49, uint8_t* status);
+
 #ifdef __cplusplus
 }
 #endif
