@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-UNITS = ["c12381_hip.hip", "api_pair.hip", "api_ps.hip", "api_bbs.hip", "api_bbs04.hip", "k_g1.hip", "k_g1sum.hip", "k_g2gt.hip", "k_g2h.hip", "k_pair3.hip", "k_hash_zp.hip", "k_fixed.hip", "k_pairk.hip", "k_bbs04.hip", "k_ps.hip", "api_ac_bbs.hip", "k_ac_bbs.hip", "api_ac_rbbs.hip", "k_ac_rbbs.hip", "api_ac_rps.hip", "k_ac_rps.hip", "api_mhac_bbs.hip", "k_mhac_bbs.hip", "api_mhac_iss.hip", "k_mhac_iss.hip"]
+UNITS = ["c12381_hip.hip", "api_pair.hip", "api_ps.hip", "api_bbs.hip", "api_bbs04.hip", "k_g1.hip", "k_g1sum.hip", "k_g2gt.hip", "k_g2h.hip", "k_pair3.hip", "k_hash_zp.hip", "k_fixed.hip", "k_pairk.hip", "k_bbs04.hip", "k_ps.hip", "api_ac_bbs.hip", "k_ac_bbs.hip", "api_ac_rbbs.hip", "k_ac_rbbs.hip", "api_ac_rps.hip", "k_ac_rps.hip", "api_mhac_bbs.hip", "k_mhac_bbs.hip", "api_mhac_iss.hip", "k_mhac_iss.hip", "api_ac_issue.hip", "k_ac_issue.hip"]
 EXP_UNITS = ["c12381_hip.hip", "api_pair.hip", "k_g2gt.hip"]              # the units that test C12381_EXPERIMENTS
 EXP_ONLY_UNITS = ["k_fp_raw.hip"]                           # linked into the experiments library alone: the raw-limb test kernel of the Fp / Fp2 leaf
 LIB = os.path.join(HERE, "lib", "libc12381_hip.so")
@@ -70,7 +70,7 @@ VALIDATED_COMPILER = "AMD clang version 22.0.0git"          # ROCm 7.2.0
 
 def _headers():
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))] + [
-        os.path.join(os.path.dirname(HERE), "include", f) for f in ("c12381_hip.h", "c12381_ac.h", "c12381_mhac.h")]
+        os.path.join(os.path.dirname(HERE), "include", f) for f in ("c12381_hip.h", "c12381_ac.h", "c12381_mhac.h", "c12381_ac_issue.h")]
 
 
 def _stale(target: str, deps) -> bool:

@@ -173,6 +173,12 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz] + [vp] * 8
         for name in ("c12381_mhac_bbs_type_batch", "c12381_mhac_bbs_type_batch_dev"):
             getattr(lib, name).argtypes = [vp, sz, sz, sz, vp, sz, vp] + [vp] * 6
+        for name in ("c12381_ac_bbs_issue_batch", "c12381_ac_bbs_issue_batch_dev", "c12381_ac_rbbs_issue_batch", "c12381_ac_rbbs_issue_batch_dev"):      # include/c12381_ac_issue.h
+            getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 7
+        for name in ("c12381_ac_rps_user_keygen_batch", "c12381_ac_rps_user_keygen_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz] + [vp] * 4
+        for name in ("c12381_ac_rps_issue_batch", "c12381_ac_rps_issue_batch_dev"):
+            getattr(lib, name).argtypes = [vp, sz, sz] + [vp] * 8
         if hasattr(lib, "c12381_exp_fp_raw_batch"):           # experiments library only: raw-limb test entry of the Fp / Fp2 leaf (tests/test_gpu_fp_raw.py)
             lib.c12381_exp_fp_raw_batch.argtypes = [vp, ci, sz, ci, ci, vp, vp, vp]
         _lib = lib
@@ -899,6 +905,36 @@ class Context:
         (pa, nP), (ra, nR) = self._idx(prv), self._idx(rev)
         n = len(pub48) // (48 * (m - nP)) if n is None else n
         return self._mhac_call("c12381_mhac_bbs_type_batch", (n, m, nP, pa, nR, ra), [pp146, h49, pub48 or None], [49 * n, 49 * n, n], strict, dev)
+
+    def ac_bbs_issue(self, sk48: bytes, pk243: bytes, Y49: bytes, attr48: bytes, rnd32: bytes, strict: bool = True, dev: bool = False):
+        """AC-bbs issue from the wire formats (include/c12381_ac_issue.h): the issuer's key serialize(x) (48 B), pk.fixed_part (243 B), pk.Y (nattr x
+        49 B), the holders' whole attribute spans (nattr x 48 B each) and the caller's randomness (w: 32 B per credential) -> (n x 97-byte
+        Signature serialize(A, w), n status bytes: 0, or 0xff — and a record of 0xff — where an attribute is >= r).  x >= r is C12381_E_ARG, a
+        key that does not decode C12381_E_POINT (every byte 0xff): the latter raised when strict, returned as bytes otherwise.  Not constant-time."""
+        n, nattr = len(rnd32) // 32, len(Y49) // 49
+        return self._mhac_call("c12381_ac_bbs_issue_batch", (n, nattr), [sk48, pk243, Y49, attr48, rnd32], [97 * n, n], strict, dev)
+
+    def ac_rbbs_issue(self, sk96: bytes, pk243: bytes, Y49: bytes, attr48: bytes, rnd32: bytes, strict: bool = True, dev: bool = False):
+        """AC-rbbs issue: as ac_bbs_issue with the key serialize(x, y) (96 B, both fields range-checked) and the 2 nattr records of pk.Y, of
+        which the first nattr are read."""
+        n, nattr = len(rnd32) // 32, len(Y49) // 49 // 2
+        return self._mhac_call("c12381_ac_rbbs_issue_batch", (n, nattr), [sk96, pk243, Y49, attr48, rnd32], [97 * n, n], strict, dev)
+
+    def ac_rps_user_keygen(self, pk243: bytes, rnd32: bytes, strict: bool = True, dev: bool = False):
+        """AC-rps user_keygen: pk.fixed_part (243 B) and the caller's randomness (usk: 32 B per key pair, reduced mod r) -> (n x 48-byte
+        UserSecretKey, n x 49-byte UserPublicKey g^usk).  A pk that does not decode is C12381_E_POINT (every byte 0xff): raised when strict,
+        returned as bytes otherwise.  Not constant-time."""
+        n = len(rnd32) // 32
+        return self._mhac_call("c12381_ac_rps_user_keygen_batch", (n,), [pk243, rnd32], [48 * n, 49 * n], strict, dev)
+
+    def ac_rps_issue(self, sk96: bytes, pk243: bytes, tY97: bytes, upk49: bytes, attr48: bytes, rnd32: bytes, strict: bool = True, dev: bool = False):
+        """AC-rps issue from the wire formats: the issuer's key serialize(x, y) (96 B), pk.fixed_part, pk.tilde_Y ((nattr + 1) x 97 B), one
+        UserPublicKey per credential (49 B each), the holders' whole attribute spans and the caller's randomness (alpha: 32 B per credential)
+        -> (n x 195-byte Signature serialize(h, sigma, tilde_M), n status bytes: 0, or 0xff — and a record of 0xff — where an attribute is >= r
+        or upk does not decode).  x or y >= r is C12381_E_ARG, a key that does not decode C12381_E_POINT (every byte 0xff): the latter raised
+        when strict, returned as bytes otherwise.  Not constant-time."""
+        n, nattr = len(rnd32) // 32, len(tY97) // 97 - 1
+        return self._mhac_call("c12381_ac_rps_issue_batch", (n, nattr), [sk96, pk243, tY97, upk49, attr48, rnd32], [195 * n, n], strict, dev)
 
     def _rps_dev(self, call, ins, out_sizes, strict):
         """the _dev form of an AC-rps entry on device copies of `ins` (bytes, or None for a null pointer): call(input pointers, output pointers), sync,

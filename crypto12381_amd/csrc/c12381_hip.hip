@@ -124,7 +124,7 @@ int read_flag(c12381_ctx* c) {
         return C12381_E_INTERNAL;
     }
     if (c->h_flag[2]) {
-        std::snprintf(c->err, sizeof c->err, "a secret scalar is not below r (bbs04 open: gmsk; PS sign: x, y; MHAC-bbs iss: sk)");
+        std::snprintf(c->err, sizeof c->err, "a secret scalar is not below r (bbs04 open: gmsk; PS sign: x, y; MHAC-bbs iss: sk; AC issue: sk)");
         return C12381_E_ARG;
     }
     return c->h_flag[0] ? C12381_E_POINT : 0;

@@ -1,4 +1,4 @@
-// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip, api_ac_rbbs.hip, api_ac_rps.hip, api_mhac_bbs.hip, api_mhac_iss.hip): the context and its
+// Host side shared by the units behind the C ABI (c12381_hip.hip, api_pair.hip, api_ps.hip, api_bbs.hip, api_bbs04.hip, api_ac_bbs.hip, api_ac_rbbs.hip, api_ac_rps.hip, api_mhac_bbs.hip, api_mhac_iss.hip, api_ac_issue.hip): the context and its
 // workspaces, and the idioms every entry point is written in — launch, slab (host_layouts.hpp), host form.  Everything in namespace c12381_host
 // has external linkage and hidden visibility: the units call each other's helpers, the library exports the C ABI alone.  The comment at each
 // declaration names the unit that defines it.
@@ -29,7 +29,7 @@ struct c12381_ctx {
     // (host forms are synchronous), so a host form's slab is never overwritten while the call still needs it.
     enum { WS_TAB, WS_PROJ, WS_PREF, WS_STAGE, WS_RED0, WS_RED1, WS_BBS_Q, WS_BBS_B, WS_BBS_WIRE,
            WS_PAIR_ST, WS_POW_ST, WS_FQ_W, WS_FQ_P, WS_FB_G2, WS_FB_G1_0, WS_FB_G1_1, WS_FB_G1_2, WS_FB_G1_3, WS_FB_G1_4, WS_MSM_PTS, WS_MSM_K0, WS_MSM_K1, WS_MSM_V0, WS_MSM_V1, WS_MSM_TMP, WS_MSM_RNG, WS_MSM_BK, WS_MSM_ORD, WS_MSM_OVF, WS_DEC1, WS_DEC2, WS_GT_POW,
-           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_PS, WS_AC_BBS, WS_AC_RBBS, WS_AC_RPS, WS_MHAC_BBS, WS_COUNT };
+           WS_FQ_K, WS_FQK_PTS, WS_FQK_G1, WS_BBS04, WS_FB_G1_SUM, WS_FB_G2_SUM, WS_PS, WS_AC_BBS, WS_AC_RBBS, WS_AC_RPS, WS_MHAC_BBS, WS_AC_ISSUE, WS_COUNT };
     void* ws[WS_COUNT] = {nullptr};
     size_t ws_bytes[WS_COUNT] = {0};
     int* d_flag = nullptr;

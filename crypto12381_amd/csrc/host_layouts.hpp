@@ -335,6 +335,43 @@ inline mhac_iss_type_slab mhac_iss_type_layout(void* base, size_t m, size_t nPub
     return s;
 }
 
+// ---------------------------------------------------------------- AC issuance (WS_AC_ISSUE, api_ac_issue.hip): every slab starts behind the public block
+// The public block is ac_rps_public's, read as: g96 = g and g2 = tilde_g, tilde_X decoded straight from pk.fixed_part; y96 = Y[0 .. nattr) of pk.Y
+// (AC-bbs / AC-rbbs) and ty192 = tilde_Y[0 .. nattr) of pk.tilde_Y (AC-rps), decoded where they lie in the key, in attribute order; st = the
+// statuses g, tilde_g, tilde_X, then the nattr used records (user_keygen: the first three alone)
+constexpr size_t AC_ISSUE_PUB_BYTES = AC_RPS_PUB_BYTES;
+// AC-bbs / AC-rbbs issue, per credential of a chunk: the nattr attribute columns, w, x + w, its inverse, the parse status, the sum g * prod Y_i^a_i, A:
+// 289 + 32 nattr bytes
+struct ac_issue_bbs_slab { uint8_t *sca, *w32, *d32, *inv, *st, *b96, *a96; size_t bytes; };
+inline ac_issue_bbs_slab ac_issue_bbs_layout(void* base, size_t m, size_t nattr) {
+    carver f(base, AC_ISSUE_PUB_BYTES);
+    ac_issue_bbs_slab s;
+    s.sca = f.take(32 * nattr * m); s.w32 = f.take(32 * m); s.d32 = f.take(32 * m); s.inv = f.take(32 * m); s.st = f.take(m); s.b96 = f.take(96 * m);
+    s.a96 = f.take(96 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+// AC-rps user_keygen, per key pair: usk as the scalar of g: 32 bytes
+struct ac_issue_keygen_slab { uint8_t* sc; size_t bytes; };
+inline ac_issue_keygen_slab ac_issue_keygen_layout(void* base, size_t m) {
+    carver f(base, AC_ISSUE_PUB_BYTES);
+    ac_issue_keygen_slab s;
+    s.sc = f.take(32 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+// AC-rps issue, per credential: the nattr attribute columns, alpha, the scalars x + ym | alpha y^(nattr+1) of the k = 2 product, the parse status, upk's
+// decoding status, the terms h | Z of the product, the encodings h | sigma, tilde_M encoded: 485 + 32 nattr bytes
+struct ac_issue_rps_slab { uint8_t *sca, *al32, *sc2, *st, *st_z, *q96, *e49, *tm97; size_t bytes; };
+inline ac_issue_rps_slab ac_issue_rps_layout(void* base, size_t m, size_t nattr) {
+    carver f(base, AC_ISSUE_PUB_BYTES);
+    ac_issue_rps_slab s;
+    s.sca = f.take(32 * nattr * m); s.al32 = f.take(32 * m); s.sc2 = f.take(2 * 32 * m); s.st = f.take(m); s.st_z = f.take(m); s.q96 = f.take(2 * 96 * m);
+    s.e49 = f.take(2 * 49 * m); s.tm97 = f.take(97 * m);
+    s.bytes = f.bytes;
+    return s;
+}
+
 // ---------------------------------------------------------------- pairing work queue (WS_PAIR_ST; the GT power: WS_POW_ST)
 // The figures of the queue kernels (api_pair.hip asserts them against kernels.hpp): 21 pairings per wavefront group, 4 wavefronts per
 // workgroup, a grid that fills the machine at 2 wavefronts per SIMD, and a queued group's state block in the tagged / the fenced form.

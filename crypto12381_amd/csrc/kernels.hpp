@@ -14,6 +14,7 @@
 //   k_ac_rps.hip the AC-rps credential stages (ac_rps.hpp): the q_k hashes over points and indices, the exponents of pres, G2 subtraction
 //   k_mhac_bbs.hip the MHAC-bbs credential stages (mhac_bbs.hpp): the index sets, the transcript over revealed values, the threshold responses
 //   k_mhac_iss.hip the MHAC-bbs issuance stages (mhac_iss.hpp): the polynomial shares, the Lagrange columns, the row gather, the records and statuses
+//   k_ac_issue.hip the AC issuance stages (ac_issue.hpp): the issuer's scalars — x + w; the Horner sum and the power of y —, the records and statuses
 // c12381_hip.hip (context, workspaces, C ABI) launches them.  Every kernel is built for 2 waves per SIMD
 // (__launch_bounds__(BLOCK, 2)): the field routines are not inlined and get the full 256-VGPR budget.
 #pragma once
@@ -200,6 +201,13 @@ __global__ void __launch_bounds__(BLOCK, 2) mhac_iss_group_prep_kernel(size_t n,
 __global__ void __launch_bounds__(BLOCK, 2) mhac_iss_group_finish_kernel(size_t n, size_t t, size_t nPrv, const uint8_t* st_p, const uint8_t* u96, uint8_t* Dg49, uint8_t* lam48, uint8_t* eS48, uint8_t* aS48, uint8_t* status);
 __global__ void __launch_bounds__(BLOCK, 2) mhac_iss_type_prep_kernel(size_t n, size_t nPub, mhac_iss_type_plan plan, const uint8_t* pub48, uint8_t* sca, uint8_t* st);
 __global__ void __launch_bounds__(BLOCK, 2) mhac_iss_type_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* st, const uint8_t* r96, const uint8_t* p96, uint8_t* crev49, uint8_t* cpub49, uint8_t* status, int* bad_flag);
+// k_ac_issue.hip: AC-bbs / AC-rbbs / AC-rps credential issuance and AC-rps user_keygen (ac_issue.hpp)
+__global__ void __launch_bounds__(BLOCK, 2) ac_issue_bbs_prep_kernel(size_t n, size_t nattr, size_t nsk, const uint8_t* sk48, const uint8_t* attr48, const uint8_t* rnd32, uint8_t* sca, uint8_t* w32, uint8_t* d32, uint8_t* st, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_issue_bbs_finish_kernel(size_t n, size_t npub, size_t nsk, const uint8_t* st_pub, const uint8_t* sk48, const uint8_t* st, const uint8_t* a96, const uint8_t* w32, uint8_t* sig97, uint8_t* status, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_issue_keygen_prep_kernel(size_t n, const uint8_t* rnd32, uint8_t* sc);
+__global__ void __launch_bounds__(BLOCK, 2) ac_issue_keygen_finish_kernel(size_t n, const uint8_t* st_pub, const uint8_t* sc, uint8_t* usk48, uint8_t* upk49, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_issue_rps_prep_kernel(size_t n, size_t nattr, const uint8_t* sk96, const uint8_t* attr48, const uint8_t* rnd32, uint8_t* sca, uint8_t* al32, uint8_t* sc2, uint8_t* st, int* bad_flag);
+__global__ void __launch_bounds__(BLOCK, 2) ac_issue_rps_finish_kernel(size_t n, size_t npub, const uint8_t* st_pub, const uint8_t* sk96, const uint8_t* st, const uint8_t* st_z, const uint8_t* e49, const uint8_t* tm97, uint8_t* sig195, uint8_t* status, int* bad_flag);
 // k_fixed.hip: device-built tables in arrays of 1 .. TABLE_ARRAY_MAX, tab_stride dwords apart; the cached points travel by value
 constexpr int TABLE_ARRAY_MAX = 32;
 struct table_points { const uint8_t* p[TABLE_ARRAY_MAX]; };
